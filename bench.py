@@ -5,6 +5,11 @@ single_dim 512, pair_dim 64, 4 folding blocks, T = 1000 -- on N GPUs of one node
 
     python bench.py [--gpus N --steps K --warmup W]          # N > 1: starts N ranks itself (see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py --full ...                               # + roofline, other arithmetic, CPU baseline, shard check
+    python bench.py --dump-outputs DIR ...                   # + the last step's samples as DIR/<name>.npy
+
+A plain run sets up, warms up, times the steps and prints the line; ``roofline``, ``cpu_baseline``, the other arithmetic's
+step time and ``sharded_sample_check`` are null unless ``--full`` is given.
 
 One process per GPU over RCCL (backend "nccl").  Samples of ``sample()`` never interact, so the path shards by
 global sample index with no collective inside the loop (weak scaling: every rank runs ``--samples-per-gpu``
@@ -67,6 +72,11 @@ def parse_args():
     ap.add_argument("--samples-per-gpu", type=int, default=1)
     ap.add_argument("--residues", type=int, default=256)
     ap.add_argument("--atoms", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the dominant kernel's roofline (with its rocprofv3 --pmc passes), the other arithmetic's "
+                         "step time, the CPU baseline and, under a launcher, the sharded-sampling check")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps: the samples the last step handed back (positions, logits) as float32 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-traffic", action="store_true", help="skip the child rocprofv3 --pmc passes behind roofline.traffic")
@@ -171,6 +181,25 @@ def measure_traffic(a):
              "kernel_cycles_profiled": int(cyc)}
     return traffic, (f"measured in this run: child rocprofv3 --pmc passes, FETCH_SIZE {vals['FETCH_SIZE']:.0f} KiB x2 (gfx950 wide-read "
                      f"correction) + WRITE_SIZE {vals['WRITE_SIZE']:.0f} KiB per launch"), pipes
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, **arrays):
+    """``out_dir/<name>.npy`` (float32) for every array: the samples the timed path returns, leading axis = sample.  Above
+    DUMP_CAP_BYTES in all, the same fixed, seeded subset of the samples is written for every array."""
+    import numpy as np
+    import torch
+    n = next(iter(arrays.values())).shape[0]
+    total = sum(t.numel() for t in arrays.values()) * 4
+    keep = None
+    if total > DUMP_CAP_BYTES:
+        keep = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:max(1, n * DUMP_CAP_BYTES // total)].sort().values
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        np.save(os.path.join(out_dir, f"{name}.npy"), (t if keep is None else t[keep]).numpy())
 
 
 def cpu_baseline(a, N, margs, params):
@@ -292,10 +321,12 @@ def main():
     # the guard of the split-16 default (diffusion_model.ReverseDiffusion.finite): the sticky flag the step-boundary kernel keeps
     # over ALL steps of the loop or'ed with a check of the final state -- one host read, outside the timed region
     finite = bool(loop.finite() and torch.isfinite(pos_all).all() and torch.isfinite(logits_all).all())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, positions=pos_all, logits=logits_all)
 
     # ---- N > 1: the product's sharded sampler end to end, against single-rank runs (bit-identical by construction) ----
     shard_check = None
-    if dist is not None and not a.no_shard_check:
+    if a.full and dist is not None and not a.no_shard_check:
         model.num_steps, model.setup_schedule = 24, False        # a short loop: this is a correctness check, not the timed region
         one = batch_to(synthetic_batch([(a.atoms, a.residues)], seed=0), dev)
         c0 = time.perf_counter()
@@ -322,7 +353,7 @@ def main():
 
     # ---- dominant kernel, measured live with HIP events on the launch stream (rank 0) ----
     roofline = None
-    if rank == 0:
+    if a.full and rank == 0:
         kus = dominant_kernel(model, loop.mask, bpg, N, dev, reps=20)
         kfl = tri_attn_core_flops(bpg, N, P)
         ach = kfl / (kus * 1e-6) / 1e12
@@ -370,7 +401,7 @@ def main():
 
     # ---- the same loop in the other arithmetic (rank 0, single process): one line shows both ----
     other_ms = None
-    if rank == 0 and world == 1 and not a.no_traffic:
+    if a.full and rank == 0 and world == 1 and not a.no_traffic:
         cur = _lib.lib().prd_get_gemm_mode()
         _lib.lib().prd_set_gemm_mode(1 - cur)
         try:
@@ -388,7 +419,7 @@ def main():
             _lib.lib().prd_set_gemm_mode(cur)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(a, N, margs, params)
 
     if rank == 0:

@@ -58,7 +58,7 @@ def test_bench_under_one_rank_rccl_launcher():
     """bench.py exactly as the driver launches it for N > 1, with one rank: RCCL init, the samples' all_gather inside the timed
     region, and the shard check with a batch of two complexes of the bench shape (N = 320) per GPU."""
     line = _torchrun_one_rank([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--samples-per-gpu", "2",
-                               "--no-cpu-baseline", "--no-traffic"], 29621)
+                               "--full", "--no-cpu-baseline", "--no-traffic"], 29621)
     assert line["n_gpus"] == 1 and line["config"]["backend"] == "nccl (RCCL)"
     chk = line["config"]["sharded_sample_check"]
     assert chk["identical_to_same_batch_size_recompute"] is True and chk["batch_size"] == 2 and chk["rel_l2_vs_sample_drawn_alone"] < 2e-5

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${TAG}_summaries
 mkdir -p $OUT
 db() { find "$1" -name "*.db" | head -1; }
-B="python3 bench.py --no-cpu-baseline --no-traffic"
+B="python3 bench.py --full --no-cpu-baseline --no-traffic"
 # (a) kernel trace of the headline config, (b) one-step breakdown
 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_trace -o t -- $B --steps 20 --warmup 2 > gpurun_out/${TAG}_trace.log 2>&1
 python tools/rocprof_summary.py $(db gpurun_out/${TAG}_trace) $OUT/${TAG}_kernel_stats.txt > /dev/null

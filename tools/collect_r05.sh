@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${TAG}_summaries
 mkdir -p $OUT
 db() { find "$1" -name "*.db" | head -1; }
-B="python3 bench.py --no-cpu-baseline --no-traffic"
+B="python3 bench.py --full --no-cpu-baseline --no-traffic"
 PMCSETS=("FETCH_SIZE" "WRITE_SIZE" \
          "SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY GRBM_GUI_ACTIVE" \
          "SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_BUSY_CYCLES")
@@ -48,7 +48,7 @@ cat $OUT/${TAG}_n769_roofline.txt
   $B --residues 1000 --atoms 24 --steps 20 --warmup 2 2>/dev/null
   PRD_GEMM_MODE=fp32 $B 2>/dev/null
 } > $OUT/${TAG}_bench_lines.jsonl
-python bench.py > $OUT/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err
+python bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
 python tools/op_bench.py > $OUT/${TAG}_op_bench.txt 2>&1
 python tools/spa_bench.py > $OUT/${TAG}_spa_bench.txt 2>&1
 python tools/ta_long_bench.py 449 640 769 832 961 2>&1 | grep -v amdgpu.ids > $OUT/${TAG}_ta_long_bench.txt

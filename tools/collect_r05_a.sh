@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/r05_summaries
 mkdir -p $OUT
 db() { find "$1" -name "*.db" | head -1; }
-B="python3 bench.py --no-cpu-baseline --no-traffic"
+B="python3 bench.py --full --no-cpu-baseline --no-traffic"
 PRD_LIB=protein_redesign_amd/libprd_hip_timing.so python tools/ta3_timing.py 320 > $OUT/r05_tri_attn_v3_phases.txt 2>&1
 prof() {  # $1 prefix, rest: bench args
   local PFX=$1; shift
