@@ -483,6 +483,25 @@ size_t prd_spa_attn_core_workspace(int b, int N, int H, int c);
 int prd_spa_attn_core(float* o, const float* qkvg, int ldq, const float* bias, const float* mask,
                       int b, int N, int H, int c, float* ws, size_t ws_bytes, int arith, hipStream_t stream);
 
+/* Triangle attention for head layouts other than 4 heads x 16 channels (csrc/prd_tri_heads.hip): the contract of
+ * prd_tri_attn_core with og of width H c -- og[b,i,j,h c:(h+1) c] = sigmoid(LN(x_j) Wg_h^T + bg_h) * sum_k softmax_k(s_jk) V_h[k],
+ * s_jk = (LN(x_j) Wq_h^T / sqrt(c)) . (LN(x_k) Wk_h^T) replaced by -2^15 where mask[b,i] mask[b,k] < 0.5 (a row whose keys are all
+ * masked averages V over all N keys), x = pair[b,i,:,:] ("starting") or pair[b,:,i,:] ("ending"), og [b,N,N,H c] in the pair's own
+ * (i, j) layout in both orientations, so the output projection is a plain row GEMM (K = H c).  LN without affine parameters.
+ * Supported: 1 <= H <= 8, c a multiple of 4 with 4 <= c <= 64, P in {32, 64}, any N >= 1 (keys stream through the LDS with an online
+ * softmax: no row limit; one launch).  Arithmetic: fp32-input MFMA in BOTH modes -- the `arith` word is validated, its split bit is
+ * ignored.  Also accepts H = 4, c = 16 (same contract as the tuned kernels, which the model keeps for that layout).
+ * prd_tri_attn_heads_supported: 1 / 0, host-only.  prd_tri_attn_heads_workspace_bytes: bytes of `ws` = og's b N N H c floats plus
+ * any softmax statistics (none in the single-launch form); 0 outside the supported set.  og may point to the start of ws (as
+ * ops.tri_attn passes it) or elsewhere.  prd_tri_attn_core_heads: PRD_ERR_ARG for a NULL pointer or b, N <= 0,
+ * PRD_ERR_UNSUPPORTED outside the set above, PRD_ERR_WORKSPACE when ws_bytes is short, PRD_ERR_ALIGN unless og and pair are
+ * 16-byte aligned; nothing is launched on an error.  Offsets are 64-bit. */
+int prd_tri_attn_heads_supported(int N, int P, int H, int c, int arith);
+size_t prd_tri_attn_heads_workspace_bytes(int b, int N, int P, int H, int c);
+int prd_tri_attn_core_heads(float* og, const float* pair, const float* mask, const float* wq, const float* wk,
+                            const float* wv, const float* wg, const float* bg, int ending, int b, int N, int P, int H, int c,
+                            float* ws, size_t ws_bytes, int arith, hipStream_t stream);
+
 /* bytes of scratch an operator needs: op = "tri_mul" | "tri_attn" */
 size_t prd_workspace_bytes(const char* op, int b, int N, int S, int P);
 

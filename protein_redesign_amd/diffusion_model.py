@@ -501,6 +501,9 @@ class ProteinReDiffModel(_Base):
         """``step_inputs`` = (single, ebeta) if already computed; ``raw_noise``: return the coordinate head's output before
         remove_mean (the step-boundary kernel removes the mean itself); ``defer_seq_head``: return the sequence head's HIDDEN units
         instead of the logits (the step-boundary kernel applies the last layer itself)."""
+        den = self.Denoiser
+        if z.is_cuda and not ops.default_head_layout(den.num_heads, den.head_dim):
+            ops.check_head_layout(den.num_heads, den.head_dim, den.pair_dim)     # before the first launch, with the supported set
         if static is None:
             static = self._static_inputs(batch)
         rm = batch["residue_mask"].contiguous()

@@ -636,9 +636,52 @@ def tri_attn_variant(N: int, P: int) -> int:
     return v
 
 
-def tri_attn(pair, mask, wts, H: int, c: int, *, ending: bool, residual: bool, out=None, ws=None) -> torch.Tensor:
-    """wts = (q.w, k.w, v.w, gate.w, gate.b, out.w, out.b)"""
+HEAD_LAYOUTS = "num_heads 1..8, head_dim a multiple of 4 up to 64, pair_dim 32/64"
+
+
+def default_head_layout(H: int, c: int) -> bool:
+    """4 heads x 16 channels: the layout the tuned triangle-attention kernels (and their fused / persistent forms) serve."""
+    return H == 4 and c == 16
+
+
+def check_head_layout(H: int, c: int, P: int) -> None:
+    """Raises ValueError naming the supported set when the GPU path cannot run an attention layout (host-only, no launch)."""
+    if not (1 <= H <= 8 and 4 <= c <= 64 and c % 4 == 0 and P in (32, 64)):
+        raise ValueError(f"attention layout num_heads={H}, head_dim={c}, pair_dim={P} does not run on the GPU; "
+                         f"supported: {HEAD_LAYOUTS}")
+
+
+def tri_attn_heads_supported(N: int, P: int, H: int, c: int) -> bool:
+    """True when prd_tri_attn_core_heads serves this shape (any N; the arithmetic does not matter: fp32 MFMA in both)."""
+    return lib().prd_tri_attn_heads_supported(N, P, H, c) == 1
+
+
+def tri_attn_heads_ws_floats(b: int, N: int, P: int, H: int, c: int) -> int:
+    """floats of the workspace of tri_attn_core_heads: og [b,N,N,H c] (+ softmax statistics: none in the single-launch kernel)"""
+    return int(lib().prd_tri_attn_heads_workspace_bytes(b, N, P, H, c)) // 4
+
+
+def tri_attn_core_heads(pair, mask, wts, H: int, c: int, *, ending: bool, ws=None) -> torch.Tensor:
+    """The general-layout core (prd_tri_attn_core_heads): og [b,N,N,H c] = the gated head outputs, a view of the start of ``ws``
+    (allocated here if not given or too small).  wts = (q.w, k.w, v.w, gate.w, gate.b)."""
     b, N, _, P = pair.shape
+    check_head_layout(H, c, P)
+    need = tri_attn_heads_ws_floats(b, N, P, H, c)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=pair.device, dtype=F32)
+    og = ws[:b * N * N * H * c].view(b, N, N, H * c)
+    check(lib().prd_tri_attn_core_heads(dptr(og), dptr(pair), dptr(mask), *[dptr(w) for w in wts], int(ending), b, N, P, H, c,
+                                        dptr(ws), ws.numel() * 4, stream()), "prd_tri_attn_core_heads")
+    return og
+
+
+def tri_attn(pair, mask, wts, H: int, c: int, *, ending: bool, residual: bool, out=None, ws=None) -> torch.Tensor:
+    """wts = (q.w, k.w, v.w, gate.w, gate.b, out.w, out.b).  Layouts other than 4 x 16: the general core, then the output
+    projection (+ bias, + residual) as a row GEMM with K = H c."""
+    b, N, _, P = pair.shape
+    if not default_head_layout(H, c):
+        og = tri_attn_core_heads(pair, mask, wts[:5], H, c, ending=ending, ws=ws)
+        return linear(og, wts[5], wts[6], resid=pair if residual else None, out=out)
     if out is None:
         out = torch.empty_like(pair)
     nbytes = workspace_bytes("tri_attn", b, N, 0, P)
@@ -880,6 +923,9 @@ def gated_attention_single(x_normed, mask, bias, packed, wo, bo, H: int, c: int,
         return linear(o, wo, bo, resid=resid, rscale=rscale, slab=slab_ok(b * N, wo.shape[0], HC), out_ln=out_ln)
     ldp = round_up(N, 4)
     logits = torch.empty(b, H, N, ldp, device=x_normed.device, dtype=F32)
+    # qkvg may be a column block of a wider projection (the previous block's merged one, FoldingBlock.run_): rows L floats apart
+    # when it is contiguous, else its own pitch
+    qkvg, L = row_block(qkvg)
     gemm(qkvg, qkvg, logits, N, N, c, L, L, ldp, b_off=HC, G1=b, G2=H, sa=(N * L, c), sb=(N * L, c),
          sc=(H * N * ldp, N * ldp), addmat=bias, sad=(H * N * N, N * N), ldadd=N,
          colmask=(mask if key_mask else None), scm1=N, fill=-(2.0 ** 15),

@@ -437,7 +437,8 @@ def tri_attn_update(ta, pair: torch.Tensor, mask: torch.Tensor, residual: bool =
     """The update, or with ``residual`` pair + update."""
     a = ta.attn
     H, c, end = a.num_heads, a.head_dim, ta.mode == "ending"
-    if pair.shape[1] <= TRI_ATTN_BWD_MAX_N:
+    # the hand-written backward cores are 4 x 16 only: other layouts run the general forward core and recompute through torch_ref
+    if pair.shape[1] <= TRI_ATTN_BWD_MAX_N and ops.default_head_layout(H, c):
         return TriAttnFn.apply(pair, mask, end, H, c, residual, *a.weights())
 
     def ref(p, *w):
@@ -537,6 +538,8 @@ def network(model, batch: Dict[str, torch.Tensor], z: torch.Tensor, seq_t: torch
     mask = mask.contiguous()
     den = model.Denoiser
     H = den.num_heads
+    if z.is_cuda and not ops.default_head_layout(H, den.head_dim):
+        ops.check_head_layout(H, den.head_dim, den.pair_dim)
 
     # ---- input stage (model.py:332-361) ----
     atom_tabs = [e.weight for e in model.embed_atom_feats.embeddings]

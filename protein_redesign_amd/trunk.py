@@ -266,10 +266,12 @@ class FoldingBlock(nn.Module):
         there: "qkvg" = the next block's projection, "tail" = the tail layer's output."""
         sa = self.single_attn
         b, N = mask.shape
+        ta = self.pair_attn_ending.attn
+        general = not ops.default_head_layout(ta.num_heads, ta.head_dim)
+        if general and pair.is_cuda:
+            ops.check_head_layout(ta.num_heads, ta.head_dim, pair.shape[-1])
         if ws is None:
-            ws = torch.empty(max(ops.workspace_bytes("tri_mul", b, N, 0, pair.shape[-1]),
-                                 ops.workspace_bytes("tri_attn", b, N, 0, pair.shape[-1])) // 4,
-                             device=pair.device, dtype=torch.float32)
+            ws = torch.empty(ws_floats(b, N, pair.shape[-1], ta.num_heads, ta.head_dim), device=pair.device, dtype=torch.float32)
         if bias is None:
             bias = ops.pair_bias(pair, self.attn_bias[1].weight, self.attn_bias[1].bias)
         single = sa.run_single(single, mask, bias, single, ln_a=True, qkvg=qkvg)
@@ -293,7 +295,21 @@ class FoldingBlock(nn.Module):
         else:
             self.pair_mul_outgoing.run(pair, mask, residual=True, out=pair, ws=ws)
             self.pair_mul_incoming.run(pair, mask, residual=True, out=pair, ws=ws)
-        ta = self.pair_attn_ending.attn
+        pf = self.pair_fc
+        nb_w = next_block.attn_bias[1].weight if next_block is not None else None
+        nb_b = next_block.attn_bias[1].bias if next_block is not None else None
+        if general:
+            # layouts other than 4 x 16 (prd_tri_attn_core_heads, og [b,N,N,H c]); the opt-in fused / persistent forms are 4 x 16 only
+            self.pair_attn_starting.run(pair, mask, residual=True, out=pair, ws=ws)
+            og = ops.tri_attn_core_heads(pair, mask, ta.weights()[:5], ta.num_heads, ta.head_dim, ending=True, ws=ws)
+            if og.shape[-1] == 64:      # the fused row pass takes a 64-wide og whatever the head split
+                next_bias = ops.block_tail_(pair, og, ta.out_proj.weight, ta.out_proj.bias, pf[1].weight, pf[1].bias,
+                                            pf[3].weight, pf[3].bias, nb_w, nb_b)
+            else:
+                ops.linear(og, ta.out_proj.weight, ta.out_proj.bias, resid=pair, out=pair)
+                ops.pair_transition(pair, pf[1].weight, pf[1].bias, pf[3].weight, pf[3].bias, residual=True, out=pair)
+                next_bias = ops.pair_bias(pair, nb_w, nb_b) if nb_w is not None else None
+            return single, pair, next_bias
         nog = b * N * N * 64
         if _TRI_ATTN_FUSE and ops.tri_attn_core_fused_supported(N, pair.shape[-1]) and ws.numel() >= 2 * nog:
             # starting attention: core only; its output projection + residual ride in the row load of the ending core, which
@@ -319,9 +335,6 @@ class FoldingBlock(nn.Module):
             # transition + (if there is a next block) that block's attention bias
             og = ops.tri_attn_core(pair, mask, ta.weights()[:5], ta.num_heads, ta.head_dim, ending=True,
                                    og=ws[:nog].view(b, N, N, 64), stats=ws[nog:] if ws.numel() > nog else None)
-        pf = self.pair_fc
-        nb_w = next_block.attn_bias[1].weight if next_block is not None else None
-        nb_b = next_block.attn_bias[1].bias if next_block is not None else None
         next_bias = ops.block_tail_(pair, og, ta.out_proj.weight, ta.out_proj.bias, pf[1].weight, pf[1].bias,
                                     pf[3].weight, pf[3].bias, nb_w, nb_b)
         return single, pair, next_bias
@@ -329,6 +342,13 @@ class FoldingBlock(nn.Module):
     def forward(self, single: torch.Tensor, pair: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         single, pair, _ = self.run_(single.contiguous(), pair.contiguous().clone(), mask.contiguous())
         return single, pair
+
+
+def ws_floats(b: int, N: int, P: int, H: int, c: int) -> int:
+    """Scratch of one folding block: triangle multiplication's operands, the attention's og (+ key-chunk statistics) -- for a
+    layout other than 4 x 16 the general core's og [b,N,N,H c]."""
+    att = ops.workspace_bytes("tri_attn", b, N, 0, P) // 4 if ops.default_head_layout(H, c) else ops.tri_attn_heads_ws_floats(b, N, P, H, c)
+    return max(ops.workspace_bytes("tri_mul", b, N, 0, P) // 4, att)
 
 
 class Denoiser(nn.Module):
@@ -350,8 +370,7 @@ class Denoiser(nn.Module):
              for _ in range(self.num_blocks)])
 
     def ws_floats(self, b: int, N: int) -> int:
-        P = self.pair_dim
-        return max(ops.workspace_bytes("tri_mul", b, N, 0, P), ops.workspace_bytes("tri_attn", b, N, 0, P)) // 4
+        return ws_floats(b, N, self.pair_dim, self.num_heads, self.head_dim)
 
     def project_single(self, single: torch.Tensor, mask: torch.Tensor):
         """Everything at the head of the trunk that depends on the single representation only (OPM's a | b projection, SPA's
@@ -399,6 +418,8 @@ class Denoiser(nn.Module):
         ``pair_init`` = (static_pair, z, centers, w_dist, ebeta) is given: the pair input stage then runs here, fused with the
         outer-product update and the first attention-bias heads where the library has that form (ops.pair_head)."""
         b, N = mask.shape
+        if mask.is_cuda and not ops.default_head_layout(self.num_heads, self.head_dim):
+            ops.check_head_layout(self.num_heads, self.head_dim, self.pair_dim)
         if ws is None:
             ws = torch.empty(self.ws_floats(b, N), device=mask.device, dtype=torch.float32)
         if pre is None:
