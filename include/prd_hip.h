@@ -160,6 +160,9 @@ typedef struct PrdGemm {
                                        into the fp16 subnormal range (see OPERAND RANGE above).  Ignored by the fp32 kernels. */
     int mul_pos;                    /* with mulmat: v = mulmat[g][m][n] > 0 ? v : 0 instead of the product (the ReLU mask of a backward pass,
                                        read from the recomputed activations) */
+    const unsigned* a_amax;         /* optional (split-16 tile kernel, without a_ln): the float bits of max |A| (a gradient: any scale).  A is
+                                       multiplied by the power of two split_scale(*a_amax) (max |A| s in [2^12, 2^13)) while it is split and
+                                       the accumulator by 1 / s -- exact; without it A far below 1 loses its lo part (OPERAND RANGE above) */
 } PrdGemm;
 size_t prd_gemm_slab_workspace(int M, int N, int K);
 int prd_gemm_slab_ok(int M, int N, int K, int arith);   /* 1 when a PrdGemm of this shape with `ws` set takes the K-slab path */
@@ -241,6 +244,9 @@ int prd_tri_mul(float* out, const float* pair, const float* mask, const float* w
  * AB[b][2P][N][ldn] (A = channels 0..P-1, B = channels P..2P-1, ldn = round_up(N,32), zero padded), O[b][P][N][ldn].
  * The backward calls it on transposed operands for dA and dB (P = 128 is accepted for its two contractions stacked). */
 int prd_tri_mul_contract(float* O, const float* AB, int b, int N, int P, int arith, hipStream_t stream);
+/* The same with the first operand a GRADIENT (the stacked contraction of the backward): in split-16 arithmetic it is split x a power of
+ * two s chosen from a_amax[complex] (float bits of its max |.|, e.g. from prd_tri_mul_out_bwd), and the result taken back by 1 / s. */
+int prd_tri_mul_contract_scaled(float* O, const float* AB, const unsigned* a_amax, int b, int N, int P, int arith, hipStream_t stream);
 /* The operands of both gradient contractions stacked for ONE prd_tri_mul_contract call with 2P channel pairs:
  * ops[b][4P][N][ldn] = dO | dO^T | B^T | A^T by channel block (dO already in block 0: prd_tri_mul_out_bwd with
  * dO_batch_channels = 4P); A, B = the forward operands AB[b][2P][N][ldn].  prd_tri_mul_contract(dAB, ops, b, N, 2P) then yields
@@ -267,6 +273,12 @@ int prd_tri_mul_out_bwd(float* dz, float* dgp, float* dO, float* dx1, const floa
                         const float* w_out, const float* b_out, const float* w_ogate, const float* b_ogate,
                         const float* w_out_t, const float* w_ogate_t, float* x_out, float* lo_out, int dO_batch_channels,
                         int b, int N, int P, hipStream_t stream);
+/* The same, and dO_amax (optional, [b] uint32, zeroed by the caller) receives max |dO| per complex as float bits, for
+ * prd_tri_mul_contract_scaled (one atomicMax per wave: a max does not depend on the order of the updates). */
+int prd_tri_mul_out_bwd_amax(float* dz, float* dgp, float* dO, float* dx1, const float* dy, const float* pair, const float* O,
+                             const float* w_out, const float* b_out, const float* w_ogate, const float* b_ogate,
+                             const float* w_out_t, const float* w_ogate_t, float* x_out, float* lo_out, int dO_batch_channels,
+                             int b, int N, int P, unsigned* dO_amax, hipStream_t stream);
 /* Projection stage backward.  dAB = gradient of the operands (channel-major [b][2P][N][ldn]); writes dpair [b,N,N,P] (gradient of
  * the update with respect to its input pair tensor), and dpp / dpg = d(pre-activations of ab_proj / ab_gate) in row layout
  * [b,N,N,2P] by pair position (dW_proj = dpp^T LN(pair), dW_gate = dpg^T LN(pair) are left to the caller's BLAS). */
@@ -315,6 +327,8 @@ int prd_sym_rows(float* out, const float* x, float scale, int b, int N, int P, h
 /* out[b][i][p][j] = dy[b][i][j][p] + dy[b][j][i][p] (dy [b,N,N,P] -> out [b,N,P,N]): the symmetrised, transposed gradient the
  * backward of the outer-linear update (modules.py:283-287) contracts with LN(single) over j.  P in {32, 64}. */
 int prd_sym_transpose(float* out, const float* dy, int b, int N, int P, hipStream_t stream);
+/* The same, and amax (optional, [b] uint32, zeroed by the caller) receives max |out| per complex as float bits, for PrdGemm.a_amax. */
+int prd_sym_transpose_amax(float* out, const float* dy, int b, int N, int P, unsigned* amax, hipStream_t stream);
 /* A linear at every pair position as a row kernel (the activation-gradient GEMMs of the training backward: 2e5 rows, K and OUT
  * at most 256; autograd of nn.Linear over [b,N,N,*], modules.py:236-243, 321-326): out[row][0..OUT) = act(LN?(x[row]) W^T + bias),
  * W [OUT][K] as in nn.Linear.  ln_in: LayerNorm (no affine) of the x rows first (K = 64), xn_out (optional) receives them.

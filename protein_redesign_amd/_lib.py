@@ -39,6 +39,7 @@ class PrdGemm(C.Structure):
         ("out_ln", vp), ("ldol", ci),
         ("a_scale", cf),
         ("mul_pos", ci),
+        ("a_amax", vp),
     ]
 
 
@@ -64,11 +65,13 @@ SIGNATURES = {
     "prd_outer_linear": [vp] * 4 + [ci] + [vp] * 2 + [ci] * 5 + [vp, ci, vp],
     "prd_tri_mul": [vp] * 11 + [ci] * 5 + [vp, cz, vp, ci, vp],
     "prd_tri_mul_contract": [vp, vp, ci, ci, ci, ci, vp],
+    "prd_tri_mul_contract_scaled": [vp, vp, vp, ci, ci, ci, ci, vp],
     "prd_tri_mul_chain_supported": [ci, ci, ci],
     "prd_tri_attn_core_fused_supported": [ci, ci, ci],
     "prd_tri_attn_core_fused": [vp] * 12 + [ci] * 6 + [vp],
     "prd_tri_mul_chain": [vp, vp, vp, vp, ci, ci, ci, vp, cz, ci, vp],
     "prd_tri_mul_out_bwd": [vp] * 15 + [ci] * 4 + [vp],
+    "prd_tri_mul_out_bwd_amax": [vp] * 15 + [ci] * 4 + [vp, vp],
     "prd_tri_mul_bwd_operands": [vp, vp, ci, ci, ci, vp],
     "prd_tri_mul_proj_bwd": [vp] * 13 + [ci] * 5 + [vp],
     "prd_tri_attn_bwd_core": [vp] * 9 + [ci] * 6 + [vp],
@@ -77,6 +80,7 @@ SIGNATURES = {
     "prd_ln_rows_bwd": [vp, vp, vp, vp, cll, ci, vp],
     "prd_pair_bias_bwd": [vp, vp, vp, vp, vp, vp, ci, cll, ci, ci, vp],
     "prd_sym_transpose": [vp, vp, ci, ci, ci, vp],
+    "prd_sym_transpose_amax": [vp, vp, ci, ci, ci, vp, vp],
     "prd_sym_rows": [vp, vp, cf, ci, ci, ci, vp],
     "prd_outer_linear_bwd_reduce": [vp, vp, ci, vp, vp, vp, cll, ci, ci, vp],
     "prd_pair_linear_supported": [ci, ci, ci],
@@ -118,7 +122,7 @@ GEMM_MODES = {"fp32": 0, "split16": 1, "bf16x3": 1}      # "bf16x3": earlier nam
 DEFAULT_GEMM_MODE = "split16"       # process default of the Python host side (env PRD_GEMM_MODE overrides)
 
 # entry points that take the arithmetic as their last argument before the stream ...
-_ARITH_BEFORE_STREAM = ("prd_coord_head", "prd_pair_head", "prd_pair_init", "prd_opm_pair", "prd_outer_linear", "prd_tri_mul", "prd_tri_mul_contract", "prd_tri_mul_proj_bwd",
+_ARITH_BEFORE_STREAM = ("prd_coord_head", "prd_pair_head", "prd_pair_init", "prd_opm_pair", "prd_outer_linear", "prd_tri_mul", "prd_tri_mul_contract", "prd_tri_mul_contract_scaled", "prd_tri_mul_proj_bwd",
                         "prd_tri_attn", "prd_tri_attn_core", "prd_tri_attn_out", "prd_pair_transition", "prd_block_tail", "prd_tri_mul_chain",
                         "prd_linear_wgrad", "prd_pair_linear", "prd_spa_attn_core", "prd_tri_attn_pair",
                         "prd_tri_attn_core_heads")

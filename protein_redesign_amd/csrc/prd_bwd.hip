@@ -59,7 +59,7 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_out_bwd_kernel(
     const float* __restrict__ dy, const float* __restrict__ pair, const float* __restrict__ O,
     const float* __restrict__ wo, const float* __restrict__ bo, const float* __restrict__ wog, const float* __restrict__ bog,
     const float* __restrict__ woT, const float* __restrict__ wogT, int b, int N, int ldn,
-    float* __restrict__ x_out, float* __restrict__ lo_out, int dO_bch) {
+    float* __restrict__ x_out, float* __restrict__ lo_out, int dO_bch, unsigned* __restrict__ dO_amax) {
     constexpr int KH = P / 2, NB = P / 32, WSZ = P * (P + 4);
     extern __shared__ __attribute__((aligned(16))) float smem_b1[];
     float* Wol = smem_b1;
@@ -136,6 +136,12 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_out_bwd_kernel(
 #pragma unroll
             for (int s = 0; s < KH; ++s) dlo[s] = a[s >> 4][s & 15];
             ln_cll_bwd<KH>(dlo, lo, rstd_o);
+            if (dO_amax) {                           // max |dO| per complex: the split factor of the gradient contraction
+                float m = 0.f;
+#pragma unroll
+                for (int s = 0; s < KH; ++s) m = fmaxf(m, fabsf(dlo[s]));
+                wave_amax(dO_amax + bb, valid ? m : 0.f);
+            }
             {
                 const prd_rsrc rdo = make_rsrc(dO + (((long)bb * dO_bch) * N + i) * ldn + vb * 32);
 #pragma unroll
@@ -208,7 +214,9 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_proj_bwd_kernel(
         zero_acc(adx);
         u32x4 xs[2][P / 16];
         if (B3) split2h_cll<KH>(x, xs);
+        float rs = 1.0f;                             // B3: the factor of the split gradients (and of adx)
         if constexpr (B3) {
+            rs = split_scale(0u);
             // dAB through a buffer descriptor: the lane part of the address once, the channel stride as a scalar offset (64
             // scattered 64-bit address computations per task otherwise)
             const prd_rsrc rdab = make_rsrc(dAB + (((long)bb * OUT) * N + u) * ldn + vb * 32);
@@ -242,6 +250,21 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_proj_bwd_kernel(
                         *reinterpret_cast<float4*>(d1 + 8 * g) = make_float4(dpg[4 * g], dpg[4 * g + 1], dpg[4 * g + 2], dpg[4 * g + 3]); \
                     }                                                                                                   \
                 }                                                                                                       \
+                /* the gradients are split x rs, a power of two from the running max|.| of the row (prd_common.h: split_scale): a part */ \
+                /* that needs a smaller factor rescales what adx holds (exact) */                                        \
+                float mx = 0.f;                                                                                         \
+                _Pragma("unroll") for (int q = 0; q < 16; ++q) mx = fmaxf(mx, fmaxf(fabsf(dpp[q]), fabsf(dpg[q])));     \
+                mx = fmaxf(mx, __shfl_xor(mx, 32));     /* the row's other half of the channels */                      \
+                const float sp = split_scale(__float_as_uint(mx));                                                      \
+                if (sp < rs) {                                                                                          \
+                    if constexpr ((H_) + (NB_) > 0) {   /* the first part finds adx still zero */                       \
+                        const float f = sp / rs;                                                                        \
+                        _Pragma("unroll") for (int nb = 0; nb < NB; ++nb)                                               \
+                            _Pragma("unroll") for (int q = 0; q < 16; ++q) adx[nb][q] *= f;                             \
+                    }                                                                                                   \
+                    rs = sp;                                                                                            \
+                }                                                                                                       \
+                _Pragma("unroll") for (int q = 0; q < 16; ++q) { dpp[q] *= rs; dpg[q] *= rs; }                          \
                 u32x4 ps[2][2], gs[2][2];                                                                               \
                 split2h_cll<16>(dpp, ps);                                                                               \
                 split2h_cll<16>(dpg, gs);                                                                               \
@@ -303,8 +326,9 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_proj_bwd_kernel(
         }
         float dx[KH];
         load_row_cll<P>(dx1 + prow * P, hi, valid, dx);
+        const float irs = __uint_as_float((254u << 23) - __float_as_uint(rs));     // 1 / rs (a power of two)
 #pragma unroll
-        for (int s = 0; s < KH; ++s) dx[s] += adx[s >> 4][s & 15] * ASC;
+        for (int s = 0; s < KH; ++s) dx[s] += (adx[s >> 4][s & 15] * irs) * ASC;
         ln_cll_bwd<KH>(dx, x, rstd_x);
         store_row_cll<P>(dpair + prow * P, hi, valid, dx);
     }
@@ -1181,7 +1205,9 @@ __global__ __launch_bounds__(256) void tri_mul_bwd_operands_kernel(float* __rest
 // out[b][i][p][j] = dy[b][i][j][p] + dy[b][j][i][p]: the symmetrised gradient of the outer-linear update (modules.py:283-287:
 // out[i][j] depends on x_i x_j and on u_i - u_j) in the [b, N P, N] row layout its backward GEMM contracts over j.  One workgroup
 // per (b, i, 64 positions j): both reads are 4 P-byte rows, the transpose goes through a 64 x 65 LDS tile.
-__global__ __launch_bounds__(256) void sym_transpose_kernel(float* __restrict__ out, const float* __restrict__ dy, int N, int P, int T, long ntask) {
+// amax (optional): max |out| per complex, as float bits (the split factor of the GEMM that contracts it, prd_common.h: split_scale)
+__global__ __launch_bounds__(256) void sym_transpose_kernel(float* __restrict__ out, const float* __restrict__ dy, int N, int P, int T, long ntask,
+                                                            unsigned* __restrict__ amax) {
     __shared__ float tile[64][65];
     const int t = threadIdx.x, c4 = 4 * (t & 15), rl = t >> 4;
     for (long task = blockIdx.x; task < ntask; task += gridDim.x) {
@@ -1190,6 +1216,7 @@ __global__ __launch_bounds__(256) void sym_transpose_kernel(float* __restrict__ 
         const long bb = bi / N;
         const int i = (int)(bi - bb * N), j0 = 64 * tj;
         __syncthreads();
+        float m = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int jl = rl + 16 * k, j = j0 + jl;
@@ -1199,8 +1226,10 @@ __global__ __launch_bounds__(256) void sym_transpose_kernel(float* __restrict__ 
                 const float4 c = *reinterpret_cast<const float4*>(dy + ((bb * N + j) * N + i) * P + c4);
                 v = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w);
             }
+            m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
             tile[jl][c4] = v.x; tile[jl][c4 + 1] = v.y; tile[jl][c4 + 2] = v.z; tile[jl][c4 + 3] = v.w;
         }
+        if (amax) wave_amax(amax + bb, m);
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -1328,13 +1357,17 @@ extern "C" int prd_sym_rows(float* out, const float* x, float scale, int b, int 
 }
 
 extern "C" int prd_sym_transpose(float* out, const float* dy, int b, int N, int P, hipStream_t stream) {
+    return prd_sym_transpose_amax(out, dy, b, N, P, nullptr, stream);
+}
+
+extern "C" int prd_sym_transpose_amax(float* out, const float* dy, int b, int N, int P, unsigned* amax, hipStream_t stream) {
     if (!out || !dy || b <= 0 || N <= 0) return PRD_ERR_ARG;
     if (P != 32 && P != 64) return PRD_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(dy)) & 15) return PRD_ERR_ALIGN;
     const int T = prd_ceil_div(N, 64);
     const long ntask = (long)b * N * T;
     const int grid = (int)(ntask < 256 * 8 ? ntask : 256 * 8);
-    hipLaunchKernelGGL(sym_transpose_kernel, dim3(grid), dim3(256), 0, stream, out, dy, N, P, T, ntask);
+    hipLaunchKernelGGL(sym_transpose_kernel, dim3(grid), dim3(256), 0, stream, out, dy, N, P, T, ntask, amax);
     return (int)hipGetLastError();
 }
 
@@ -1352,6 +1385,14 @@ extern "C" int prd_tri_mul_out_bwd(float* dz, float* dgp, float* dO, float* dx1,
                                    const float* w_out, const float* b_out, const float* w_ogate, const float* b_ogate,
                                    const float* w_out_t, const float* w_ogate_t, float* x_out, float* lo_out, int dO_batch_channels,
                                    int b, int N, int P, hipStream_t stream) {
+    return prd_tri_mul_out_bwd_amax(dz, dgp, dO, dx1, dy, pair, O, w_out, b_out, w_ogate, b_ogate, w_out_t, w_ogate_t, x_out, lo_out,
+                                    dO_batch_channels, b, N, P, nullptr, stream);
+}
+
+extern "C" int prd_tri_mul_out_bwd_amax(float* dz, float* dgp, float* dO, float* dx1, const float* dy, const float* pair, const float* O,
+                                        const float* w_out, const float* b_out, const float* w_ogate, const float* b_ogate,
+                                        const float* w_out_t, const float* w_ogate_t, float* x_out, float* lo_out, int dO_batch_channels,
+                                        int b, int N, int P, unsigned* dO_amax, hipStream_t stream) {
     if (!dz || !dgp || !dO || !dx1 || !dy || !pair || !O || !w_out || !b_out || !w_ogate || !b_ogate || b <= 0 || N <= 0) return PRD_ERR_ARG;
     if (P != 32 && P != 64) return PRD_ERR_UNSUPPORTED;
     if (dO_batch_channels == 0) dO_batch_channels = P;
@@ -1363,11 +1404,11 @@ extern "C" int prd_tri_mul_out_bwd(float* dz, float* dgp, float* dO, float* dx1,
     if (P == 64) {
         PRD_BWD_SET_LDS((tri_mul_out_bwd_kernel<64, NWB>));
         hipLaunchKernelGGL((tri_mul_out_bwd_kernel<64, NWB>), dim3(grid), dim3(NWB * 64), lds, stream, dz, dgp, dO, dx1, dy, pair, O, w_out,
-                           b_out, w_ogate, b_ogate, w_out_t, w_ogate_t, b, N, ldn, x_out, lo_out, dO_batch_channels);
+                           b_out, w_ogate, b_ogate, w_out_t, w_ogate_t, b, N, ldn, x_out, lo_out, dO_batch_channels, dO_amax);
     } else {
         PRD_BWD_SET_LDS((tri_mul_out_bwd_kernel<32, NWB>));
         hipLaunchKernelGGL((tri_mul_out_bwd_kernel<32, NWB>), dim3(grid), dim3(NWB * 64), lds, stream, dz, dgp, dO, dx1, dy, pair, O, w_out,
-                           b_out, w_ogate, b_ogate, w_out_t, w_ogate_t, b, N, ldn, x_out, lo_out, dO_batch_channels);
+                           b_out, w_ogate, b_ogate, w_out_t, w_ogate_t, b, N, ldn, x_out, lo_out, dO_batch_channels, dO_amax);
     }
     return (int)hipGetLastError();
 }

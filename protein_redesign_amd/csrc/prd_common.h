@@ -412,6 +412,24 @@ PRD_DEV void split2h(float a, float b, unsigned& hi, unsigned& lo) {
     asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(rb) : "v"(hi), "v"(b));
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{ra, rb}, prd_h16x2));
 }
+// Range of GRADIENT operands.  The split above keeps 22+ bits only while x sits in the fp16 normal range: hi needs |x| >= 2^-14,
+// lo needs |x| >~ 2^-3.  Forward operands are O(1); gradients are not (training feeds rms 1e-2 .. 1e-6, and the error of an
+// unscaled split grows as 1 / scale: rel-L2 1.7e-5 at 1e-3, 1.7e-2 at 1e-6).  A split gradient is therefore multiplied by an exact
+// power of two s chosen from its magnitude, and the fp32 accumulator by 1 / s -- exact both ways.
+// split_scale(bits of max|x|): s with max|x| s in [2^12, 2^13) (far below the fp16 limit 65504; values down to 2^-16 max|x| keep a
+// normal lo part), clamped to [2^-126, 2^126] so that s and 1 / s are normal floats (2^126 for max|x| = 0).  max|x| is >= 0: its
+// bits order like the values, so an unsigned atomicMax over them is the float max, independent of the order of the updates.
+PRD_DEV float split_scale(unsigned amax_bits) {
+    int e = 266 - (int)(amax_bits >> 23);               // 127 + 12 - (biased exponent of max|x| - 127)
+    e = e > 253 ? 253 : (e < 1 ? 1 : e);
+    return __uint_as_float((unsigned)e << 23);
+}
+// *amax = max(*amax, max over the wave of m) for m >= 0, as float bits: one atomic per wave
+PRD_DEV void wave_amax(unsigned* amax, float m) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) atomicMax(amax, __float_as_uint(m));
+}
 // NE CLL elements x[0 .. NE) (NE a multiple of 8) -> 2 planes x NE/8 operand registers of 8 fp16
 template <int NE>
 PRD_DEV void split2h_cll(const float (&x)[NE], u32x4 (&p)[2][NE / 8]) {

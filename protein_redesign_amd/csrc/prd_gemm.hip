@@ -432,6 +432,14 @@ __global__ __launch_bounds__(256 * KG) void gemm_h2_kernel(PrdGemm g) {
         dst[i] = (isb ? 2 * PLANE : 0) + row * 64 + (((f >> 1) ^ ((row >> 2) & 3)) << 4) + (f & 1) * 8;
         if (!isb) { amu[i] = g.a_ln ? mean_l[row] : 0.f; ars[i] = g.a_ln ? (ok ? rstd_l[row] : 0.f) : 1.f; }
     }
+    // PrdGemm.a_amax: a GRADIENT as the A operand, split x a power of two from its max |.| (prd_common.h: split_scale) -- the
+    // LayerNorm factor's slot ars carries it -- and the accumulator taken back by the inverse
+    float iasc = 1.0f;
+    if (g.a_amax && !g.a_ln) {
+        const float asc = split_scale(g.a_amax[0]);
+        iasc = __uint_as_float((254u << 23) - __float_as_uint(asc));
+        ars[0] = ars[1] = asc;
+    }
     unsigned char* mybuf = gh + kg * 2 * BUF;
     const unsigned swz = (unsigned)((r >> 2) & 3);
     f32x16 acc;
@@ -513,7 +521,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_h2_kernel(PrdGemm g) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int m = m0 + wm0 + drow32(q, hi);
-                if (m < g.M) epilogue_store(g, g1, g2, m, n, acc[q] * H2_INV_WSCALE, C);
+                if (m < g.M) epilogue_store(g, g1, g2, m, n, (acc[q] * iasc) * H2_INV_WSCALE, C);
             }
         }
     }

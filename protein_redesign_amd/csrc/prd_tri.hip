@@ -440,9 +440,12 @@ constexpr int TMS_T = 160, TMS_PLANE = TMS_T * 64, TMS_OPER = 2 * TMS_PLANE;    
 // waves per workgroup of the split contraction: 8 by default; 16 (PRD_TMS_NW=16) makes the kernel itself 1 us faster (18.8 vs
 // 19.8 us) but the whole step 15 us slower in the same run (1.932 vs 1.918 ms, twice); 12 waves: 22.5 vs 22.7 us -- A/B switch
 // PRD_TUNE_TMS_NW in the upper bits of `arith`
-template <int NWV, int DEPTH = 2>                   // 8 or 16 waves: 25 sub-tiles dealt round-robin, 4 or 2 accumulators per wave; DEPTH: chunks of operands in flight
+// ASC (the stacked gradient contraction of the backward, prd_tri_mul_contract_scaled): the first operand is a GRADIENT, not O(1);
+// it is split x split_scale(a_amax[complex]) and the result taken back by the inverse power of two (prd_common.h: split_scale)
+template <int NWV, int DEPTH = 2, bool ASC = false>  // 8 or 16 waves: 25 sub-tiles dealt round-robin, 4 or 2 accumulators per wave; DEPTH: chunks of operands in flight
 __global__ __launch_bounds__(NWV * 64) void tri_mul_contract_split_kernel(float* __restrict__ O, const float* __restrict__ AB,
-                                                                          int N, int ldn, int P, int nbatch, int tiles, int swap) {
+                                                                          int N, int ldn, int P, int nbatch, int tiles, int swap,
+                                                                          const unsigned* __restrict__ a_amax) {
     constexpr int NT = NWV * 64, NPT = (2560 + NT - 1) / NT, NSUB = (25 + NWV - 1) / NWV;
     extern __shared__ __attribute__((aligned(16))) unsigned char tms[];          // [2 buffers][A | B][2 planes][160 rows][64 B]
     PhaseTimer pt;
@@ -482,6 +485,11 @@ __global__ __launch_bounds__(NWV * 64) void tri_mul_contract_split_kernel(float*
         }
         const int bb = ch / P, d = ch - bb * P;
         const int m0 = (tile / tiles) * TMS_T, n0 = (tile % tiles) * TMS_T;
+        float asc = 1.0f, iasc = 1.0f;
+        if constexpr (ASC) {
+            asc = split_scale(a_amax[bb]);
+            iasc = __uint_as_float((254u << 23) - __float_as_uint(asc));
+        }
         // swap: the operands change roles, i.e. the output is the TRANSPOSE O^T[j][i] (what the column-wise tasks of
         // tri_mul_out_proj_kernel read contiguously)
         const float* __restrict__ A = AB + ((size_t)bb * 2 * P + (swap ? P : 0) + d) * N * ldn;
@@ -512,9 +520,11 @@ __global__ __launch_bounds__(NWV * 64) void tri_mul_contract_split_kernel(float*
 #define PRD_TMS_STAGE(R, BUF)                                                                                       \
     _Pragma("unroll") for (int i = 0; i < NPT; ++i) {                                                               \
         if (!sok[i]) continue;                                                                                      \
+        float x0 = __uint_as_float(R[i][0]), x1 = __uint_as_float(R[i][1]), x2 = __uint_as_float(R[i][2]), x3 = __uint_as_float(R[i][3]); \
+        if (ASC && !sisb[i]) { x0 *= asc; x1 *= asc; x2 *= asc; x3 *= asc; }                                       \
         unsigned h0, l0, h1, l1;                                                                                    \
-        split2h(__uint_as_float(R[i][0]), __uint_as_float(R[i][1]), h0, l0);                                        \
-        split2h(__uint_as_float(R[i][2]), __uint_as_float(R[i][3]), h1, l1);                                        \
+        split2h(x0, x1, h0, l0);                                                                                    \
+        split2h(x2, x3, h1, l1);                                                                                    \
         unsigned char* dst = tms + (BUF) * 2 * TMS_OPER + sdst[i];                                                  \
         *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};                                                             \
         *reinterpret_cast<u32x2*>(dst + TMS_PLANE) = u32x2{l0, l1};                                                 \
@@ -622,7 +632,7 @@ __global__ __launch_bounds__(NWV * 64) void tri_mul_contract_split_kernel(float*
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const int m = m0 + 32 * si[k] + drow32(q, hi);
-                    if (m < N) Oc[(size_t)m * ldn + n] = acc[k][q];
+                    if (m < N) Oc[(size_t)m * ldn + n] = ASC ? acc[k][q] * iasc : acc[k][q];
                 }
             }
         }
@@ -2218,26 +2228,31 @@ int grid_for(long tasks, int per_wg, int cap) {
 
 // the split contraction by the A/B switches of the caller (waves per workgroup; chunks of operands in flight)
 static void launch_contract_split(int tune, int grid, size_t lds3, hipStream_t stream, float* O, const float* AB, int N, int ldn, int P, int nbatch,
-                                  int tiles, int swap) {
+                                  int tiles, int swap, const unsigned* a_amax = nullptr) {
+    if (a_amax) {       // the scaled first operand of the backward: one form (8 waves)
+        PRD_SET_LDS((tri_mul_contract_split_kernel<8, 2, true>), lds3);
+        hipLaunchKernelGGL((tri_mul_contract_split_kernel<8, 2, true>), dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, a_amax);
+        return;
+    }
     const int nw = PRD_TGET_TMS_NW(tune);
 #ifdef PRD_AB       // (libprd_hip_ab.so) three chunks in flight / 16 waves: measured in rounds 3 and 5, not faster
     if (nw == 8 && PRD_TGET_TMS_D3(tune)) {
         PRD_SET_LDS((tri_mul_contract_split_kernel<8, 3>), lds3);
-        hipLaunchKernelGGL((tri_mul_contract_split_kernel<8, 3>), dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap);
+        hipLaunchKernelGGL((tri_mul_contract_split_kernel<8, 3>), dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
         return;
     }
     if (nw == 16) {
         PRD_SET_LDS((tri_mul_contract_split_kernel<16>), lds3);
-        hipLaunchKernelGGL((tri_mul_contract_split_kernel<16>), dim3(grid), dim3(1024), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap);
+        hipLaunchKernelGGL((tri_mul_contract_split_kernel<16>), dim3(grid), dim3(1024), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
         return;
     }
 #endif
     if (nw == 12) {     // (kept in the shipped library: the second arm of the direct parity test -- same results bit for bit)
         PRD_SET_LDS((tri_mul_contract_split_kernel<12>), lds3);
-        hipLaunchKernelGGL((tri_mul_contract_split_kernel<12>), dim3(grid), dim3(768), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap);
+        hipLaunchKernelGGL((tri_mul_contract_split_kernel<12>), dim3(grid), dim3(768), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
     } else {
         PRD_SET_LDS((tri_mul_contract_split_kernel<8>), lds3);
-        hipLaunchKernelGGL((tri_mul_contract_split_kernel<8>), dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap);
+        hipLaunchKernelGGL((tri_mul_contract_split_kernel<8>), dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
     }
 }
 
@@ -2415,6 +2430,19 @@ extern "C" int prd_tri_mul_contract(float* O, const float* AB, int b, int N, int
         const int vblocks = b * P * tiles * tiles;
         hipLaunchKernelGGL(tri_mul_contract_kernel, dim3(vblocks < 1024 ? vblocks : 1024), dim3(256), 0, stream, O, AB, N, ldn, P, b, tiles);
     }
+    return (int)hipGetLastError();
+}
+
+extern "C" int prd_tri_mul_contract_scaled(float* O, const float* AB, const unsigned* a_amax, int b, int N, int P, int arith, hipStream_t stream) {
+    if (!a_amax) return PRD_ERR_ARG;
+    if ((arith & 0xff) != PRD_ARITH_SPLIT16) return prd_tri_mul_contract(O, AB, b, N, P, arith, stream);      // fp32 operands: nothing to scale
+    PRD_SPLIT_ARITH(arith);
+    if (!O || !AB || b <= 0 || N <= 0) return PRD_ERR_ARG;
+    if (P != 32 && P != 64 && P != 128) return PRD_ERR_UNSUPPORTED;
+    const int ldn = prd_round_up(N, 32);
+    const int tl = prd_ceil_div(N, TMS_T);
+    const int vb3 = b * P * tl * tl;
+    launch_contract_split(tune, vb3 < 256 ? vb3 : 256, (size_t)4 * TMS_OPER, stream, O, AB, N, ldn, P, b, tl, 0, a_amax);
     return (int)hipGetLastError();
 }
 

@@ -74,7 +74,7 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, *, a_off=0, b_off=0, c_off=0, G1=1,
          addmat=None, sad=(0, 0), ldadd=0, colmask=None, scm1=0, fill=0.0, rowmask=None, srm1=0,
          mulmat=None, mul_off=0, smu=(0, 0), ldmul=0, resid=None, res_off=0, sr=(0, 0), ldr=0,
          colscale=None, tile_hint=0, a_ln=False, ln_out=None, c2=None, n_split=0, rowmask_cols=0, rscale=None,
-         slab=False, wsum=None, out_ln=None, a_scale=0.0, mul_pos=False, unsupported_ok=False):
+         slab=False, wsum=None, out_ln=None, a_scale=0.0, mul_pos=False, a_amax=None, unsupported_ok=False):
     """Raw batched GEMM + epilogue (see PrdGemm in include/prd_hip.h).  ``a_ln`` may be 2 (row softmax of A, see the header);
     with ``unsupported_ok`` a PRD_ERR_UNSUPPORTED shape returns None instead of raising (the caller falls back)."""
     g = PrdGemm()
@@ -102,6 +102,7 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, *, a_off=0, b_off=0, c_off=0, G1=1,
     g.out_ln, g.ldol = dptr(out_ln), (out_ln.shape[-1] if out_ln is not None else 0)
     g.a_scale = float(a_scale)
     g.mul_pos = int(mul_pos)
+    g.a_amax = (a_amax if isinstance(a_amax, int) else dptr(a_amax, torch.int32)) if a_amax is not None else None
     g.arith = lib().prd_get_gemm_mode() | (lib().prd_get_tune() << 8)
     import ctypes
     code = lib().prd_gemm(ctypes.byref(g), stream())
@@ -422,13 +423,15 @@ def tri_mul_backward(dy, pair, mask, wts, *, incoming: bool, ws=None):
     # dA[i][k] = sum_j dO[i][j] B^T[k][j];  dB[j][k] = sum_i dO^T[j][i] A^T[k][i]: one contraction over the stacked operands
     # dO | dO^T | B^T | A^T (dO written in place by the output-stage backward, the transposes by prd_tri_mul_bwd_operands)
     ops4 = torch.empty(b, 4 * P, N, ldn, device=dev, dtype=F32)
+    # max |dO| per complex (float bits): the split-16 contraction scales its gradient operand by a power of two from it
+    amax = torch.zeros(b, device=dev, dtype=torch.int32)
     # (the transposed weight images are staged from wo / wog / wp / wg read column-wise: no transposed copies)
-    check(lib().prd_tri_mul_out_bwd(dptr(dz), dptr(dgp), dptr(ops4), dptr(dx1), dptr(dy), dptr(pair), dptr(O), dptr(wo), dptr(bo),
-                                    dptr(wog), dptr(bog), None, None, dptr(x), dptr(lo), 4 * P, b, N, P, stream()),
-          "prd_tri_mul_out_bwd")
+    check(lib().prd_tri_mul_out_bwd_amax(dptr(dz), dptr(dgp), dptr(ops4), dptr(dx1), dptr(dy), dptr(pair), dptr(O), dptr(wo), dptr(bo),
+                                         dptr(wog), dptr(bog), None, None, dptr(x), dptr(lo), 4 * P, b, N, P, dptr(amax, torch.int32), stream()),
+          "prd_tri_mul_out_bwd_amax")
     check(lib().prd_tri_mul_bwd_operands(dptr(ops4), dptr(AB), b, N, P, stream()), "prd_tri_mul_bwd_operands")
     dAB = torch.empty(b, 2 * P, N, ldn, device=dev, dtype=F32)
-    check(lib().prd_tri_mul_contract(dptr(dAB), dptr(ops4), b, N, 2 * P, stream()), "prd_tri_mul_contract")
+    check(lib().prd_tri_mul_contract_scaled(dptr(dAB), dptr(ops4), dptr(amax, torch.int32), b, N, 2 * P, stream()), "prd_tri_mul_contract_scaled")
     del ops4
     dpair = torch.empty_like(pair)
     dpp = torch.empty(b, N, N, 2 * P, device=dev, dtype=F32)
@@ -509,11 +512,12 @@ def sym_rows(x: torch.Tensor, scale: float = 0.5) -> torch.Tensor:
     return out
 
 
-def sym_transpose(dy: torch.Tensor) -> torch.Tensor:
-    """[b, N, N, P] -> [b, N, P, N]: out[b,i,p,j] = dy[b,i,j,p] + dy[b,j,i,p] (prd_sym_transpose)."""
+def sym_transpose(dy: torch.Tensor, amax: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[b, N, N, P] -> [b, N, P, N]: out[b,i,p,j] = dy[b,i,j,p] + dy[b,j,i,p] (prd_sym_transpose_amax).  ``amax`` (optional, int32 [b],
+    zeros): receives max |out| per complex as float bits (PrdGemm.a_amax)."""
     b, N, _, P = dy.shape
     out = torch.empty(b, N, P, N, device=dy.device, dtype=F32)
-    check(lib().prd_sym_transpose(dptr(out), dptr(dy), b, N, P, stream()), "prd_sym_transpose")
+    check(lib().prd_sym_transpose_amax(dptr(out), dptr(dy), b, N, P, dptr(amax, torch.int32), stream()), "prd_sym_transpose_amax")
     return out
 
 

@@ -334,15 +334,20 @@ class OuterLinearFn(torch.autograd.Function):
             s2 = single.detach().contiguous()
             x = ops.layer_norm(s2)
             w1, w2 = w[:, :S], w[:, S:]
+            tile_gemm = dy.is_cuda and ops.split16_gemm_ok(N * P, S, N)
+            # max |dsym| per complex (float bits): the split-16 tile GEMM scales its gradient operand by a power of two from it
+            amax = torch.zeros(b, device=dy.device, dtype=torch.int32) if tile_gemm else None
             if dy.is_cuda and P in (32, 64) and LIBRARY_BWD:
-                dsym = ops.sym_transpose(dy.contiguous()).view(b, N * P, N)     # (dy + dy^T)[b, i, p, j] in one pass
+                dsym = ops.sym_transpose(dy.contiguous(), amax).view(b, N * P, N)     # (dy + dy^T)[b, i, p, j] in one pass
             else:
                 dsym = (dy + dy.transpose(1, 2)).permute(0, 1, 3, 2).reshape(b, N * P, N)
-            if dy.is_cuda and ops.split16_gemm_ok(N * P, S, N):                 # the split-16 tile GEMM, one launch per complex
+                if amax is not None:
+                    amax.copy_(dsym.abs().amax(dim=(1, 2)).view(torch.int32))
+            if tile_gemm:                                                       # the split-16 tile GEMM, one launch per complex
                 xt = x.transpose(1, 2).contiguous()                             # [b, S, N]: B as [N_out][K]
                 T = torch.empty(b, N * P, S, device=dy.device, dtype=torch.float32)
                 for bb in range(b):
-                    ops.gemm(dsym[bb], xt[bb], T[bb], N * P, S, N, N, N, S)
+                    ops.gemm(dsym[bb], xt[bb], T[bb], N * P, S, N, N, N, S, a_amax=amax[bb:bb + 1])
                 T = T.view(b, N, P, S)
             else:
                 T = torch.bmm(dsym, x).view(b, N, P, S)

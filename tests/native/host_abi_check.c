@@ -92,6 +92,12 @@ int main(void) {
     EXPECT(prd_tri_attn_out(0, p, p, p, p, 1, 1, 8, 64, 0, A1, s), PRD_ERR_ARG);
     EXPECT(prd_tri_mul_contract(0, p, 1, 8, 64, A1, s), PRD_ERR_ARG);
     EXPECT(prd_tri_mul_contract(p, p, 1, 8, 48, A0, s), PRD_ERR_UNSUPPORTED);
+    EXPECT(prd_tri_mul_contract_scaled(p, p, 0, 1, 8, 64, A1, s), PRD_ERR_ARG);                              /* no max |dO| */
+    EXPECT(prd_tri_mul_contract_scaled(0, p, (const unsigned*)p, 1, 8, 64, A1, s), PRD_ERR_ARG);
+    EXPECT(prd_tri_mul_contract_scaled(p, p, (const unsigned*)p, 1, 8, 48, A1, s), PRD_ERR_UNSUPPORTED);
+    EXPECT(prd_tri_mul_out_bwd_amax(0, p, p, p, p, p, p, p, p, p, p, p, p, 0, 0, 0, 1, 8, 64, (unsigned*)p, s), PRD_ERR_ARG);
+    EXPECT(prd_sym_transpose_amax(0, p, 1, 8, 64, (unsigned*)p, s), PRD_ERR_ARG);
+    EXPECT(prd_sym_transpose_amax(p, p, 1, 8, 48, (unsigned*)p, s), PRD_ERR_UNSUPPORTED);
     {
         const float* w8[8] = {p, p, p, p, p, p, p, p};
         const float* w7[8] = {p, p, p, 0, p, p, p, p};
