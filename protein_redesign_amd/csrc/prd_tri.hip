@@ -937,8 +937,9 @@ PRD_DEV void ta_block(const float* __restrict__ Kl, const float* __restrict__ Vt
 // fp32 MFMA and VALU instructions share the SIMD's issue time on gfx950 (tools/ubench/coissue_bench.hip: the cycles
 // add, for any number of waves), so the softmax arithmetic is kept as short as it gets: the first block runs the online
 // update and fixes the reference maximum, the others use it unchanged (softmax is shift invariant; a later logit above the
-// reference only makes p > 1).  Should a logit exceed the reference by more than the fp32 exponent range the sum
-// overflows to inf -- then, and only then, the wave redoes its tiles with the online update in every block.
+// reference only makes p > 1).  A logit g log2 units above the reference gives p = 2^g: the sum l overflows past g = 128, the
+// accumulator o = sum p v already past g = 128 - log2|v| (|v| > 1: l finite, o inf).  When either is not finite the wave redoes
+// its tiles with the online update in every block; no other input takes the second pass.
 template <int NTQ, bool MASKED>
 PRD_DEV void ta_keyloop(const float* __restrict__ Kl, const float* __restrict__ Vt, const float* __restrict__ kadd,
                         const float4 (&qf)[NTQ], int npad, int ql, int g4, f32x4 (&o)[NTQ], float (&l_tot)[NTQ],
@@ -962,8 +963,10 @@ PRD_DEV void ta_keyloop(const float* __restrict__ Kl, const float* __restrict__ 
         for (int t = 0; t < NTQ; ++t) {
             l_tot[t] = rows4_sum(l_run[t]);
             bad |= !(l_tot[t] < 3.0e38f);        // inf or NaN
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bad |= !(__builtin_fabsf(o[t][e]) <= 3.4028235e38f);   // o overflows first when |v| > 1
         }
-        if (online_all || !__any(bad)) break;    // the second pass is never needed for logit spreads below 2^127
+        if (online_all || !__any(bad)) break;    // (the online pass keeps p <= 1: o and l stay finite)
         online_all = true;
     }
     if (m_out) {                                 // the reference the sums are relative to (log2 domain), per query: chunk merges

@@ -28,8 +28,8 @@
 //            the idle waves of the other SIMDs (every shed piece is a quarter of the row's keys); those blocks are merged
 //            from partials (reference, sum, O) in LDS after one barrier (flash-decoding merge).
 //            The reference maximum of a piece is fixed by its first tile (later tiles: accumulator preloaded with
-//            -reference, one v_exp_f32 per logit); should a probability leave the fp16 range the piece is redone with the
-//            online update in every tile.
+//            -reference, one v_exp_f32 per logit); should a probability reach 30000 (near the fp16 range; for the fp32
+//            rank-1 tail of v2l the bound that keeps o = sum p v finite) the piece is redone with the online update in every tile.
 //
 // Why this shape (tools/ubench/{valu_rate,overlap,tile_step}_bench.hip, MI355X): the kernel is VALU-bound, not MFMA-bound.
 // Per 32 x 32 logits a wave issues 7 MFMAs (224 matrix-pipe cycles) against 16 v_exp_f32 (8.4 SIMD cycles each), 32
@@ -913,7 +913,8 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_v2l_kernel(
     // tile step (7 MFMAs, 16 exponentials and splits per lane for 1-4 useful columns: N = 769 = 24 x 32 + 1, BASELINE configs[4], paid
     // a 25th tile step in every sweep) but as rank-1 updates in fp32 from K / V rows that phase 1 leaves un-split in `tail`:
     // s = q . k_j, p = 2^(s - ref), l += p, o += p v_j.  The tile's regular K / V planes are still written: the online redo of an
-    // overflowed piece sweeps all tiles the usual way.
+    // overflowed piece sweeps all tiles the usual way.  A tail p >= 30000 requests that redo like a regular tile's: o (V x 16) would
+    // overflow about log2(16 |v|) log2 units before l does.
     const int ntail = (GV && (flags & 64)) ? N - 32 * (nqb - 1) : 0;
     const float* tailkv = reinterpret_cast<const float*>(lds + L.tail);
     const int rstride = gridDim.x / H;
@@ -1278,6 +1279,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_v2l_kernel(
                     const float ka = kadd[32 * (nqb - 1) + j];
                     const float sj = ((ka == 0.f) ? sd : ka) - mref;
                     const float pj = __builtin_amdgcn_exp2f(sj);
+                    big |= !(pj < 30000.0f);            // the bound exp_split keeps: o0 += pj v (v x 16) overflows long before lsum
                     if (hi == 0) lsum += pj;            // (the halves of a query add their row sums in finish / the merge)
                     const float4 v0 = *reinterpret_cast<const float4*>(tk + 8), v1 = *reinterpret_cast<const float4*>(tk + 12);
                     o0[0] = __builtin_fmaf(pj, v0.x, o0[0]); o0[1] = __builtin_fmaf(pj, v0.y, o0[1]);
