@@ -344,6 +344,7 @@ class ProteinReDiffModel(_Base):
         """model.py:528-549: mean over the batch of diffusion_loss / node count, differentiable with respect to every trainable
         parameter (training.network: HIP forward, per-operator backward, per-block recompute).  ``t`` / the noises / the mask
         sources may be injected (parity tests); otherwise they are drawn like the reference draws them."""
+        self.check_widths()
         if not self.setup_schedule:
             self.run_setup_schedule()
             self.setup_schedule = True
@@ -502,6 +503,7 @@ class ProteinReDiffModel(_Base):
         remove_mean (the step-boundary kernel removes the mean itself); ``defer_seq_head``: return the sequence head's HIDDEN units
         instead of the logits (the step-boundary kernel applies the last layer itself)."""
         den = self.Denoiser
+        self.check_widths()                     # before the first launch, with the supported set
         if z.is_cuda and not ops.default_head_layout(den.num_heads, den.head_dim):
             ops.check_head_layout(den.num_heads, den.head_dim, den.pair_dim)     # before the first launch, with the supported set
         if static is None:
@@ -533,6 +535,12 @@ class ProteinReDiffModel(_Base):
         side.join()
         return noise_pred, seq_pred
 
+    def check_widths(self) -> None:
+        """ValueError naming the supported set when a width of this model does not run on the GPU (ops.check_model_widths;
+        host-only: no library call)."""
+        ops.check_model_widths(dict(single_dim=self.single_dim, pair_dim=self.pair_dim, dist_dim=self.dist_dim, time_dim=self.time_dim,
+                                    esm_dim=self.esm_dim, transition_factor=self.Denoiser.transition_factor))
+
     def forward(self, batch, z, seq_t, mask, t):
         """Inference (no_grad / inference_mode): the fused HIP path.  With autograd enabled: the same HIP operators, one
         autograd node each (training.py), so that ``diffusion_loss(...).backward()`` reaches every parameter."""
@@ -547,6 +555,7 @@ class ProteinReDiffModel(_Base):
     # ------------------------------------------------------------------ reverse diffusion (model.py:377-422)
     @torch.inference_mode()
     def sample(self, batch, sources: Optional[Sequence] = None, batch_idx: Optional[int] = None):
+        self.check_widths()
         if sources is None:
             sources = self._sources(batch["atom_mask"].shape[0], batch_idx)
         # the keyed generators are consumed by a loop: remember where they stood so that a repeat draws the same noise
@@ -623,7 +632,8 @@ class ReverseDiffusion:
         self.seq_pred = None
         # inputs of the coming step that the previous step's boundary kernel prepares (single, time embedding)
         import os
-        self.fused_boundary = os.environ.get("PRD_FUSED_BOUNDARY", "1") != "0"
+        # time_dim > 512: the fused boundary has no room for the time features; the separate launches serve any width
+        self.fused_boundary = os.environ.get("PRD_FUSED_BOUNDARY", "1") != "0" and ops.step_boundary_fusable(m.time_dim)
         self.sync = torch.zeros(2, dtype=torch.int32, device=dev)     # [0] arrival counter, [1] sticky non-finite flag (prd_step_boundary)
         self._seq_pred_buf = None               # logits of the last step (written by the step-boundary kernel)
         self.single_in, self.eb_in = m._step_inputs(self.static, self.seq_t, self.rm, self.t)

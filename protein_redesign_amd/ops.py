@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional, Tuple
+from typing import Mapping, Optional, Tuple
 
 import torch
 
@@ -653,6 +653,57 @@ def check_head_layout(H: int, c: int, P: int) -> None:
     if not (1 <= H <= 8 and 4 <= c <= 64 and c % 4 == 0 and P in (32, 64)):
         raise ValueError(f"attention layout num_heads={H}, head_dim={c}, pair_dim={P} does not run on the GPU; "
                          f"supported: {HEAD_LAYOUTS}")
+
+
+MODEL_WIDTHS = ("transition_factor 4; single_dim a multiple of 32 up to 2528 (pair_dim 64) / 5088 (pair_dim 32); "
+                "dist_dim a multiple of 8 up to 624 (pair_dim 64) / 1232 (pair_dim 32); esm_dim a multiple of 4; time_dim even, up to 16384")
+
+
+def _width_refusals(w) -> list:
+    """The widths of ``w`` (a mapping; missing keys are not checked) that an entry point of the library refuses, or that it would
+    read out of bounds with.  Mirrors the refusals of the C entries: prd_outer_linear (S % 8), prd_opm_pair (C = S/4: C % 8, LDS
+    P (C + 4) + P floats <= 160 KiB), prd_pair_init (dist_dim % 8, LDS P (dist_dim + 4) + dist_dim floats <= 160 KiB),
+    prd_time_embed (time_dim even; its feature row is the launch's dynamic LDS, 64 KiB), the row GEMMs (lda % 4); the pair-transition
+    kernels hard-code the hidden width 4 P and take none."""
+    bad = []
+    P = w.get("pair_dim")
+    if w.get("transition_factor", 4) != 4:
+        bad.append(f"transition_factor={w['transition_factor']}")
+    if P not in (32, 64):               # refused by every pair entry itself (PRD_ERR_UNSUPPORTED); the LDS limits below are per pair_dim
+        P = None
+    lds_floats = 40 * 1024
+    S = w.get("single_dim")
+    if S is not None and (S <= 0 or S % 32 or (P is not None and P * (S // 4 + 4) + P > lds_floats)):
+        bad.append(f"single_dim={S}")
+    D = w.get("dist_dim")
+    if D is not None and (D <= 0 or D % 8 or (P is not None and P * (D + 4) + D > lds_floats)):
+        bad.append(f"dist_dim={D}")
+    E = w.get("esm_dim")
+    if E is not None and (E <= 0 or E % 4):
+        bad.append(f"esm_dim={E}")
+    T = w.get("time_dim")
+    if T is not None and (T <= 0 or T % 2 or T > 16384):
+        bad.append(f"time_dim={T}")
+    return bad
+
+
+def check_model_widths(args) -> None:
+    """Raises ValueError naming the supported set when a model width cannot run on the GPU (host-only, no launch).  ``args``: a
+    mapping or an object with the width attributes (an argparse namespace, the model, its Denoiser); absent widths are skipped."""
+    keys = ("single_dim", "pair_dim", "dist_dim", "time_dim", "esm_dim", "transition_factor")
+    if isinstance(args, Mapping):
+        w = {k: args[k] for k in keys if k in args}
+    else:
+        w = {k: getattr(args, k) for k in keys if hasattr(args, k)}
+    bad = _width_refusals(w)
+    if bad:
+        raise ValueError(f"model widths {', '.join(bad)} do not run on the GPU; supported: {MODEL_WIDTHS}")
+
+
+def step_boundary_fusable(time_dim: int) -> bool:
+    """True when prd_step_boundary serves this time embedding (its feature row is a fixed 512-float LDS array); wider ones run
+    the boundary as separate launches (reverse update, then the next step's single / time-embedding inputs)."""
+    return 0 < time_dim <= 512 and time_dim % 2 == 0
 
 
 def tri_attn_heads_supported(N: int, P: int, H: int, c: int) -> bool:

@@ -543,6 +543,7 @@ def network(model, batch: Dict[str, torch.Tensor], z: torch.Tensor, seq_t: torch
     mask = mask.contiguous()
     den = model.Denoiser
     H = den.num_heads
+    model.check_widths()
     if z.is_cuda and not ops.default_head_layout(H, den.head_dim):
         ops.check_head_layout(H, den.head_dim, den.pair_dim)
 

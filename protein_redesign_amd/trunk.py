@@ -418,6 +418,7 @@ class Denoiser(nn.Module):
         ``pair_init`` = (static_pair, z, centers, w_dist, ebeta) is given: the pair input stage then runs here, fused with the
         outer-product update and the first attention-bias heads where the library has that form (ops.pair_head)."""
         b, N = mask.shape
+        ops.check_model_widths(self)
         if mask.is_cuda and not ops.default_head_layout(self.num_heads, self.head_dim):
             ops.check_head_layout(self.num_heads, self.head_dim, self.pair_dim)
         if ws is None:

@@ -1,0 +1,409 @@
+"""GPU: model widths other than the defaults (``--single_dim``, ``--pair_dim``, ``--dist_dim``, ``--time_dim`` of the reference).
+
+Every width-dependent operator against the oracle evaluated in float64 on the device, at widths that land on every dispatch branch
+of its entry point (the branch each case expects is stated by a Python mirror of the entry's conditions, ``*_form`` below), at
+pair_dim 32 and 64, on a ragged batch (two complexes padded to N = 40) and at N = 97; whole network steps at five width
+configurations; hipGraph-replayed trajectories, training gradients, and the separate-launch step boundary against the fused one.
+Bars: whole tensors 1e-5 (rel-L2), the worst 64 x 64 block of pair positions 4e-5, the worst node row 2e-5, steps 2e-5,
+trajectories and gradients 1e-4.  Both arithmetic modes run."""
+import json
+
+import pytest
+import torch
+
+import prd_oracle as O
+from conftest import mismatch_report, rel_l2
+from protein_redesign_amd import _lib, ops
+from protein_redesign_amd.constants import make_args
+from protein_redesign_amd.diffusion_model import ProteinReDiffModel
+from protein_redesign_amd.synthetic import NoiseSource, batch_to, deterministic_state_dict, synthetic_batch
+from protein_redesign_amd.weights import spec_tensors
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+NOISE_SEED = 7
+OP_TOL, BLOCK_TOL, TRAJ_TOL, GRAD_TOL = 1e-5, 2e-5, 1e-4, 1e-4
+PAIR_BLOCK_TOL, ROW_TOL = 4e-5, 2 * OP_TOL
+SIZES40 = [(6, 30), (3, 22)]                # two complexes, padded to N = 40
+SIZES97 = [(7, 90)]
+
+
+@pytest.fixture(params=["fp32", "split16"])
+def gemm_mode(request):
+    prev = _lib.lib().prd_get_gemm_mode()
+    assert _lib.lib().prd_set_gemm_mode(1 if request.param == "split16" else 0) == 0
+    yield request.param
+    assert _lib.lib().prd_set_gemm_mode(prev) == 0
+
+
+# ---------------------------------------------------------------------------------------------------
+# checking helpers (CPU self-test: tests/test_model_widths_cpu.py)
+# ---------------------------------------------------------------------------------------------------
+
+def worst_block(got, want, blk=64):
+    """Largest ||got - want|| / ||want|| over the 64 x 64 blocks of pair positions (i, j) of a [b, N, N, C] tensor; a block whose
+    reference is tiny against the average block is measured against 1e-3 of that average."""
+    b, N = want.shape[:2]
+    T = (N + blk - 1) // blk
+    d = torch.zeros(b, T * blk, T * blk, device=want.device, dtype=torch.float64)
+    w = torch.zeros_like(d)
+    d[:, :N, :N] = (got.to(want.device).double() - want.double()).pow(2).flatten(3).sum(-1)
+    w[:, :N, :N] = want.double().pow(2).flatten(3).sum(-1)
+    e = d.view(b, T, blk, T, blk).sum(dim=(2, 4)).sqrt()
+    r = w.view(b, T, blk, T, blk).sum(dim=(2, 4)).sqrt()
+    worst = e / r.clamp_min(1e-3 * float(r.mean()))
+    k = int(worst.argmax())
+    return float(worst.max()), (k // (T * T), (k // T) % T * blk, k % T * blk)
+
+
+def worst_row(got, want):
+    """Largest ||got - want|| / ||want|| over the node rows of a [b, N, C] tensor (rows with a tiny reference against 1e-3 of the
+    average row norm)."""
+    d = (got.to(want.device).double() - want.double()).flatten(0, -2).norm(dim=-1)
+    r = want.double().flatten(0, -2).norm(dim=-1)
+    worst = d / r.clamp_min(1e-3 * float(r.mean()))
+    return float(worst.max()), int(worst.argmax())
+
+
+def check_pair(got, want, what, rerun=None):
+    assert torch.isfinite(got).all(), what
+    e = rel_l2(got.cpu(), want.cpu())
+    assert e < OP_TOL, (what, mismatch_report(got.cpu(), want.cpu(), rerun))
+    wb, where = worst_block(got, want)
+    assert wb < PAIR_BLOCK_TOL, (what, wb, where)
+
+
+def check_single(got, want, what):
+    assert torch.isfinite(got).all(), what
+    e = rel_l2(got.cpu(), want.cpu())
+    assert e < OP_TOL, (what, e)
+    wr, where = worst_row(got, want)
+    assert wr < ROW_TOL, (what, wr, where)
+
+
+# ---------------------------------------------------------------------------------------------------
+# mirrors of the entries' dispatch conditions (csrc/prd_pair.hip, csrc/prd_spa.hip)
+# ---------------------------------------------------------------------------------------------------
+
+def ol_form(S, P, split):
+    """prd_outer_linear: K-split kernel / split-16 resident image / fp32 resident image / W1 streamed through LDS in K chunks."""
+    if split and S in (128, 256, 512):
+        return "outer_linear_ks_kernel"
+    if split and S % 128 == 0 and 4 * P * S + 4 * P <= 160 * 1024:
+        return "outer_linear_res_h2_kernel"
+    if (P * (S + 4) + P) * 4 <= 150 * 1024 and S % 64 == 0:
+        return "outer_linear_res_kernel"
+    return "outer_linear_kernel"
+
+
+def opm_form(S, split):
+    return "opm_pair_h2_kernel" if split and (S // 4) % 128 == 0 else "opm_pair_kernel"
+
+
+def pair_init_form(D, split):
+    return "pair_init_h2_kernel" if split and D % 128 == 0 else "pair_init_kernel"
+
+
+def pair_head_form(P, D, S, split):
+    C = S // 4
+    lds = 4 * P * D + 4 * P * C + (D + P + 16 * P + 4 * P) * 4
+    return "pair_head_h2_kernel" if split and D % 128 == 0 and C % 128 == 0 and lds <= 160 * 1024 else "separate"
+
+
+def spa_form(S, split):
+    """SPAttention's core at head width c = S in a sampling forward: one launch, or logits GEMM + softmax + P V."""
+    return "prd_spa_attn_core" if split and 64 <= S <= 512 and S % 64 == 0 else "gemm"
+
+
+# ---------------------------------------------------------------------------------------------------
+# models and float64 references
+# ---------------------------------------------------------------------------------------------------
+
+def widths_args(S, P, D=256, T=256, num_blocks=1, **kw):
+    return make_args(single_dim=S, pair_dim=P, dist_dim=D, time_dim=T, head_dim=16, num_heads=4, num_blocks=num_blocks, esm_dim=32,
+                     num_steps=8, mask_prob=0.3, **kw)
+
+
+_MODELS = {}
+
+
+def model_for(args, seed):
+    key = json.dumps([args, seed], sort_keys=True)
+    if key not in _MODELS:
+        if len(_MODELS) > 4:
+            _MODELS.clear()
+        params = deterministic_state_dict(spec_tensors(args), seed=seed, style="random")
+        m = ProteinReDiffModel(args)
+        m.load_state_dict(params)
+        _MODELS[key] = (m.to(DEV).eval(), params)
+    return _MODELS[key]
+
+
+def to64(d):
+    """float64 copies ON THE DEVICE of the floating tensors of a parameter / batch dict (integer tensors moved as they are)."""
+    return {k: (v.to(DEV).double() if v.is_floating_point() else v.to(DEV)) if torch.is_tensor(v) else v for k, v in d.items()}
+
+
+def batch_for(args, sizes, seed):
+    n_total = 40 if sizes == SIZES40 else None
+    batch = synthetic_batch(sizes, esm_dim=args["esm_dim"], seed=seed, n_total=n_total)
+    perms = [NoiseSource(NOISE_SEED, 100 + k).randperm(n) for k, (_, n) in enumerate(sizes)]
+    return O.prepare_batch(batch, args["mask_prob"], perms)
+
+
+def trunk_inputs(args, pb, seed):
+    g = torch.Generator().manual_seed(seed)
+    b, N = pb["atom_mask"].shape
+    single = torch.randn(b, N, args["single_dim"], generator=g) * 1.3 + 0.2
+    pair = torch.randn(b, N, N, args["pair_dim"], generator=g)
+    return single, pair, pb["residue_and_atom_mask"]
+
+
+# ---------------------------------------------------------------------------------------------------
+# 1: the operator table
+# ---------------------------------------------------------------------------------------------------
+
+# (S, P, sizes): S = 96 / 160 / 288: not a multiple of 64 or 128 (fp32 tiles, outer_linear_kernel); 384: split-16 resident image;
+# 640 / 768 / 1024: LDS image too large at P = 64, split-16 resident at P = 32; 1024: C = 256 -> the split-16 OPM tail
+S_CASES = [(S, P, SIZES40) for S in (96, 160, 288, 384, 640, 768, 1024) for P in (32, 64)] + \
+          [(160, 64, SIZES97), (768, 32, SIZES97), (384, 64, SIZES97)]
+
+
+def _sid(c):
+    return f"S{c[0]}-P{c[1]}-N{40 if c[2] == SIZES40 else 97}"
+
+
+def test_mirrors_reach_every_branch():
+    """The operator table lands on every branch the issue of these widths named (otherwise a parametrization drifted)."""
+    ol = {ol_form(S, P, sp) for S, P, _ in S_CASES for sp in (False, True)}
+    assert ol == {"outer_linear_kernel", "outer_linear_res_h2_kernel", "outer_linear_res_kernel"}, ol
+    assert {opm_form(S, sp) for S, _, _ in S_CASES for sp in (False, True)} == {"opm_pair_kernel", "opm_pair_h2_kernel"}
+    assert {pair_init_form(D, sp) for D in (16, 64, 136, 384) for sp in (False, True)} == {"pair_init_kernel", "pair_init_h2_kernel"}
+    assert {spa_form(S, True) for S, _, _ in S_CASES} == {"prd_spa_attn_core", "gemm"}
+    assert any(not ops.ln_fusable(S) for S, _, _ in S_CASES) and any(ops.ln_fusable(S) for S, _, _ in S_CASES)
+
+
+def test_mirrors_agree_with_the_library():
+    """Where the library answers a dispatch question itself, the mirrors must give the same answer."""
+    L = _lib.lib()
+    for S in (96, 160, 192, 384, 512, 576, 640, 768, 1024):
+        assert (L._cdll.prd_spa_attn_core_supported(97, S, 1) == 1) == (spa_form(S, True) == "prd_spa_attn_core"), S
+        assert L._cdll.prd_spa_attn_core_supported(97, S, 0) == 0
+        for P in (32, 64):
+            for D in (16, 64, 128, 136, 256, 384, 512):
+                got = L._cdll.prd_pair_head_supported(P, D, S // 4, 1) == 1
+                assert got == (pair_head_form(P, D, S, True) == "pair_head_h2_kernel"), (P, D, S)
+
+
+@pytest.mark.parametrize("case", S_CASES, ids=_sid)
+def test_outer_linear(case, gemm_mode):
+    S, P, sizes = case
+    form = ol_form(S, P, gemm_mode == "split16")
+    args = widths_args(S, P)
+    model, params = model_for(args, seed=S + P)
+    pb = batch_for(args, sizes, seed=S)
+    single, _, _ = trunk_inputs(args, pb, seed=S + 1)
+    pfx = "Denoiser.folding_blocks.0.outer_linear"
+    with torch.inference_mode():
+        want = O.outer_linear(to64(params), pfx, single.to(DEV).double())
+        mod = model.Denoiser.folding_blocks[0].outer_linear
+        got = mod(single.to(DEV))
+        check_pair(got, want, (form, S, P), rerun=lambda: mod(single.to(DEV)).cpu())
+
+
+@pytest.mark.parametrize("case", S_CASES, ids=_sid)
+def test_outer_product_update(case, gemm_mode):
+    S, P, sizes = case
+    form = opm_form(S, gemm_mode == "split16")
+    args = widths_args(S, P)
+    model, params = model_for(args, seed=S + P)
+    pb = batch_for(args, sizes, seed=S)
+    single, _, mask = trunk_inputs(args, pb, seed=S + 2)
+    with torch.inference_mode():
+        want = O.outer_product_update(to64(params), "Denoiser.opm", single.to(DEV).double(), mask.to(DEV).double())
+        got = model.Denoiser.opm(single.to(DEV), mask.to(DEV))
+        check_pair(got, want, (form, S, P))
+
+
+@pytest.mark.parametrize("case", S_CASES, ids=_sid)
+def test_single_track(case, gemm_mode):
+    """The node-row linears at K = S and 4 S (transition; LayerNorm fused into the GEMM for S <= 512, a separate launch beyond),
+    the folding block's gated attention (q | k | v | gate projection from S) and SPAttention (head width c = S)."""
+    S, P, sizes = case
+    split = gemm_mode == "split16"
+    args = widths_args(S, P)
+    model, params = model_for(args, seed=S + P)
+    pb = batch_for(args, sizes, seed=S)
+    single, pair, mask = trunk_inputs(args, pb, seed=S + 3)
+    p64, s64, z64, m64 = to64(params), single.to(DEV).double(), pair.to(DEV).double(), mask.to(DEV).double()
+    fb = model.Denoiser.folding_blocks[0]
+    pre = "Denoiser.folding_blocks.0"
+    with torch.inference_mode():
+        fc = fb.single_fc
+        got = ops.transition_single(single.to(DEV), fc[1].weight, fc[1].bias, fc[3].weight, fc[3].bias, residual=False)
+        check_single(got, O.transition(p64, pre + ".single_fc", s64), ("transition", ops.ln_fusable(S), S, P))
+        bias = O.pair_bias(p64, pre + ".attn_bias", z64)
+        want = O.gated_attention(p64, pre + ".single_attn", s64, m64, args["num_heads"], args["head_dim"], bias=bias)
+        got = fb.single_attn(single.to(DEV), mask.to(DEV), attn_bias=bias.float().contiguous())
+        check_single(got, want, ("single attention", S, P))
+        want = O.single_pair_attention(p64, "Denoiser.SPAAttnBlock", s64, z64, args["num_heads"])
+        got = model.Denoiser.SPAAttnBlock(single.to(DEV), pair.to(DEV), mask.to(DEV))
+        check_single(got, want, ("SPAttention", spa_form(S, split), S, P))
+
+
+# (S, P, dist_dim, time_dim, sizes): dist_dim 16 / 64 / 136 on the fp32 pair_init kernel in either arithmetic, 384 on the split-16 one
+INPUT_CASES = [(96, 32, 16, 16, SIZES40), (192, 64, 64, 64, SIZES40), (384, 32, 136, 510, SIZES40), (768, 64, 384, 1024, SIZES40),
+               (1024, 32, 384, 256, SIZES40), (160, 64, 136, 1024, SIZES97), (96, 64, 616, 64, SIZES40), (96, 32, 1232, 64, SIZES40)]
+
+
+@pytest.mark.parametrize("case", INPUT_CASES, ids=lambda c: f"S{c[0]}-P{c[1]}-D{c[2]}-T{c[3]}-N{40 if c[4] == SIZES40 else 97}")
+def test_input_stage_and_heads(case, gemm_mode):
+    """single_init (S), time_embed (time_dim), pair_init (dist_dim), the coordinate head (P) and the sequence head (S)."""
+    S, P, D, T, sizes = case
+    form = pair_init_form(D, gemm_mode == "split16")
+    args = widths_args(S, P, D, T)
+    m, params = model_for(args, seed=D + T)
+    pb = batch_for(args, sizes, seed=D)
+    b, N = pb["atom_mask"].shape
+    g = torch.Generator().manual_seed(T)
+    z, seq_t, t = torch.randn(b, N, 3, generator=g), torch.randn(b, N, 21, generator=g), torch.tensor([5, 2][:b])
+    p64, pb64 = to64(params), to64(pb)
+    single, pair, mask = trunk_inputs(args, pb, seed=S + 4)
+    with torch.inference_mode():
+        wsingle, wpair, zij, m2 = O.embed_inputs(p64, args, pb64, z.to(DEV).double(), seq_t.to(DEV).double(), pb64["residue_and_atom_mask"],
+                                                  t.to(DEV))
+        dpb = batch_to(pb, DEV)
+        st = m._static_inputs(dpb)
+        gs = ops.single_init(st["single"], seq_t.to(DEV), dpb["residue_mask"].contiguous(), m.embed_residue_type[1].weight)
+        eb = ops.time_embed(t.to(DEV), m.embed_beta[0].weight, m.embed_beta[1].weight, args["num_steps"])
+        gp = ops.pair_init(st["pair"], z.to(DEV), dpb["residue_and_atom_mask"].contiguous(), m.embed_dist[0].center,
+                           m.embed_dist[1].weight, eb)
+        check_single(gs, wsingle, ("single input", S))
+        check_pair(gp, wpair, (form, P, D, T))
+        s64, z64 = single.to(DEV).double(), pair.to(DEV).double()
+        want_eps, want_logits = O.heads(p64, s64, 0.5 * (z64 + z64.transpose(1, 2)), zij, m2, pb64["residue_and_atom_mask"])
+        dm = dpb["residue_and_atom_mask"].contiguous()
+        wr, sm = m.weight_radial, m.seq_mlp
+        eps = ops.remove_mean(ops.coord_head(pair.to(DEV), z.to(DEV), dm, wr[1].weight, wr[1].bias, wr[3].weight), dm)
+        check_single(eps, want_eps, ("coordinate head", P))
+        logits = ops.linear(ops.linear(ops.layer_norm(single.to(DEV)), sm[1].weight, sm[1].bias, act=1), sm[3].weight)
+        check_single(logits, want_logits, ("sequence head", S))
+
+
+# ---------------------------------------------------------------------------------------------------
+# 2: whole network steps, trajectories, gradients
+# ---------------------------------------------------------------------------------------------------
+
+STEP_CASES = [(96, 32, 16, 16), (192, 64, 64, 64), (384, 32, 136, 510), (768, 64, 384, 1024), (1024, 32, 384, 256)]
+
+
+def _stid(c):
+    return "S{}-P{}-D{}-T{}".format(*c)
+
+
+@pytest.mark.parametrize("case,sizes", [(c, SIZES40) for c in STEP_CASES] + [(STEP_CASES[1], SIZES97)],
+                         ids=[_stid(c) + "-N40" for c in STEP_CASES] + [_stid(STEP_CASES[1]) + "-N97"])
+def test_network_step_vs_oracle(case, sizes, gemm_mode):
+    S, P, D, T = case
+    args = widths_args(S, P, D, T, num_blocks=2)
+    model, params = model_for(args, seed=S + D)
+    assert (pair_head_form(P, D, S, gemm_mode == "split16") == "pair_head_h2_kernel") == (ops.pair_head_supported(P, D, S // 4))
+    pb = batch_for(args, sizes, seed=S + 1)
+    b, N = pb["atom_mask"].shape
+    g = torch.Generator().manual_seed(S + 2)
+    z, seq_t, t = torch.randn(b, N, 3, generator=g), torch.randn(b, N, 21, generator=g), torch.tensor([5, 2][:b])
+    pb64 = to64(pb)
+    with torch.inference_mode():
+        want = O.network_step(to64(params), args, pb64, z.to(DEV).double(), seq_t.to(DEV).double(), pb64["residue_and_atom_mask"],
+                              t.to(DEV))
+        dpb = batch_to(pb, DEV)
+        got = model.sample_step(dpb, z.to(DEV), seq_t.to(DEV), dpb["residue_and_atom_mask"], t.to(DEV))
+    for name, a, w in zip(("noise_pred", "seq_pred"), got, want):
+        assert torch.isfinite(a).all(), name
+        assert rel_l2(a.cpu(), w.cpu()) < BLOCK_TOL, (name, rel_l2(a.cpu(), w.cpu()))
+
+
+def _sample(model, args, seed):
+    batch = batch_to(synthetic_batch([(3, 17)], esm_dim=args["esm_dim"], seed=seed), DEV)
+    return model.sample(batch, sources=[NoiseSource(NOISE_SEED, 0)])
+
+
+@pytest.mark.parametrize("case", [STEP_CASES[0], STEP_CASES[3]], ids=_stid)
+def test_trajectory_vs_oracle(case, gemm_mode):
+    """sample(), T = 8: the first step eager, the rest one replayed hipGraph.  time_dim 1024: the step boundary as separate
+    launches (ops.step_boundary_fusable)."""
+    S, P, D, T = case
+    args = widths_args(S, P, D, T, num_blocks=1)
+    model, params = model_for(args, seed=S + D + 1)
+    assert model.use_hip_graph
+    pos, logits = _sample(model, args, seed=S)
+    batch = synthetic_batch([(3, 17)], esm_dim=args["esm_dim"], seed=S)
+    with torch.inference_mode():
+        wpos, wlogits = O.sample(params, args, batch, [NoiseSource(NOISE_SEED, 0)])
+    assert rel_l2(pos.cpu(), wpos) < TRAJ_TOL
+    assert rel_l2(logits.cpu(), wlogits) < TRAJ_TOL
+
+
+def test_unfused_boundary_equals_fused(gemm_mode, monkeypatch):
+    """PRD_FUSED_BOUNDARY=0 (remove_mean, reverse update, time embedding and single init as separate launches) against the fused
+    step boundary, at the default widths (single 512, pair 64, dist 256, time 256)."""
+    args = widths_args(512, 64, 256, 256, num_blocks=1)
+    model, params = model_for(args, seed=11)
+    fused = [o.cpu() for o in _sample(model, args, seed=12)]
+    monkeypatch.setenv("PRD_FUSED_BOUNDARY", "0")
+    plain = [o.cpu() for o in _sample(model, args, seed=12)]
+    for f, p_ in zip(fused, plain):
+        assert rel_l2(p_, f) < 1e-5
+    batch = synthetic_batch([(3, 17)], esm_dim=args["esm_dim"], seed=12)
+    with torch.inference_mode():
+        want = O.sample(params, args, batch, [NoiseSource(NOISE_SEED, 0)])
+    for p_, w in zip(plain, want):
+        assert rel_l2(p_, w) < TRAJ_TOL
+
+
+@pytest.mark.parametrize("case", [STEP_CASES[0], STEP_CASES[2]], ids=_stid)
+def test_training_gradients_vs_oracle(case, gemm_mode):
+    from test_training_cpu import oracle_grads
+    S, P, D, T = case
+    args = widths_args(S, P, D, T, num_blocks=1)
+    params = deterministic_state_dict(spec_tensors(args), seed=S + 5, style="random")
+    pb = batch_for(args, SIZES40, seed=S + 6)
+    b, N = pb["atom_mask"].shape
+    g = torch.Generator().manual_seed(S + 7)
+    t = torch.tensor([5, 2])
+    nz = O.remove_mean(torch.randn(b, N, 3, generator=g), pb["residue_and_atom_mask"])
+    ns = O.remove_mean(torch.randn(b, N, 21, generator=g), pb["residue_mask"])
+    want_loss, want = oracle_grads(args, params, pb, t, nz, ns)
+    model = ProteinReDiffModel(args)
+    model.load_state_dict(params)
+    model = model.to(DEV).train()
+    model.run_setup_schedule()
+    model.setup_schedule = True
+    dpb = batch_to(pb, DEV)
+    mask = dpb["residue_and_atom_mask"]
+    diff = model.diffusion_loss(dpb, dpb["x"], mask, t.to(DEV), nz.to(DEV), ns.to(DEV))
+    loss = torch.mean(diff / (mask > 0.5).sum(-1))
+    loss.backward()
+    assert abs(float(loss) - want_loss) < GRAD_TOL * abs(want_loss)
+    got = {k: p.grad for k, p in model.named_parameters() if p.requires_grad}
+    assert sorted(got) == sorted(want) and all(v is not None for v in got.values())
+    scale = float(torch.stack([v.double().norm() for v in want.values()]).norm())
+    for k, w in want.items():
+        err = float((got[k].detach().cpu().double() - w.double()).norm())
+        ref = float(w.double().norm())
+        assert err < GRAD_TOL * ref + 1e-6 * scale, (k, err, ref)
+
+
+# ---------------------------------------------------------------------------------------------------
+# 3: refusals on the device path (no launch: the check runs before the first library call)
+# ---------------------------------------------------------------------------------------------------
+
+def test_transition_factor_refused_before_any_launch():
+    args = widths_args(64, 64, transition_factor=2)
+    params = deterministic_state_dict(spec_tensors(args), seed=1, style="random")
+    model = ProteinReDiffModel(args)
+    model.load_state_dict(params)
+    model = model.to(DEV).eval()
+    batch = batch_to(synthetic_batch([(3, 12)], esm_dim=32, seed=2), DEV)
+    with pytest.raises(ValueError, match="transition_factor=2 .*supported: transition_factor 4"):
+        model.sample(batch, sources=[NoiseSource(1, 0)])
