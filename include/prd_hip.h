@@ -515,6 +515,32 @@ size_t prd_tri_attn_heads_workspace_bytes(int b, int N, int P, int H, int c);
 int prd_tri_attn_core_heads(float* og, const float* pair, const float* mask, const float* wq, const float* wk,
                             const float* wv, const float* wg, const float* bg, int ending, int b, int N, int P, int H, int c,
                             float* ws, size_t ws_bytes, int arith, hipStream_t stream);
+/* prd_tri_attn_core_heads that also writes the softmax statistics of every query for the backward core below:
+ * lse [b*N rows][H][N][2] = (m, log2 l) as prd_tri_attn_core_v2_lse defines them (m: the running maximum of the logits in the exp2
+ * domain, replaced logits included; l = sum over the keys of 2^(logit log2(e) - m)), 8-byte aligned (PRD_ERR_ALIGN).  og has the bits
+ * of prd_tri_attn_core_heads; lse == NULL is that launch itself. */
+int prd_tri_attn_core_heads_lse(float* og, float* lse, const float* pair, const float* mask, const float* wq, const float* wk,
+                                const float* wv, const float* wg, const float* bg, int ending, int b, int N, int P, int H, int c,
+                                float* ws, size_t ws_bytes, int arith, hipStream_t stream);
+
+/* Backward core of the triangle attention for the whole set of prd_tri_attn_core_heads (csrc/prd_tri_heads_bwd.hip; 4 x 16 included,
+ * any N >= 1), with the contract of prd_tri_attn_bwd_core: dqkvg [b,N,N,4,H c] by pair position = d(W_q x) | d(W_k x) | d(W_v x) |
+ * d(gate pre-activation), channels head-major, in the pair's own (i, j) order in both orientations; dog = d(og) and og (the forward's
+ * gated head outputs) [b,N,N,H c].  lse (may be NULL): the statistics prd_tri_attn_core_heads_lse wrote; NULL: the kernel finds them
+ * with one more logits-only sweep per row.  x_out (may be NULL): receives LN(pair) [b,N,N,P].  Every element of dqkvg (and x_out) is
+ * written, by one owner and without atomics: the result is bit-reproducible.  Arithmetic: fp32-input MFMA in BOTH modes -- the
+ * `arith` word is validated, its split bit is ignored.  ws: prd_tri_attn_bwd_heads_workspace_bytes bytes (one slab of
+ * round_up(N, 64) (4 CP + 4) floats per workgroup, CP = c padded to 16 / 32 / 64, at most 256 workgroups; nothing grows as N^3;
+ * 0 outside the supported set).  prd_tri_attn_bwd_heads_supported: 1 / 0, host-only (-1 for a bad arith word).
+ * prd_tri_attn_bwd_core_heads: PRD_ERR_ARG for a NULL pointer other than lse / x_out or b, N <= 0, PRD_ERR_UNSUPPORTED outside the
+ * set, PRD_ERR_WORKSPACE when ws_bytes is short, PRD_ERR_ALIGN unless dqkvg, dog, og, pair, x_out and ws are 16-byte (lse: 8-byte)
+ * aligned; nothing is launched on an error.  Offsets are 64-bit. */
+int prd_tri_attn_bwd_heads_supported(int N, int P, int H, int c, int arith);
+size_t prd_tri_attn_bwd_heads_workspace_bytes(int b, int N, int P, int H, int c);
+int prd_tri_attn_bwd_core_heads(float* dqkvg, const float* dog, const float* og, const float* pair, const float* mask,
+                                const float* wq, const float* wk, const float* wv, const float* wg, const float* bg,
+                                const float* lse, float* x_out, int ending, int b, int N, int P, int H, int c,
+                                float* ws, size_t ws_bytes, int arith, hipStream_t stream);
 
 /* bytes of scratch an operator needs: op = "tri_mul" | "tri_attn" */
 size_t prd_workspace_bytes(const char* op, int b, int N, int S, int P);

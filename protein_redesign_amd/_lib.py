@@ -116,6 +116,10 @@ SIGNATURES = {
     "prd_tri_attn_heads_supported": [ci] * 5,
     "prd_tri_attn_heads_workspace_bytes": [ci] * 5,
     "prd_tri_attn_core_heads": [vp] * 8 + [ci] * 6 + [vp, cz, ci, vp],
+    "prd_tri_attn_core_heads_lse": [vp] * 9 + [ci] * 6 + [vp, cz, ci, vp],
+    "prd_tri_attn_bwd_heads_supported": [ci] * 5,
+    "prd_tri_attn_bwd_heads_workspace_bytes": [ci] * 5,
+    "prd_tri_attn_bwd_core_heads": [vp] * 12 + [ci] * 6 + [vp, cz, ci, vp],
 }
 
 GEMM_MODES = {"fp32": 0, "split16": 1, "bf16x3": 1}      # "bf16x3": earlier name of the split-operand mode
@@ -125,11 +129,12 @@ DEFAULT_GEMM_MODE = "split16"       # process default of the Python host side (e
 _ARITH_BEFORE_STREAM = ("prd_coord_head", "prd_pair_head", "prd_pair_init", "prd_opm_pair", "prd_outer_linear", "prd_tri_mul", "prd_tri_mul_contract", "prd_tri_mul_contract_scaled", "prd_tri_mul_proj_bwd",
                         "prd_tri_attn", "prd_tri_attn_core", "prd_tri_attn_out", "prd_pair_transition", "prd_block_tail", "prd_tri_mul_chain",
                         "prd_linear_wgrad", "prd_pair_linear", "prd_spa_attn_core", "prd_tri_attn_pair",
-                        "prd_tri_attn_core_heads")
+                        "prd_tri_attn_core_heads", "prd_tri_attn_core_heads_lse", "prd_tri_attn_bwd_core_heads")
 # ... and the queries that take it as their last argument
 _ARITH_LAST = ("prd_tri_attn_variant", "prd_tri_mul_chain_supported", "prd_tri_attn_core_fused_supported", "prd_tri_attn_stats_bytes",
                "prd_gemm_slab_ok", "prd_pair_head_supported", "prd_pair_linear_supported", "prd_spa_attn_core_supported",
-               "prd_tri_attn_pair_supported", "prd_tri_attn_heads_supported")
+               "prd_tri_attn_pair_supported", "prd_tri_attn_heads_supported",
+               "prd_tri_attn_bwd_heads_supported")
 # entry points without an arithmetic that still dispatch between kernel generations: the PRD_TUNE_* switch word alone
 _TUNE_BEFORE_STREAM = ("prd_tri_attn_core_v2", "prd_tri_attn_core_v2_lse")
 _TUNE_LAST = ("prd_tri_attn_v2_supported", "prd_tri_attn_v2_form")
@@ -248,7 +253,7 @@ def lib():
             fn.argtypes = argtypes
             fn.restype = cz if name in ("prd_workspace_bytes", "prd_linear_wgrad_workspace", "prd_embed_wgrad_workspace", "prd_tri_attn_stats_bytes",
                                         "prd_gemm_slab_workspace", "prd_spa_attn_core_workspace",
-                                        "prd_tri_attn_heads_workspace_bytes") else ci
+                                        "prd_tri_attn_heads_workspace_bytes", "prd_tri_attn_bwd_heads_workspace_bytes") else ci
         if cdll.prd_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} reports PRD_VERSION {cdll.prd_version()}, this binding was written against {ABI_VERSION} "
                                "(include/prd_hip.h lists what changed): rebuild with `python -m protein_redesign_amd.build`")

@@ -88,9 +88,11 @@ PRD_DEV void th_project(const float* Wl, const float (&x)[P / 4], f32x4 (&y)[CP 
     }
 }
 
-template <int P, int CP>
+// LSE: the running (m, log2 l) of every query, which sit in registers at the end of a query group, are also stored to
+// lse [b*N rows][H][N][2] for the backward core (prd_tri_heads_bwd.hip); a compile-time flag, so the plain instance is unchanged
+template <int P, int CP, bool LSE>
 __global__ __launch_bounds__(TH_NW * 64) void tri_attn_heads_kernel(
-    float* __restrict__ og, const float* __restrict__ pair, const float* __restrict__ mask,
+    float* __restrict__ og, float* __restrict__ lse, const float* __restrict__ pair, const float* __restrict__ mask,
     const float* __restrict__ wq, const float* __restrict__ wk, const float* __restrict__ wv,
     const float* __restrict__ wg, const float* __restrict__ bg, int b, int N, int H, int c, int ending) {
     using L = ThLds<P, CP>;
@@ -250,6 +252,10 @@ __global__ __launch_bounds__(TH_NW * 64) void tri_attn_heads_kernel(
                     l += __shfl_xor(l, 32);
                     const float il = 1.0f / l;
                     const int qi = q0 + (wave * TH_QB + qb) * 16 + i;
+                    if constexpr (LSE) {
+                        if (qi < N && g == 0)
+                            *reinterpret_cast<float2*>(lse + ((bu * H + h) * N + qi) * 2) = make_float2(mrun[qb], log2f(l));
+                    }
                     if (qi < N) {
                         float* dst = og + (rowbase + (long)qi * vstep) * HC + h * c;
 #pragma unroll
@@ -275,8 +281,8 @@ __global__ __launch_bounds__(TH_NW * 64) void tri_attn_heads_kernel(
         });                                                                                                     \
     } while (0)
 
-template <int P, int CP>
-void th_launch(float* og, const float* pair, const float* mask, const float* wq, const float* wk, const float* wv,
+template <int P, int CP, bool LSE>
+void th_launch(float* og, float* lse, const float* pair, const float* mask, const float* wq, const float* wk, const float* wv,
                const float* wg, const float* bg, int ending, int b, int N, int H, int c, hipStream_t stream) {
     const size_t lds = th_lds_bytes<P, CP>();
     // persistent, one workgroup of 8 waves per CU (the registers allow no second one): per head the smallest workgroup count that
@@ -287,9 +293,9 @@ void th_launch(float* og, const float* pair, const float* mask, const float* wq,
     if (per_head < 1) per_head = 1;
     const long rounds = (rows_total + per_head - 1) / per_head;
     per_head = (rows_total + rounds - 1) / rounds;
-    PRD_TH_SET_LDS((tri_attn_heads_kernel<P, CP>));
-    hipLaunchKernelGGL((tri_attn_heads_kernel<P, CP>), dim3((unsigned)(per_head * H)), dim3(TH_NW * 64), lds, stream,
-                       og, pair, mask, wq, wk, wv, wg, bg, b, N, H, c, ending);
+    PRD_TH_SET_LDS((tri_attn_heads_kernel<P, CP, LSE>));
+    hipLaunchKernelGGL((tri_attn_heads_kernel<P, CP, LSE>), dim3((unsigned)(per_head * H)), dim3(TH_NW * 64), lds, stream,
+                       og, lse, pair, mask, wq, wk, wv, wg, bg, b, N, H, c, ending);
 }
 
 }  // namespace
@@ -305,18 +311,39 @@ extern "C" size_t prd_tri_attn_heads_workspace_bytes(int b, int N, int P, int H,
     return (size_t)b * N * N * H * c * sizeof(float);       // og; the single-launch kernel keeps no softmax statistics outside registers
 }
 
-extern "C" int prd_tri_attn_core_heads(float* og, const float* pair, const float* mask, const float* wq, const float* wk,
-                                       const float* wv, const float* wg, const float* bg, int ending, int b, int N, int P, int H,
-                                       int c, float* ws, size_t ws_bytes, int arith, hipStream_t stream) {
+namespace {
+
+int th_core(float* og, float* lse, const float* pair, const float* mask, const float* wq, const float* wk, const float* wv,
+            const float* wg, const float* bg, int ending, int b, int N, int P, int H, int c, float* ws, size_t ws_bytes, int arith,
+            hipStream_t stream) {
     PRD_SPLIT_ARITH(arith);                    // validated; the split bit is ignored (fp32 MFMA in both modes)
     if (!og || !pair || !mask || !wq || !wk || !wv || !wg || !bg || !ws || b <= 0 || N <= 0) return PRD_ERR_ARG;
     if (prd_tri_attn_heads_supported(N, P, H, c, arith) != 1) return PRD_ERR_UNSUPPORTED;
     if (ws_bytes < prd_tri_attn_heads_workspace_bytes(b, N, P, H, c)) return PRD_ERR_WORKSPACE;
     if (((uintptr_t)og | (uintptr_t)pair) & 15) return PRD_ERR_ALIGN;
+    if ((uintptr_t)lse & 7) return PRD_ERR_ALIGN;
     const int cp = c <= 16 ? 16 : c <= 32 ? 32 : 64;
-#define PRD_TH(PP, CC) th_launch<PP, CC>(og, pair, mask, wq, wk, wv, wg, bg, ending, b, N, H, c, stream)
+#define PRD_TH(PP, CC)                                                                                          \
+    do {                                                                                                        \
+        if (lse) th_launch<PP, CC, true>(og, lse, pair, mask, wq, wk, wv, wg, bg, ending, b, N, H, c, stream);  \
+        else th_launch<PP, CC, false>(og, lse, pair, mask, wq, wk, wv, wg, bg, ending, b, N, H, c, stream);     \
+    } while (0)
     if (P == 64) { if (cp == 16) PRD_TH(64, 16); else if (cp == 32) PRD_TH(64, 32); else PRD_TH(64, 64); }
     else { if (cp == 16) PRD_TH(32, 16); else if (cp == 32) PRD_TH(32, 32); else PRD_TH(32, 64); }
 #undef PRD_TH
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int prd_tri_attn_core_heads(float* og, const float* pair, const float* mask, const float* wq, const float* wk,
+                                       const float* wv, const float* wg, const float* bg, int ending, int b, int N, int P, int H,
+                                       int c, float* ws, size_t ws_bytes, int arith, hipStream_t stream) {
+    return th_core(og, nullptr, pair, mask, wq, wk, wv, wg, bg, ending, b, N, P, H, c, ws, ws_bytes, arith, stream);
+}
+
+extern "C" int prd_tri_attn_core_heads_lse(float* og, float* lse, const float* pair, const float* mask, const float* wq,
+                                           const float* wk, const float* wv, const float* wg, const float* bg, int ending, int b,
+                                           int N, int P, int H, int c, float* ws, size_t ws_bytes, int arith, hipStream_t stream) {
+    return th_core(og, lse, pair, mask, wq, wk, wv, wg, bg, ending, b, N, P, H, c, ws, ws_bytes, arith, stream);
 }

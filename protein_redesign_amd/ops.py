@@ -12,7 +12,7 @@ from typing import Mapping, Optional, Tuple
 
 import torch
 
-from ._lib import PrdGemm, check, dptr, lib, stream
+from ._lib import PrdGemm, arithmetic, check, dptr, lib, stream
 
 F32 = torch.float32
 
@@ -448,6 +448,7 @@ def tri_mul_backward(dy, pair, mask, wts, *, incoming: bool, ws=None):
 
 
 TRI_ATTN_BWD_V2 = os.environ.get("PRD_TRI_ATTN_BWD_V2", "1") != "0"      # 0: the fp32-MFMA backward core in split-16 mode too (A/B measurements)
+TRI_ATTN_BWD_TUNED_MAX_N = 416      # longest row of the two 4 x 16 backward cores (their LDS layout; training.TRI_ATTN_BWD_MAX_N)
 
 
 def tri_attn_backward(dy, pair, mask, wts, H: int, c: int, *, ending: bool, og=None, lse=None, residual: bool = False):
@@ -455,21 +456,33 @@ def tri_attn_backward(dy, pair, mask, wts, H: int, c: int, *, ending: bool, og=N
     to the pair gradient) with respect to ``pair`` and its seven weight
     tensors on the hand-written backward (csrc/prd_bwd.hip): out-projection backward (row GEMM) -> attention core backward per
     (row, head) -> projections backward (row GEMM) -> LayerNorm backward.  Weight gradients: slab reductions over all N^2 rows
-    (linear_wgrad)."""
+    (linear_wgrad).  The core: 4 x 16 at N <= TRI_ATTN_BWD_TUNED_MAX_N on the two tuned cores (prd_tri_attn_bwd_core, _v2), every
+    other layout and every longer row on the general core (prd_tri_attn_bwd_core_heads: no row limit)."""
     wq, wk, wv, wg, bg, wo, bo = wts
     b, N, _, P = pair.shape
     HC = H * c
     dev = pair.device
     dy = dy.contiguous()
-    if og is None:                                                                              # forward recompute: gated head outputs
+    tuned = default_head_layout(H, c) and N <= TRI_ATTN_BWD_TUNED_MAX_N
+    if og is None and tuned:                                                                    # forward recompute: gated head outputs
         lse = torch.empty(b * N, H, N, 2, device=dev, dtype=F32) if tri_attn_lse_supported(N, P) else None
         og = tri_attn_core(pair, mask, (wq, wk, wv, wg, bg), H, c, ending=ending, lse=lse)
+    elif og is None and default_head_layout(H, c):      # long 4 x 16 rows: the tuned long-row / chunked forward keeps no statistics
+        lse = None
+        og = tri_attn_core(pair, mask, (wq, wk, wv, wg, bg), H, c, ending=ending)
+    elif og is None:
+        lse = torch.empty(b * N, H, N, 2, device=dev, dtype=F32)
+        og = tri_attn_core_heads(pair, mask, (wq, wk, wv, wg, bg), H, c, ending=ending, lse=lse)
     dog = pair_linear(dy.view(-1, P), wo.t())                                                     # d og = dy W_o
-    if dog is None:
-        dog = linear(dy, wo.t().contiguous())
+    if dog is None:                 # general core: fp32 MFMA (a split-16 GEMM loses training-scale gradients to the fp16 subnormal range)
+        with arithmetic(None if tuned else 0):
+            dog = linear(dy, wo.t().contiguous())
     dqkvg = torch.empty(b, N, N, 4, HC, device=dev, dtype=F32)
     x = None
-    if lib().prd_get_gemm_mode() == 1 and TRI_ATTN_BWD_V2 and lib().prd_tri_attn_bwd_core_v2_supported(N, P) == 1:
+    if not tuned:
+        x = torch.empty_like(pair)                                                                # LN(pair), left by the core
+        tri_attn_bwd_core_heads(dog, og, pair, mask, (wq, wk, wv, wg, bg), H, c, ending=ending, lse=lse, x_out=x, dqkvg=dqkvg)
+    elif lib().prd_get_gemm_mode() == 1 and TRI_ATTN_BWD_V2 and lib().prd_tri_attn_bwd_core_v2_supported(N, P) == 1:
         x = torch.empty_like(pair)                                                                # LN(pair), left by the core
         check(lib().prd_tri_attn_bwd_core_v2(dptr(dqkvg), dptr(dog), dptr(og), dptr(pair), dptr(mask), dptr(wq), dptr(wk), dptr(wv), dptr(wg),
                                              dptr(bg), dptr(lse) if lse is not None else None, dptr(x), int(ending), b, N, P, H, c, stream()),
@@ -480,7 +493,8 @@ def tri_attn_backward(dy, pair, mask, wts, H: int, c: int, *, ending: bool, og=N
     wcat = torch.cat([wq, wk, wv, wg], dim=0)                                                     # [4 HC, P]
     dxn = pair_linear(dqkvg.view(-1, 4 * HC), wcat.t())                                          # gradient of LN(pair)
     if dxn is None:
-        dxn = linear(dqkvg.view(b, N, N, 4 * HC), wcat.t().contiguous())
+        with arithmetic(None if tuned else 0):
+            dxn = linear(dqkvg.view(b, N, N, 4 * HC), wcat.t().contiguous())
     dpair = torch.empty_like(pair)
     check(lib().prd_ln_rows_bwd(dptr(dpair), dptr(dxn), dptr(pair), dptr(dy) if residual else None, b * N * N, P, stream()), "prd_ln_rows_bwd")
     x = (x if x is not None else layer_norm(pair.contiguous())).view(-1, P)
@@ -716,18 +730,48 @@ def tri_attn_heads_ws_floats(b: int, N: int, P: int, H: int, c: int) -> int:
     return int(lib().prd_tri_attn_heads_workspace_bytes(b, N, P, H, c)) // 4
 
 
-def tri_attn_core_heads(pair, mask, wts, H: int, c: int, *, ending: bool, ws=None) -> torch.Tensor:
+def tri_attn_core_heads(pair, mask, wts, H: int, c: int, *, ending: bool, ws=None, lse=None) -> torch.Tensor:
     """The general-layout core (prd_tri_attn_core_heads): og [b,N,N,H c] = the gated head outputs, a view of the start of ``ws``
-    (allocated here if not given or too small).  wts = (q.w, k.w, v.w, gate.w, gate.b)."""
+    (allocated here if not given or too small).  wts = (q.w, k.w, v.w, gate.w, gate.b).  ``lse`` [b*N, H, N, 2]: receives
+    (m, log2 l) of every query for tri_attn_backward (prd_tri_attn_core_heads_lse; og has the same bits)."""
     b, N, _, P = pair.shape
     check_head_layout(H, c, P)
     need = tri_attn_heads_ws_floats(b, N, P, H, c)
     if ws is None or ws.numel() < need:
         ws = torch.empty(need, device=pair.device, dtype=F32)
     og = ws[:b * N * N * H * c].view(b, N, N, H * c)
+    if lse is not None:
+        if lse.numel() != b * N * H * N * 2:
+            raise ValueError("tri_attn_core_heads: lse must be [b*N, H, N, 2]")
+        check(lib().prd_tri_attn_core_heads_lse(dptr(og), dptr(lse), dptr(pair), dptr(mask), *[dptr(w) for w in wts], int(ending), b, N, P,
+                                                H, c, dptr(ws), ws.numel() * 4, stream()), "prd_tri_attn_core_heads_lse")
+        return og
     check(lib().prd_tri_attn_core_heads(dptr(og), dptr(pair), dptr(mask), *[dptr(w) for w in wts], int(ending), b, N, P, H, c,
                                         dptr(ws), ws.numel() * 4, stream()), "prd_tri_attn_core_heads")
     return og
+
+
+def tri_attn_bwd_heads_supported(N: int, P: int, H: int, c: int) -> bool:
+    """True when prd_tri_attn_bwd_core_heads serves this shape (the set of the general forward core, any N)."""
+    return lib().prd_tri_attn_bwd_heads_supported(N, P, H, c) == 1
+
+
+def tri_attn_bwd_core_heads(dog, og, pair, mask, wts, H: int, c: int, *, ending: bool, lse=None, x_out=None, dqkvg=None, ws=None):
+    """The general backward core (prd_tri_attn_bwd_core_heads) called directly: dqkvg [b,N,N,4,H c] from dog, og [b,N,N,H c];
+    wts = (q.w, k.w, v.w, gate.w, gate.b).  ``lse``: the statistics of tri_attn_core_heads(lse=) (None: recomputed in the kernel);
+    ``x_out``: receives LN(pair)."""
+    b, N, _, P = pair.shape
+    HC = H * c
+    check_head_layout(H, c, P)
+    if dqkvg is None:
+        dqkvg = torch.empty(b, N, N, 4, HC, device=pair.device, dtype=F32)
+    need = int(lib().prd_tri_attn_bwd_heads_workspace_bytes(b, N, P, H, c)) // 4
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=pair.device, dtype=F32)
+    check(lib().prd_tri_attn_bwd_core_heads(dptr(dqkvg), dptr(dog), dptr(og), dptr(pair), dptr(mask), *[dptr(w) for w in wts], dptr(lse),
+                                            dptr(x_out), int(ending), b, N, P, H, c, dptr(ws), ws.numel() * 4, stream()),
+          "prd_tri_attn_bwd_core_heads")
+    return dqkvg
 
 
 def tri_attn(pair, mask, wts, H: int, c: int, *, ending: bool, residual: bool, out=None, ws=None) -> torch.Tensor:

@@ -400,7 +400,8 @@ class TriMulFn(torch.autograd.Function):
 class TriAttnFn(torch.autograd.Function):
     """TriangleAttention update with a hand-written backward (ops.tri_attn_backward: out-projection backward, flash-style attention
     core backward per (row, head), projection + LayerNorm backward on HIP kernels; weight-gradient reductions through BLAS).
-    Rows longer than the backward core's LDS layout (N > ~400) fall back to the recompute-in-torch node (HipOp)."""
+    4 heads x 16 channels run the tuned forward cores, and the tuned backward cores up to TRI_ATTN_BWD_MAX_N positions; every other
+    layout, and longer 4 x 16 rows, take the general backward core (prd_tri_attn_bwd_core_heads), which has no row limit."""
 
     @staticmethod
     def forward(ctx, pair, mask, ending: bool, H: int, c: int, residual: bool, *wts):
@@ -412,10 +413,16 @@ class TriAttnFn(torch.autograd.Function):
             # the queries (2 floats per query and head) are kept for the backward instead of being recomputed by a second core launch
             ctx.keep_og = not USE_CHECKPOINT
             b, N, _, P = p.shape
-            lse = (torch.empty(b * N, H, N, 2, device=p.device, dtype=torch.float32)
-                   if ctx.keep_og and p.is_cuda and ops.tri_attn_lse_supported(N, P) else None)
-            og = ops.tri_attn_core(p, mask, w[:5], H, c, ending=ending, lse=lse)
-            out = ops.tri_attn_out(p, og, w[5], w[6], residual=residual)
+            if ops.default_head_layout(H, c):
+                # (the long-row / chunked forward cores beyond TRI_ATTN_BWD_MAX_N keep no statistics: the general backward core finds them)
+                lse = (torch.empty(b * N, H, N, 2, device=p.device, dtype=torch.float32)
+                       if ctx.keep_og and p.is_cuda and N <= TRI_ATTN_BWD_MAX_N and ops.tri_attn_lse_supported(N, P) else None)
+                og = ops.tri_attn_core(p, mask, w[:5], H, c, ending=ending, lse=lse)
+                out = ops.tri_attn_out(p, og, w[5], w[6], residual=residual)
+            else:
+                lse = torch.empty(b * N, H, N, 2, device=p.device, dtype=torch.float32) if ctx.keep_og else None
+                og = ops.tri_attn_core_heads(p, mask, w[:5], H, c, ending=ending, lse=lse)
+                out = ops.linear(og, w[5], w[6], resid=p if residual else None)
         ctx.has_lse = lse is not None
         ctx.save_for_backward(pair, mask, *wts, *([og] if ctx.keep_og else []), *([lse] if ctx.has_lse else []))
         return out
@@ -435,25 +442,15 @@ class TriAttnFn(torch.autograd.Function):
 
 TRI_ATTN_BWD_MAX_N = 416        # prd_tri_attn_bwd_core keeps q, k, v, do of a row (padded to 32) and the head's weights in LDS (the gate is
                                 # parked in its own output slot): 156 KB at N = 416 (pitch 20 floats); BASELINE configs[3] draws N <= 384.
-                                # Longer rows recompute through torch_ref
+                                # Longer rows (and other layouts) take the general backward core (ops.TRI_ATTN_BWD_TUNED_MAX_N)
 
 
 def tri_attn_update(ta, pair: torch.Tensor, mask: torch.Tensor, residual: bool = False) -> torch.Tensor:
     """The update, or with ``residual`` pair + update."""
     a = ta.attn
     H, c, end = a.num_heads, a.head_dim, ta.mode == "ending"
-    # the hand-written backward cores are 4 x 16 only: other layouts run the general forward core and recompute through torch_ref
-    if pair.shape[1] <= TRI_ATTN_BWD_MAX_N and ops.default_head_layout(H, c):
-        return TriAttnFn.apply(pair, mask, end, H, c, residual, *a.weights())
-
-    def ref(p, *w):
-        return R.triangle_attention(p, mask, *w, H, c, ending=end)
-
-    def hip(p, *w):
-        return ops.tri_attn(p.contiguous(), mask, w, H, c, ending=end, residual=False)
-
-    upd = HipOp.apply(hip, ref, pair, *a.weights())
-    return pair + upd if residual else upd
+    ops.check_head_layout(H, c, pair.shape[-1])
+    return TriAttnFn.apply(pair, mask, end, H, c, residual, *a.weights())
 
 
 def tri_mul_update(tm, pair: torch.Tensor, mask: torch.Tensor, residual: bool = False) -> torch.Tensor:

@@ -7,7 +7,14 @@
   * the general core at 4 x 16 against the tuned core (ops.tri_attn_core) at the same shapes;
   * steps/s of sample_step and of one replayed sample() step at the BASELINE configs[1] shape (256 residues + 64 ligand atoms,
     single_dim 512, pair_dim 64, 4 blocks) with --num_heads 8 --head_dim 32.
-Median of CUDA-event timings after warm-up."""
+Median of CUDA-event timings after warm-up.
+
+    python tools/head_layout_bench.py --backward [--out profiles/head_layouts_backward.txt]
+
+  * forward + backward of training.tri_attn_update (TriAttnFn: the general backward core, prd_tri_attn_bwd_core_heads) against the
+    HipOp recompute through torch_ref.triangle_attention that it replaced (kept callable here, not in the package), per (N, layout),
+    the two arms alternating in one process: time and torch.cuda.max_memory_allocated above the inputs.  4 x 16 at N = 769 is the
+    former "> 416" fallback; 4 x 16 at N = 320 runs the tuned backward cores and is timed against the general core as well."""
 import argparse
 import os
 import statistics
@@ -18,7 +25,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from protein_redesign_amd import _lib, ops, torch_ref  # noqa: E402
+from protein_redesign_amd import _lib, ops, torch_ref, training  # noqa: E402
 from protein_redesign_amd.constants import make_args  # noqa: E402
 from protein_redesign_amd.diffusion_model import ProteinReDiffModel, ReverseDiffusion  # noqa: E402
 from protein_redesign_amd.synthetic import NoiseSource, batch_to, deterministic_state_dict, synthetic_batch  # noqa: E402
@@ -66,6 +73,68 @@ def ops_table(lines):
             print(line, flush=True)
 
 
+def recompute_update(pair, mask, wts, H, c):
+    """What training.tri_attn_update did for these shapes before the general backward core: HIP forward, torch_ref under autograd."""
+    def ref(p, *w):
+        return torch_ref.triangle_attention(p, mask, *w, H, c, ending=False)
+
+    def hip(p, *w):
+        return ops.tri_attn(p.contiguous(), mask, w, H, c, ending=False, residual=False)
+    return training.HipOp.apply(hip, ref, pair, *wts)
+
+
+def backward_table(lines):
+    from types import SimpleNamespace
+    P = 64
+    for N in (320, 769):
+        for H, c in ((8, 32), (4, 16)):
+            g = torch.Generator(device="cuda").manual_seed(N)
+            HC = H * c
+            pair = torch.randn(1, N, N, P, device="cuda", generator=g).requires_grad_(True)
+            mask = torch.ones(1, N, device="cuda")
+            wts = [torch.randn(HC, P, device="cuda", generator=g) / 8 for _ in range(4)] + [torch.randn(HC, device="cuda", generator=g)]
+            wts += [torch.randn(P, HC, device="cuda", generator=g) / HC ** 0.5, torch.randn(P, device="cuda", generator=g)]
+            wts = [w.requires_grad_(True) for w in wts]
+            dy = torch.randn(1, N, N, P, device="cuda", generator=g)
+            ta = SimpleNamespace(attn=SimpleNamespace(num_heads=H, head_dim=c, weights=lambda: wts), mode="starting")
+
+            def new():
+                return torch.autograd.grad(training.tri_attn_update(ta, pair, mask), [pair, *wts], dy)
+
+            def old():
+                return torch.autograd.grad(recompute_update(pair, mask, wts, H, c), [pair, *wts], dy)
+
+            def general():                  # 4 x 16 at N <= 416: the general core where the tuned cores are the dispatch
+                prev, ops.TRI_ATTN_BWD_TUNED_MAX_N = ops.TRI_ATTN_BWD_TUNED_MAX_N, 0
+                try:
+                    return new()
+                finally:
+                    ops.TRI_ATTN_BWD_TUNED_MAX_N = prev
+            arms = [("hand-written", new), ("HipOp recompute", old)]
+            if (H, c) == (4, 16) and N <= training.TRI_ATTN_BWD_MAX_N:
+                arms = [("tuned cores", new), ("HipOp recompute", old), ("general core", general)]
+            res = {name: [] for name, _ in arms}
+            peak = {}
+            for rnd in range(4):            # round 0 warms up; the arms alternate
+                for name, fn in arms:
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
+                    before = torch.cuda.memory_allocated()
+                    a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    out = fn()
+                    e.record()
+                    e.synchronize()
+                    del out
+                    peak[name] = torch.cuda.max_memory_allocated() - before
+                    if rnd:
+                        res[name].append(a.elapsed_time(e) * 1e3)
+            line = f"N={N:4d} H={H} c={c:2d} P={P} forward + backward: " + "; ".join(
+                f"{name} {statistics.median(res[name]):9.1f} us, peak {peak[name] / 1e9:6.3f} GB" for name, _ in arms)
+            lines.append(line)
+            print(line, flush=True)
+
+
 def step_table(lines):
     args = make_args(single_dim=512, pair_dim=64, num_blocks=4, head_dim=32, num_heads=8, num_steps=1000)
     model = ProteinReDiffModel(args)
@@ -89,8 +158,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--steps-only", action="store_true")
+    ap.add_argument("--backward", action="store_true", help="the training backward against the HipOp recompute it replaced")
     a = ap.parse_args()
     lines = [f"# {torch.cuda.get_device_name(0)}"]
+    if a.backward:
+        backward_table(lines)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if not a.steps_only:
         ops_table(lines)
     step_table(lines)
