@@ -168,6 +168,23 @@ size_t prd_gemm_slab_workspace(int M, int N, int K);
 int prd_gemm_slab_ok(int M, int N, int K, int arith);   /* 1 when a PrdGemm of this shape with `ws` set takes the K-slab path */
 int prd_gemm(const PrdGemm* args, hipStream_t stream);
 
+/* First layer of the single-track transition with the attention's output projection FOLDED in (modules.py:306-311 after
+ * modules.py:185-225): for og [M,HC] = the gated attention output BEFORE its out_proj (prd_single_attn_core),
+ *   single_out = single + og Wo^T + bo                       [M,S]   (what the out-projection launch would have written)
+ *   h          = relu(LN(single_out) W1^T + b1)              [M,Hd]  (LayerNorm without affine, eps 1e-5)
+ * in TWO launches (K-slab GEMM on [single | og] + reduce) instead of three: single_out W1^T = single W1^T + og (W1 Wo)^T + W1 bo.
+ * Packed once per weight set by the caller:  w1cat [Hd, S + HC] = [W1 | W1 Wo] (the product formed in float64, rounded once),
+ * woT [HC, S] = Wo^T, wsum1 [Hd] = row sums of W1, w1bo [Hd] = W1 bo;  bo [S], b1 [Hd] as in the state_dict.
+ * ws: prd_gemm_slab_workspace(M, Hd, S) bytes.  PRD_ARITH_SPLIT16 only, HC = 64, and a first layer that the K-slab path runs as
+ * four K-slab groups of one slab each (S = 512, 96 <= M <= 640): prd_single_fc1_folded_ok returns 1 there, and the call returns
+ * PRD_ERR_UNSUPPORTED elsewhere (the caller then keeps the separate launches).  Every pointer except woT / bo / single_out 16-byte
+ * aligned (PRD_ERR_ALIGN).  single_out may be single itself (a workgroup reads its row before it writes it).
+ * (Added without a PRD_VERSION step: existing calls and structures are unchanged, a caller built against 101 runs as before.) */
+int prd_single_fc1_folded_ok(int M, int S, int HC, int Hd, int arith);
+int prd_single_fc1_folded(const float* single, const float* og, const float* w1cat, const float* woT, const float* bo,
+                          const float* wsum1, const float* w1bo, const float* b1, float* single_out, float* h,
+                          int M, int S, int HC, int Hd, float* ws, size_t ws_bytes, int arith, hipStream_t stream);
+
 /* nn.LayerNorm over the last axis, eps 1e-5; gamma/beta may be NULL (elementwise_affine=False). */
 int prd_ln_rows(const float* x, float* y, const float* gamma, const float* beta,
                 int rows, int C, int ldx, int ldy, hipStream_t stream);

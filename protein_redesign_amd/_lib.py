@@ -50,6 +50,8 @@ SIGNATURES = {
     "prd_gemm": [C.POINTER(PrdGemm), vp],
     "prd_gemm_slab_workspace": [ci, ci, ci],
     "prd_gemm_slab_ok": [ci, ci, ci, ci],
+    "prd_single_fc1_folded_ok": [ci] * 5,
+    "prd_single_fc1_folded": [vp] * 10 + [ci] * 4 + [vp, cz, ci, vp],
     "prd_ln_rows": [vp, vp, vp, vp, ci, ci, ci, ci, vp],
     "prd_softmax_rows": [vp, ci, ci, ci, vp],
     "prd_static_pair": [vp] * 13 + [ci] * 5 + [vp],
@@ -129,12 +131,12 @@ DEFAULT_GEMM_MODE = "split16"       # process default of the Python host side (e
 _ARITH_BEFORE_STREAM = ("prd_coord_head", "prd_pair_head", "prd_pair_init", "prd_opm_pair", "prd_outer_linear", "prd_tri_mul", "prd_tri_mul_contract", "prd_tri_mul_contract_scaled", "prd_tri_mul_proj_bwd",
                         "prd_tri_attn", "prd_tri_attn_core", "prd_tri_attn_out", "prd_pair_transition", "prd_block_tail", "prd_tri_mul_chain",
                         "prd_linear_wgrad", "prd_pair_linear", "prd_spa_attn_core", "prd_tri_attn_pair",
-                        "prd_tri_attn_core_heads", "prd_tri_attn_core_heads_lse", "prd_tri_attn_bwd_core_heads")
+                        "prd_tri_attn_core_heads", "prd_tri_attn_core_heads_lse", "prd_tri_attn_bwd_core_heads", "prd_single_fc1_folded")
 # ... and the queries that take it as their last argument
 _ARITH_LAST = ("prd_tri_attn_variant", "prd_tri_mul_chain_supported", "prd_tri_attn_core_fused_supported", "prd_tri_attn_stats_bytes",
                "prd_gemm_slab_ok", "prd_pair_head_supported", "prd_pair_linear_supported", "prd_spa_attn_core_supported",
                "prd_tri_attn_pair_supported", "prd_tri_attn_heads_supported",
-               "prd_tri_attn_bwd_heads_supported")
+               "prd_tri_attn_bwd_heads_supported", "prd_single_fc1_folded_ok")
 # entry points without an arithmetic that still dispatch between kernel generations: the PRD_TUNE_* switch word alone
 _TUNE_BEFORE_STREAM = ("prd_tri_attn_core_v2", "prd_tri_attn_core_v2_lse")
 _TUNE_LAST = ("prd_tri_attn_v2_supported", "prd_tri_attn_v2_form")

@@ -751,11 +751,19 @@ static int launch_ring_bkn(const PrdGemm& g, dim3 grid, hipStream_t stream) {   
 // on one CU: the guide's `splitk-seam` row prices it above the kernel boundary it would save.)
 constexpr int SL_BM = 160, SL_BN = 64, SL_KS = 128, SL_NW = 10;
 constexpr int SL_LDS = (SL_BM + SL_BN) * SL_KS * 4;                  // hi | lo planes of A and W: 112 KB
+// EX > 0: a SECOND A segment A2 [M][K2] (row pitch lda2) whose weights are columns K .. K + K2 of W's rows -- C = [A | A2] W^T with
+// K2 = 16 EX SK: every slab group takes 16 EX of the K2 columns on top of its slabs (EX more MFMA steps after the 8 per slab, in an
+// LDS region of its own: rows of 32 EX bytes per plane, read as one contiguous block per step), so the groups stay balanced and the
+// grid is the same one workgroup per CU.  The single track's attention out-projection rides in its transition's first layer
+// this way (prd_single_fc1_folded).
+template <int EX>
 __global__ __launch_bounds__(SL_NW * 64) void gemm_slab_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                                float* __restrict__ ws, int M, int N, int K, int lda, int ldb,
-                                                               int tiles_m, int tiles_n, int nslab, int spw, int xmap, float wscale) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char sl[];      // A hi [160][256 B] | A lo | W hi [64][256 B] | W lo
+                                                               int tiles_m, int tiles_n, int nslab, int spw, int xmap, float wscale,
+                                                               const float* __restrict__ A2, int lda2) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sl[];      // A hi [160][256 B] | A lo | W hi [64][256 B] | W lo | extra
     constexpr int APL = SL_BM * 256, WOFF = 2 * APL, WPL = SL_BN * 256;
+    constexpr int XOFF = SL_LDS, XROW = 32 * (EX > 0 ? EX : 1), XPL = (SL_BM + SL_BN) * XROW, XQ = 4 * (EX > 0 ? EX : 1);   // extra: [160 A2 rows | 64 W rows] hi | lo
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rt = wave >> 1, ct = wave & 1;
@@ -784,6 +792,18 @@ __global__ __launch_bounds__(SL_NW * 64) void gemm_slab_kernel(const float* __re
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = 0.f;
     const int s_end = (sg + 1) * spw < nslab ? (sg + 1) * spw : nslab;
+    // extra segment: 160 x 4 EX pieces of A2 (EX per thread) and 64 x 4 EX pieces of W (threads < 256 EX), requested first
+    u32x4 xa[EX > 0 ? EX : 1], xb;
+    if (EX > 0) {
+        const prd_rsrc r2 = make_rsrc(A2 + (size_t)m0 * lda2 + (size_t)sg * 16 * EX), rw = make_rsrc(W + (size_t)n0 * ldb + K + (size_t)sg * 16 * EX);
+#pragma unroll
+        for (int i = 0; i < EX; ++i) {
+            const int idx = tid + SL_NW * 64 * i, row = idx / XQ, q = idx - row * XQ;
+            xa[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r2, (m0 + row < M) ? ((unsigned)row * lda2 + 4 * q) * 4u : BUF_OOB, 0, 0));
+        }
+        const int row = tid / XQ, q = tid - row * XQ;
+        xb = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, (row < SL_BN && n0 + row < N) ? ((unsigned)row * ldb + 4 * q) * 4u : BUF_OOB, 0, 0));
+    }
     for (int sl_i = sg * spw; sl_i < s_end; ++sl_i) {
         const prd_rsrc ra = make_rsrc(A + (size_t)m0 * lda + (size_t)sl_i * SL_KS), rb = make_rsrc(W + (size_t)n0 * ldb + (size_t)sl_i * SL_KS);
         u32x4 va[8], vb[4];
@@ -798,6 +818,27 @@ __global__ __launch_bounds__(SL_NW * 64) void gemm_slab_kernel(const float* __re
             vb[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, (row < SL_BN && n0 + row < N) ? ((unsigned)row * ldb + 4 * piece) * 4u : BUF_OOB, 0, 0));
         }
         if (sl_i > sg * spw) __syncthreads();                               // the previous slab's fragments have been read
+        if (EX > 0 && sl_i == sg * spw) {                                   // the extra segment goes to LDS under the first slab's loads
+#pragma unroll
+            for (int i = 0; i < EX; ++i) {
+                const int idx = tid + SL_NW * 64 * i, row = idx / XQ, q = idx - row * XQ;
+                unsigned h0, l0, h1, l1;
+                split2h(__uint_as_float(xa[i][0]), __uint_as_float(xa[i][1]), h0, l0);
+                split2h(__uint_as_float(xa[i][2]), __uint_as_float(xa[i][3]), h1, l1);
+                unsigned char* d_ = sl + XOFF + row * XROW + (q >> 1) * 16 + (q & 1) * 8;
+                *reinterpret_cast<u32x2*>(d_) = u32x2{h0, h1};
+                *reinterpret_cast<u32x2*>(d_ + XPL) = u32x2{l0, l1};
+            }
+            const int row = tid / XQ, q = tid - row * XQ;
+            if (row < SL_BN) {
+                unsigned h0, l0, h1, l1;
+                split2h(wscale * __uint_as_float(xb[0]), wscale * __uint_as_float(xb[1]), h0, l0);
+                split2h(wscale * __uint_as_float(xb[2]), wscale * __uint_as_float(xb[3]), h1, l1);
+                unsigned char* d_ = sl + XOFF + (SL_BM + row) * XROW + (q >> 1) * 16 + (q & 1) * 8;
+                *reinterpret_cast<u32x2*>(d_) = u32x2{h0, h1};
+                *reinterpret_cast<u32x2*>(d_ + XPL) = u32x2{l0, l1};
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int row = prow + 20 * i;
@@ -828,6 +869,18 @@ __global__ __launch_bounds__(SL_NW * 64) void gemm_slab_kernel(const float* __re
             const unsigned so = (unsigned)((2 * st + hi) ^ (r & 15)) << 4;   // (rt * 32 + r) & 15 == r & 15
             const u32x4 ah = *reinterpret_cast<const u32x4*>(ab + so), al = *reinterpret_cast<const u32x4*>(ab + APL + so);
             const u32x4 bh = *reinterpret_cast<const u32x4*>(bb + so), bl = *reinterpret_cast<const u32x4*>(bb + WPL + so);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, ah), __builtin_bit_cast(f16x8_t, bh), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, ah), __builtin_bit_cast(f16x8_t, bl), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, al), __builtin_bit_cast(f16x8_t, bh), acc, 0, 0, 0);
+        }
+    }
+    if (EX > 0) {                                                           // (staged before the first slab's barrier)
+        const unsigned char* ab = sl + XOFF + (rt * 32 + r) * XROW + hi * 16;
+        const unsigned char* bb = sl + XOFF + (SL_BM + ct * 32 + r) * XROW + hi * 16;
+#pragma unroll
+        for (int st = 0; st < EX; ++st) {
+            const u32x4 ah = *reinterpret_cast<const u32x4*>(ab + 32 * st), al = *reinterpret_cast<const u32x4*>(ab + XPL + 32 * st);
+            const u32x4 bh = *reinterpret_cast<const u32x4*>(bb + 32 * st), bl = *reinterpret_cast<const u32x4*>(bb + XPL + 32 * st);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, ah), __builtin_bit_cast(f16x8_t, bh), acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, ah), __builtin_bit_cast(f16x8_t, bl), acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, al), __builtin_bit_cast(f16x8_t, bh), acc, 0, 0, 0);
@@ -924,6 +977,74 @@ __global__ __launch_bounds__(128) void gemm_slab_reduce_kernel(PrdGemm g, const 
     }
 }
 
+// Reduce launch of the single track's first transition layer with the attention out-projection FOLDED in (prd_single_fc1_folded):
+// the slab GEMM above ran on [single | og] with [W1 | W1 Wo], so its sum is single W1^T + og (W1 Wo)^T = (single' - bo) W1^T for
+// single' = single + og Wo^T + bo, the residual row the separate out-projection launch used to write.  ONE workgroup per row, 128
+// threads per 512-column chunk of the layer (N = 2048: 512 threads): thread t first forms element t of single' itself -- 64 fma
+// from the og row (wave-uniform: scalar loads) and row j of Wo^T (coalesced) -- so the row's statistics come from the values the
+// next layers will see, the workgroup writes single' (the second layer's residual), and each thread finishes its four columns:
+// h = relu(rstd' (sum + W1 bo - mean' wsum1) + b1).  (Four 128-thread workgroups per row, as in gemm_slab_reduce_kernel, would
+// each repeat the 128 KB read of Wo^T: 160 MB through the L2 instead of 41 MB.)
+template <int HC>
+__global__ __launch_bounds__(1024) void fc1_fold_reduce_kernel(const float* __restrict__ ws, int SK, int M, int N, int S,
+                                                               const float* __restrict__ single, const float* __restrict__ og,
+                                                               const float* __restrict__ woT, const float* __restrict__ bo,
+                                                               const float* __restrict__ wsum1, const float* __restrict__ w1bo,
+                                                               const float* __restrict__ b1, float* __restrict__ single_out,
+                                                               float* __restrict__ h) {
+    __shared__ float red[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = blockDim.x >> 6;
+    const int m = blockIdx.x, n = 4 * tid;
+    const bool live = n < N, own = tid < S;                                 // N a multiple of 4, S <= blockDim.x
+    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float* wp = ws + (size_t)m * N + (live ? n : 0);
+    const size_t sstride = (size_t)M * N;
+    for (int s0 = 0; s0 < SK; s0 += 4) {
+        float4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const float4*>(wp + (size_t)(s0 + j < SK ? s0 + j : 0) * sstride);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (s0 + j < SK) { sum.x += v[j].x; sum.y += v[j].y; sum.z += v[j].z; sum.w += v[j].w; }
+    }
+    // element tid of single' = single + (og Wo^T + bo): four independent fma chains over the 64 og values, the residual added last
+    const float* ogr = og + (size_t)m * HC;
+    const float* wc = woT + (own ? tid : 0);
+    const float s0 = own ? single[(size_t)m * S + tid] : 0.f, b0 = own ? bo[tid] : 0.f;
+    float p[4] = {0.f, 0.f, 0.f, 0.f};                                      // (chains that started at the residual value would round every product to ITS ulp)
+    float wv[HC];                                                           // all HC loads in flight before the first fma
+#pragma unroll
+    for (int j = 0; j < HC; ++j) wv[j] = wc[(size_t)j * S];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < HC; j += 4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) p[e] = fmaf(ogr[j + e], wv[j + e], p[e]);
+    }
+    const float sp = own ? s0 + (((p[0] + p[1]) + (p[2] + p[3])) + b0) : 0.f;
+    auto block_sum = [&](float x) {                                         // over the workgroup, same value in every thread
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+        __syncthreads();
+        if (lane == 0) red[wave] = x;
+        __syncthreads();
+        float t = 0.f;
+        for (int w = 0; w < nwave; ++w) t += red[w];
+        return t;
+    };
+    const float mu = block_sum(sp) / (float)S;
+    const float d = own ? sp - mu : 0.f;
+    const float rz = 1.0f / sqrtf(block_sum(d * d) / (float)S + 1e-5f);
+    if (own) single_out[(size_t)m * S + tid] = sp;
+    if (live) {
+        const float4 cs = *reinterpret_cast<const float4*>(wsum1 + n), cw = *reinterpret_cast<const float4*>(w1bo + n);
+        const float4 cb = *reinterpret_cast<const float4*>(b1 + n);
+        const float v0 = ((sum.x + cw.x) - mu * cs.x) * rz + cb.x, v1 = ((sum.y + cw.y) - mu * cs.y) * rz + cb.y;
+        const float v2 = ((sum.z + cw.z) - mu * cs.z) * rz + cb.z, v3 = ((sum.w + cw.w) - mu * cs.w) * rz + cb.w;
+        *reinterpret_cast<float4*>(h + (size_t)m * N + n) = make_float4(relu_nan(v0), relu_nan(v1), relu_nan(v2), relu_nan(v3));
+    }
+}
+
 // ---- LayerNorm rows: one wave per row ------------------------------------------------------------
 __global__ __launch_bounds__(256) void ln_rows_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -995,7 +1116,50 @@ bool slab_plan(int M, int N, int K, int arith_full, int* tiles_m, int* tiles_n, 
     *spw = s;
     return true;
 }
+int slab_xmap(int SK, int tiles_n) { return (SK % 8 == 0) ? 1 : ((SK < 8 && 8 % SK == 0 && tiles_n % (8 / SK) == 0) ? 2 : 0); }
+
+// does prd_single_fc1_folded serve this shape?  The first transition layer must take the K-slab path, the 64 og columns must split
+// into 16 per slab group (the extra LDS region of gemm_slab_kernel), and one workgroup of the reduce launch holds a row.
+bool fc1_fold_plan(int M, int S, int HC, int Hd, int arith_full, int* tiles_m, int* tiles_n, int* nslab, int* spw, int* ex) {
+    if (HC != 64 || S > 512 || Hd > 4096 || 128 * prd_ceil_div(Hd, 512) < S) return false;
+    if (!slab_plan(M, Hd, S, arith_full, tiles_m, tiles_n, nslab, spw)) return false;
+    const int SK = prd_ceil_div(*nslab, *spw);
+    if (HC % (16 * SK)) return false;
+    *ex = HC / (16 * SK);
+    return *ex == 1;                // four slab groups of one slab each (S = 512, b N <= 640 rows): the form that is tested and measured
+}
 }  // namespace
+
+extern "C" int prd_single_fc1_folded_ok(int M, int S, int HC, int Hd, int arith) {
+    int a, b, c, d, e;
+    return fc1_fold_plan(M, S, HC, Hd, arith, &a, &b, &c, &d, &e) ? 1 : 0;
+}
+
+extern "C" int prd_single_fc1_folded(const float* single, const float* og, const float* w1cat, const float* woT, const float* bo,
+                                     const float* wsum1, const float* w1bo, const float* b1, float* single_out, float* h,
+                                     int M, int S, int HC, int Hd, float* ws, size_t ws_bytes, int arith, hipStream_t stream) {
+    if (!single || !og || !w1cat || !woT || !bo || !wsum1 || !w1bo || !b1 || !single_out || !h || !ws || M <= 0 || S <= 0 || HC <= 0 || Hd <= 0)
+        return PRD_ERR_ARG;
+    if (arith < 0 || (arith & 0xff) > 1) return PRD_ERR_ARG;
+    int tiles_m, tiles_n, nslab, spw, ex;
+    if (!fc1_fold_plan(M, S, HC, Hd, arith, &tiles_m, &tiles_n, &nslab, &spw, &ex)) return PRD_ERR_UNSUPPORTED;
+    const uintptr_t al = reinterpret_cast<uintptr_t>(single) | reinterpret_cast<uintptr_t>(og) | reinterpret_cast<uintptr_t>(w1cat) |
+                         reinterpret_cast<uintptr_t>(wsum1) | reinterpret_cast<uintptr_t>(w1bo) | reinterpret_cast<uintptr_t>(b1) |
+                         reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(ws);
+    if (al & 15) return PRD_ERR_ALIGN;
+    const int SK = prd_ceil_div(nslab, spw);
+    if ((size_t)SK * M * Hd * sizeof(float) > ws_bytes) return PRD_ERR_WORKSPACE;
+    static std::once_flag once;
+    std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)gemm_slab_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+    const int xmap = slab_xmap(SK, tiles_n);
+    const dim3 grid((unsigned)(tiles_m * tiles_n * SK));
+    const size_t lds = SL_LDS + (size_t)(SL_BM + SL_BN) * 32 * ex * 2;
+    hipLaunchKernelGGL(gemm_slab_kernel<1>, grid, dim3(SL_NW * 64), lds, stream, single, w1cat, ws, M, Hd, S, S, S + HC, tiles_m, tiles_n, nslab,
+                       spw, xmap, H2_WSCALE, og, HC);
+    hipLaunchKernelGGL(fc1_fold_reduce_kernel<64>, dim3((unsigned)M), dim3(128 * prd_ceil_div(Hd, 512)), 0, stream, ws, SK, M, Hd, S, single, og, woT,
+                       bo, wsum1, w1bo, b1, single_out, h);
+    return (int)hipGetLastError();
+}
 
 extern "C" int prd_gemm_slab_ok(int M, int N, int K, int arith) {
     int a, b, c, d;
@@ -1021,10 +1185,10 @@ extern "C" int prd_gemm(const PrdGemm* args, hipStream_t stream) {
             const int SK = prd_ceil_div(nslab, spw);
             if ((size_t)SK * g.M * g.N * sizeof(float) > g.ws_bytes) return PRD_ERR_WORKSPACE;
             static std::once_flag once;
-            std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)gemm_slab_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-            const int xmap = (SK % 8 == 0) ? 1 : ((SK < 8 && 8 % SK == 0 && tiles_n % (8 / SK) == 0) ? 2 : 0);
-            hipLaunchKernelGGL(gemm_slab_kernel, dim3((unsigned)(tiles_m * tiles_n * SK)), dim3(SL_NW * 64), SL_LDS, stream, g.A, g.B, g.ws, g.M, g.N,
-                               g.K, g.lda, g.ldb, tiles_m, tiles_n, nslab, spw, xmap, H2_WSCALE);
+            std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)gemm_slab_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+            const int xmap = slab_xmap(SK, tiles_n);
+            hipLaunchKernelGGL(gemm_slab_kernel<0>, dim3((unsigned)(tiles_m * tiles_n * SK)), dim3(SL_NW * 64), SL_LDS, stream, g.A, g.B, g.ws, g.M, g.N,
+                               g.K, g.lda, g.ldb, tiles_m, tiles_n, nslab, spw, xmap, H2_WSCALE, (const float*)nullptr, 0);
             hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)(g.M * prd_ceil_div(g.N, 512))), dim3(128), 0, stream, g, g.ws, SK);
             return (int)hipGetLastError();
         }

@@ -982,6 +982,17 @@ def project_qkvg(x_normed, packed, HC: int, ln_a: bool = False) -> torch.Tensor:
     return qkvg
 
 
+def single_attn_core(qkvg, mask, bias, H: int, c: int) -> torch.Tensor:
+    """Gated attention output [b,N,H c] BEFORE the output projection from the packed projection ``qkvg`` [b,N,4 H c] (possibly a
+    column block of a wider GEMM output): logits + bias + key mask + softmax + P V + gate in one launch (4 heads x 16 channels)."""
+    b, N = qkvg.shape[:2]
+    o = torch.empty(b, N, H * c, device=qkvg.device, dtype=F32)
+    qp, ldq = row_block(qkvg)
+    check(lib().prd_single_attn_core(dptr(o), qp, ldq, dptr(bias), dptr(mask) if mask is not None else None,
+                                     b, N, H, c, stream()), "prd_single_attn_core")
+    return o
+
+
 def gated_attention_single(x_normed, mask, bias, packed, wo, bo, H: int, c: int, *,
                            key_mask: bool, resid: Optional[torch.Tensor], ln_a: bool = False,
                            qkvg: Optional[torch.Tensor] = None, rscale: Optional[torch.Tensor] = None,
@@ -1005,13 +1016,11 @@ def gated_attention_single(x_normed, mask, bias, packed, wo, bo, H: int, c: int,
         if ln_a and not ln_fusable(S):
             x_normed, ln_a = layer_norm(x_normed.contiguous()), False
         qkvg = project_qkvg(x_normed, packed, HC, ln_a)
-    o = torch.empty(b, N, HC, device=x_normed.device, dtype=F32)
     if c == 16 and HC == 64:
         # heads of width 16 (FoldingBlock.single_attn): fused logits + bias + mask + softmax + PV + gate
-        qp, ldq = row_block(qkvg)
-        check(lib().prd_single_attn_core(dptr(o), qp, ldq, dptr(bias), dptr(mask) if key_mask else None,
-                                         b, N, H, c, stream()), "prd_single_attn_core")
+        o = single_attn_core(qkvg, mask if key_mask else None, bias, H, c)
         return linear(o, wo, bo, resid=resid, rscale=rscale)
+    o = torch.empty(b, N, HC, device=x_normed.device, dtype=F32)
     if SPA_CORE and not logits_fp32 and lib().prd_spa_attn_core_supported(N, c) == 1:
         # logits + softmax + P V in one launch (prd_spa_attn_core: split-16 arithmetic; a training forward keeps the fp32-MFMA logits)
         qp, ldq = row_block(qkvg)
@@ -1073,4 +1082,37 @@ def transition_single(single, w1, b1, w2, b2, *, residual: bool, wsum1=None, wan
     h = linear(single, w1, b1, act=1, ln_a=True, slab=slab1, wsum=wsum1 if slab1 else None)   # LayerNorm (no affine) fused into the first linear
     xhat = torch.empty_like(single) if (want_ln and slab2 and S <= 512) else None
     out = linear(h, w2, b2, resid=single if residual else None, slab=slab2, out_ln=xhat)
+    return (out, xhat) if want_ln else out
+
+
+def fc1_fold_ok(M: int, S: int, HC: int, Hd: int) -> bool:
+    """True when the attention out-projection can ride in the transition's first layer (prd_hip.h: prd_single_fc1_folded_ok) in
+    the current arithmetic; otherwise the out-projection stays a launch of its own."""
+    return lib().prd_single_fc1_folded_ok(M, S, HC, Hd) == 1
+
+
+def pack_fc1_fold(wo, bo, w1):
+    """Weights of ``transition_single_folded`` (prd_hip.h: prd_single_fc1_folded): ([W1 | W1 Wo] with the product formed in
+    float64 and rounded once, Wo^T, row sums of W1, W1 bo)."""
+    w1d, wod = w1.detach().double(), wo.detach().double()
+    w1cat = torch.cat([w1.detach().float(), (w1d @ wod).float()], dim=1).contiguous()
+    return w1cat, wo.detach().t().contiguous(), w1d.sum(1).float().contiguous(), (w1d @ bo.detach().double()).float().contiguous()
+
+
+def transition_single_folded(single, og, pack, bo, b1, w2, b2, *, want_ln: bool = False):
+    """Attention out-projection + transition of the single track with the projection folded into the first layer:
+    s1 = single + og Wo^T + bo;  result = s1 + W2 relu(W1 LN(s1) + b1) + b2, where ``og`` is ``single_attn_core``'s output and
+    ``pack`` = ``pack_fc1_fold(Wo, bo, W1)``.  Call only where ``fc1_fold_ok``.  Returns like ``transition_single``."""
+    b, N, S = single.shape
+    w1cat, woT, wsum1, w1bo = pack
+    Hd, HC = w1cat.shape[0], og.shape[-1]
+    M = b * N
+    s1 = torch.empty_like(single)
+    h = torch.empty(b, N, Hd, device=single.device, dtype=F32)
+    wsb = gemm_workspace(single.device, int(lib().prd_gemm_slab_workspace(M, Hd, S)))
+    check(lib().prd_single_fc1_folded(dptr(single), dptr(og), dptr(w1cat), dptr(woT), dptr(bo), dptr(wsum1), dptr(w1bo), dptr(b1),
+                                      dptr(s1), dptr(h), M, S, HC, Hd, dptr(wsb), wsb.numel() * 4, stream()), "prd_single_fc1_folded")
+    slab2 = slab_ok(M, S, Hd)
+    xhat = torch.empty_like(single) if (want_ln and slab2 and S <= 512) else None
+    out = linear(h, w2, b2, resid=s1, slab=slab2, out_ln=xhat)
     return (out, xhat) if want_ln else out

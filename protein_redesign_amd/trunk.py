@@ -165,6 +165,7 @@ _PAIR_HEAD = os.environ.get("PRD_PAIR_HEAD", "1") != "0"              # 0: pair_
 _MERGE_HEAD = os.environ.get("PRD_MERGE_HEAD", "1") != "0"            # 0: OPM / SPA LayerNorms and projections as four launches
 _HEAD_SLAB = os.environ.get("PRD_HEAD_SLAB", "0") == "1"              # 1: the merged head projection on the K-slab kernel + reduce launch (measured slower: 40.8 vs 31.4 us)
 _MERGE_PROJ = os.environ.get("PRD_MERGE_PROJ", "1") != "0"            # 0: u and the next q|k|v|gate as two launches (A/B measurements)
+_FOLD_OUT_PROJ = os.environ.get("PRD_FOLD_OUT_PROJ", "1") != "0"      # 0: the single attention's output projection as a launch of its own (A/B measurements)
 
 
 class OuterLinear(nn.Module):
@@ -255,6 +256,39 @@ class FoldingBlock(nn.Module):
             return ops.cached_pack(self, "after_transition_tail", ws, build), 1, P
         return None, 0, 0
 
+    def single_track_(self, single, mask, bias, next_block=None, qkvg=None, tail=None, extra=None):
+        """The block's single track (arguments as in ``run_``): attention with the pair bias, transition, and -- with ``extra`` and
+        a next block or a tail layer -- the ONE projection of everything linear in LN(single_out).  Returns (single_out, x, u)
+        with x = LN(single_out) and u = the outer-linear's node term as a column block of that projection, or (single_out, None,
+        None) when the outer-linear has to project for itself."""
+        sa = self.single_attn
+        b, N, S = single.shape
+        fc = self.single_fc
+        HC, Hd = sa.num_heads * sa.head_dim, fc[1].weight.shape[0]
+        if _FOLD_OUT_PROJ and single.is_cuda and sa.head_dim == 16 and ops.fc1_fold_ok(b * N, S, HC, Hd):
+            # the attention's output projection is linear and feeds only the residual: it rides in the transition's first layer
+            # (weights multiplied once per weight set) -- one dependent launch of the chain less
+            if qkvg is None:
+                qkvg = ops.project_qkvg(single, sa.packed(), HC, ln_a=True)
+            og = ops.single_attn_core(qkvg, mask, bias, sa.num_heads, sa.head_dim)
+            wo, bo = sa.out_proj.weight, sa.out_proj.bias
+            pack = ops.cached_pack(self, "fc1_fold", (wo, bo, fc[1].weight), lambda: ops.pack_fc1_fold(wo, bo, fc[1].weight))
+            single, xhat = ops.transition_single_folded(single, og, pack, bo, fc[1].bias, fc[3].weight, fc[3].bias, want_ln=True)
+        else:
+            single = sa.run_single(single, mask, bias, single, ln_a=True, qkvg=qkvg)
+            wsum1 = ops.cached_pack(self, "fc1_rowsum", (fc[1].weight,), lambda: fc[1].weight.double().sum(1).float().contiguous())
+            single, xhat = ops.transition_single(single, fc[1].weight, fc[1].bias, fc[3].weight, fc[3].bias, residual=True, wsum1=wsum1,
+                                                 want_ln=True)
+        packed, act, act_from = self._after_transition_pack(next_block if extra is not None else None, tail if extra is not None else None)
+        if packed is None or not _MERGE_PROJ:
+            return single, None, None
+        # everything that is linear in LN(single) goes through ONE launch: u of the outer-linear, and the next block's
+        # q|k|v|gate or the tail layer (-1 launch of ~8 us per block; these launches are latency-, not work-bound)
+        P = self.outer_linear.pair_dim
+        x, cat = ops.project_many(single, packed, P, act=act, act_from=act_from, xhat=xhat)
+        extra["qkvg" if next_block is not None else "tail"] = cat[..., P:]
+        return single, x, cat[..., :P]
+
     def run_(self, single: torch.Tensor, pair: torch.Tensor, mask: torch.Tensor, ws=None, bias=None, next_block=None, spare_holder=None,
              qkvg=None, tail=None, extra=None):
         """In place on ``pair`` or -- fused attention form, gemm mode 1 -- ending in another buffer: use the RETURNED pair tensor.
@@ -274,20 +308,10 @@ class FoldingBlock(nn.Module):
             ws = torch.empty(ws_floats(b, N, pair.shape[-1], ta.num_heads, ta.head_dim), device=pair.device, dtype=torch.float32)
         if bias is None:
             bias = ops.pair_bias(pair, self.attn_bias[1].weight, self.attn_bias[1].bias)
-        single = sa.run_single(single, mask, bias, single, ln_a=True, qkvg=qkvg)
-        fc = self.single_fc
-        wsum1 = ops.cached_pack(self, "fc1_rowsum", (fc[1].weight,), lambda: fc[1].weight.double().sum(1).float().contiguous())
-        single, xhat = ops.transition_single(single, fc[1].weight, fc[1].bias, fc[3].weight, fc[3].bias, residual=True, wsum1=wsum1,
-                                             want_ln=True)
-        packed, act, act_from = self._after_transition_pack(next_block if extra is not None else None, tail if extra is not None else None)
-        if packed is not None and _MERGE_PROJ:
-            # everything that is linear in LN(single) goes through ONE launch: u of the outer-linear, and the next block's
-            # q|k|v|gate or the tail layer (-1 launch of ~8 us per block; these launches are latency-, not work-bound)
-            P = self.outer_linear.pair_dim
-            x, cat = ops.project_many(single, packed, P, act=act, act_from=act_from, xhat=xhat)
+        single, x, u = self.single_track_(single, mask, bias, next_block=next_block, qkvg=qkvg, tail=tail, extra=extra)
+        if u is not None:
             ol = self.outer_linear.linear
-            ops.outer_linear_pair(pair, x, cat[..., :P], ol.weight, ol.bias, residual=True, out=pair)
-            extra["qkvg" if next_block is not None else "tail"] = cat[..., P:]
+            ops.outer_linear_pair(pair, x, u, ol.weight, ol.bias, residual=True, out=pair)
         else:
             self.outer_linear.run(single, pair, residual=True, out=pair)
         if _TRI_MUL_CHAIN and ops.tri_mul_chain_supported(N, pair.shape[-1]):      # gemm mode 1: out-stage of the first + projection of the second fused
