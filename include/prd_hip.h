@@ -559,6 +559,42 @@ int prd_tri_attn_bwd_core_heads(float* dqkvg, const float* dog, const float* og,
                                 const float* lse, float* x_out, int ending, int b, int N, int P, int H, int c,
                                 float* ws, size_t ws_bytes, int arith, hipStream_t stream);
 
+/* ---- training-mode redesign masks (model.py:442-458; mask_utils.py:16-69 SpatialMaskingModule, 72-108 RandomMaskingModule) ------
+ * All three branches of the reference's training-mode prepare_batch are one operation per sample: among the VALID residues
+ * (residue_mask > 0.5) mark the k with the smallest key.  One launch, one workgroup per sample, no workspace, no atomics; every
+ * element of the outputs is written by one owner, so two launches give the same bits.  (csrc/prd_mask.hip.  Added without a
+ * PRD_VERSION step: existing calls and structures are unchanged, a caller built against 101 runs as before.)
+ * In:  residue_mask [b,N] fp32 0/1;  p [b] fp32, the fraction of every sample;  mode:
+ *   PRD_MASK_RANDOM   key [b,N] fp32 is given (the host's draw; read at the valid residues only; must not be NaN there).
+ *                     k = (int)((double)count * (double)p[s]) per sample, count = the sample's own number of valid residues -- the
+ *                     per-sample convention of the eval branch; equal to mask_utils.py:83-84 at batch size 1
+ *                     (p is the fp32 rounding of the reference's double).
+ *   PRD_MASK_SPATIAL  the launch forms the key itself: the distance of the residue's C-alpha ca_pos[s][i] ([b,N,3], row pitch ld_ca
+ *                     floats >= 3, so that the view residue_atom_pos[:, :, 1] of the [b,N,37,3] tensor can be passed as it lies:
+ *                     ld_ca = 111) to the ligand centroid, with the reference's safe_norm (sqrt(sum of squares + 1e-12),
+ *                     mask_utils.py:12-14, 38-42).  The centroid is sum_i atom_mask atom_pos / sum_i atom_mask (atom_pos [b,N,3],
+ *                     atom_mask [b,N]); for collated batches this equals the reference's UNMASKED sum atom_pos.sum(-2) / atom_mask.sum(-1),
+ *                     because collate_fn leaves atom_pos zero outside the atom block.  ONE k for the whole batch, as the reference has
+ *                     it (mask_utils.py:36, 44-49): k = (int)(p[s] * (float)median) with median = the LOWER median over the samples of
+ *                     their valid-residue counts (what torch.median returns), every workgroup recomputing the b counts.  The
+ *                     product is an fp32 product of the fp32 rounding of the fraction: the reference multiplies a numpy double by a
+ *                     0-dim fp32 tensor, which PyTorch evaluates as tensor * Python scalar in the TENSOR's type (the scalar is rounded
+ *                     to fp32, then one fp32 multiplication; tools/gen_golden_training_masks.py asserts this against the reference
+ *                     for all 1000 fractions).  p[s] is the same value in every sample.
+ *   In both modes k is then CLIPPED to the sample's own count: the reference would go on picking among padded positions whose keys
+ *   are all 1e10 in fp32 (which of them is undefined) -- a documented deviation.  A non-positive or NaN product gives k = 0.
+ * Selection: the rank of a valid residue is the number of valid residues with a smaller key, ties broken by the lower index; it is
+ * selected when its rank is below k (keys tiled through the LDS: any N).
+ * Out: extra [b,N] = residue_mask with the selected positions zeroed;  inv [b,N] = 1 at the selected positions, 0 elsewhere;
+ *      tokens [b,N] int64 (may be NULL), rewritten IN PLACE as tokens * (int)extra + esm_mask with esm_mask = 1 - residue_mask and 32
+ *      at the selected positions (mask_utils.py:52-55, 65-69).
+ * PRD_ERR_ARG: a NULL pointer the mode needs, b, N <= 0, ld_ca < 3, an unknown mode;  PRD_ERR_UNSUPPORTED: b > 256. */
+#define PRD_MASK_RANDOM 0
+#define PRD_MASK_SPATIAL 1
+int prd_mask_lowest_k(float* extra, float* inv, int64_t* tokens, const float* residue_mask, const float* key,
+                      const float* atom_pos, const float* atom_mask, const float* ca_pos, int ld_ca, const float* p,
+                      int mode, int b, int N, hipStream_t stream);
+
 /* bytes of scratch an operator needs: op = "tri_mul" | "tri_attn" */
 size_t prd_workspace_bytes(const char* op, int b, int N, int S, int P);
 

@@ -122,6 +122,7 @@ SIGNATURES = {
     "prd_tri_attn_bwd_heads_supported": [ci] * 5,
     "prd_tri_attn_bwd_heads_workspace_bytes": [ci] * 5,
     "prd_tri_attn_bwd_core_heads": [vp] * 12 + [ci] * 6 + [vp, cz, ci, vp],
+    "prd_mask_lowest_k": [vp] * 8 + [ci, vp, ci, ci, ci, vp],
 }
 
 GEMM_MODES = {"fp32": 0, "split16": 1, "bf16x3": 1}      # "bf16x3": earlier name of the split-operand mode

@@ -27,6 +27,7 @@ from torch import nn
 from . import _lib, ops
 from .constants import ATOM_FEATURE_CARDS, BOND_FEATURE_CARDS, NUM_RESIDUE_CLASSES
 from .schedule import reverse_coefficients, schedule_tables
+from .masking import MaskDraws
 from .synthetic import NoiseSource
 from .trunk import Denoiser, Linear
 
@@ -216,6 +217,7 @@ class ProteinReDiffModel(_Base):
         self.nonfinite_group = None             # process group over which a non-finite verdict is agreed (None: the default group)
         self._side = None                       # ops.SideStream of the device the model runs on (created on first use)
         self._sample_counter = 0
+        self._mask_draw_counter = 0             # prepared batches that drew a training-mode mask (masking.MaskDraws)
 
         self.Denoiser = Denoiser(args)
         S, P = self.single_dim, self.pair_dim
@@ -340,20 +342,21 @@ class ProteinReDiffModel(_Base):
         self.log("val_loss", loss, on_epoch=True, sync_dist=True, batch_size=x.size(0))
         return loss
 
-    def training_step(self, batch, batch_idx, t=None, noise_z=None, noise_seq=None, sources=None, check_finite=True):
+    def training_step(self, batch, batch_idx, t=None, noise_z=None, noise_seq=None, sources=None, check_finite=True, mask_draws=None):
         """model.py:528-549: mean over the batch of diffusion_loss / node count, differentiable with respect to every trainable
         parameter (training.network: HIP forward, per-operator backward, per-block recompute).  ``t`` / the noises / the mask
-        sources may be injected (parity tests); otherwise they are drawn like the reference draws them."""
+        sources may be injected (parity tests); otherwise they are drawn like the reference draws them.  ``sources`` feed the
+        eval-branch mask, ``mask_draws`` (masking.MaskDraws) the training-mode one (``training_mode=True``)."""
         self.check_widths()
         if not self.setup_schedule:
             self.run_setup_schedule()
             self.setup_schedule = True
-        if sources is None:
+        if sources is None and not self.training_mode:
             # the reference draws a fresh torch.randperm at every optimisation step (model.py:460 -> mask_utils.py:87), so the
             # redesign mask of a complex differs from epoch to epoch: key the draw on a running count of training steps
             # (batch_idx restarts every epoch; keyed determinism on batch_idx is for validation / predict only)
             sources = self._sources(batch["atom_mask"].shape[0], None)
-        batch = self.prepare_batch(batch, batch_idx, sources=sources)
+        batch = self.prepare_batch(batch, batch_idx, sources=sources, mask_draws=mask_draws)
         x, mask = batch["x"], batch["residue_and_atom_mask"]
         num_nodes = (mask > 0.5).sum(-1)
         if t is None:
@@ -434,14 +437,65 @@ class ProteinReDiffModel(_Base):
             first = (int(batch_idx) * world + rank) * b
         return [NoiseSource(seed, first + k) for k in range(b)]
 
-    def prepare_batch(self, batch, id=None, sources: Optional[Sequence] = None):
-        """Eval branch (:459-468): ``int(n_res * mask_prob)`` residues per sample leave the known set.  The training-mode
-        branches (:441-458) need ``residue_esm_tokens`` that no published code produces and are out of scope:
-        ``training_step`` therefore runs with ``training_mode=False`` masking, which is also what the reference does when it is
-        trained with its default flags (``--training_mode`` is a store_true option, model.py:133)."""
+    def _mask_draws(self) -> MaskDraws:
+        """Default draws of a training-mode mask: keyed (seed, running count of the batches this object has prepared), the ranks
+        of an initialised process group interleaved -- a fresh mask at every optimisation step, as the reference draws it."""
+        seed = self.sample_seed if self.sample_seed is not None else (torch.initial_seed() & 0x7FFFFFFF)
+        world, rank = 1, 0
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            world, rank = torch.distributed.get_world_size(), torch.distributed.get_rank()
+        index = self._mask_draw_counter * world + rank
+        self._mask_draw_counter += 1
+        return MaskDraws(seed, index)
+
+    def _training_mode_mask(self, batch, mask_draws: Optional[MaskDraws]):
+        """model.py:442-455: one of three masks per prepared batch -- random (rt < 0.3, p = scale * u), spatial (0.3 <= rt < 0.5,
+        p = linspace(0, u, 1000)[idx]) or none -- with u = uniform(0.1, mask_prob).  The draws come from the host
+        (masking.MaskDraws: nothing drawn depends on device data), the selection is ONE launch of prd_mask_lowest_k on the current
+        stream: no device-to-host synchronisation, unlike the eval branch below.  ``residue_esm_tokens`` is optional (the reference
+        masks it and never reads the result): masked in place when present, in the two branches where the reference does."""
+        rm = batch["residue_mask"].contiguous()
+        b, N = rm.shape
+        dev = rm.device
+        d = (mask_draws if mask_draws is not None else self._mask_draws()).draw(b, N, self.mask_prob)
+
+        def upload(t):      # an ordinary asynchronous copy: pinned staging, ordered on the current stream
+            return t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else t.to(dev)
+
+        p = upload(torch.full((b,), d.fraction, dtype=torch.float64).to(torch.float32))
+        tokens = batch.get("residue_esm_tokens") if d.branch != "none" else None     # model.py:455 leaves the tokens alone
+        if tokens is not None and not (tokens.dtype == torch.int64 and tokens.is_contiguous()):
+            raise ValueError("residue_esm_tokens must be a contiguous int64 tensor [b, N] (it is masked in place)")
+        if d.branch == "spatial":
+            return ops.mask_lowest_k(rm, p, atom_pos=batch["atom_pos"].contiguous(), atom_mask=batch["atom_mask"].contiguous(),
+                                     ca_pos=batch["residue_atom_pos"][:, :, 1], tokens=tokens)
+        # "random", and "none" as its p = 0 case (k = 0: extra = residue_mask, inv = 0; the keys are not read)
+        return ops.mask_lowest_k(rm, p, key=upload(d.keys) if d.keys is not None else rm, tokens=tokens)
+
+    def _prepare_batch_training_mode(self, batch, mask_draws: Optional[MaskDraws]):
+        """model.py:426-458, 464-468 with the mask of ``_training_mode_mask``: the same assignments as the eval branch."""
+        am, rm = batch["atom_mask"], batch["residue_mask"]
+        one_hot = F.one_hot(batch["residue_type"], num_classes=NUM_RESIDUE_CLASSES) * 2.0 - 1.0
+        pos = am.unsqueeze(-1) * batch["atom_pos"] + rm.unsqueeze(-1) * batch["residue_atom_pos"][:, :, 1]
+        extra, inv = self._training_mode_mask(batch, mask_draws)
+        batch["residue_one_hot"] = one_hot * extra.unsqueeze(-1)
+        batch["residue_esm"] = batch["residue_esm"] * extra.unsqueeze(-1)
+        batch["residue_type_masked"] = (batch["residue_type"] * extra).long()
+        batch["residue_extra_mask"] = extra
+        batch["residue_inv_extra_mask"] = inv
+        batch["x"] = 0.1 * pos
+        batch["residue_and_atom_mask"] = am + rm
+        return batch
+
+    def prepare_batch(self, batch, id=None, sources: Optional[Sequence] = None, mask_draws: Optional[MaskDraws] = None):
+        """Eval branch (:459-468): ``int(n_res * mask_prob)`` residues per sample leave the known set, chosen on the host from
+        ``sources``.  Training-mode branch (:442-458, ``training_mode=True``, the paper's recipe ``--training_mode``): a
+        stochastic random mask, a spatial mask around the ligand centroid, or none, drawn per prepared batch from ``mask_draws``
+        (default: keyed on a running count) and selected on the device (``_training_mode_mask``).  Deviations from the reference
+        (DESIGN.md §7): the random branch takes int(count * p) residues PER SAMPLE (the reference flattens the batch; equal at
+        batch size 1), and k never exceeds a sample's own residue count.  ``residue_esm_tokens`` is optional."""
         if self.training_mode:
-            raise NotImplementedError("training-mode masking needs residue_esm_tokens, which no published code produces "
-                                      "(SURVEY.md §2/§5); run with training_mode=False")
+            return self._prepare_batch_training_mode(batch, mask_draws)
         am, rm = batch["atom_mask"], batch["residue_mask"]
         dev = am.device
         b = am.shape[0]
@@ -554,14 +608,16 @@ class ProteinReDiffModel(_Base):
 
     # ------------------------------------------------------------------ reverse diffusion (model.py:377-422)
     @torch.inference_mode()
-    def sample(self, batch, sources: Optional[Sequence] = None, batch_idx: Optional[int] = None):
+    def sample(self, batch, sources: Optional[Sequence] = None, batch_idx: Optional[int] = None, mask_draws: Optional[MaskDraws] = None):
         self.check_widths()
         if sources is None:
             sources = self._sources(batch["atom_mask"].shape[0], batch_idx)
+        if self.training_mode and mask_draws is None:
+            mask_draws = self._mask_draws()             # ONE draw per call (memoised): the fp32 repeat below prepares the same mask
         # the keyed generators are consumed by a loop: remember where they stood so that a repeat draws the same noise
         states = [s.g.get_state() if hasattr(s, "g") else None for s in sources]
         with _lib.arithmetic(self.arithmetic):
-            loop = ReverseDiffusion(self, batch, sources)
+            loop = ReverseDiffusion(self, batch, sources, mask_draws)
             loop.run()
             cur = _lib.arith()
             if self.nonfinite_policy == "off" or loop.finite():
@@ -578,7 +634,7 @@ class ProteinReDiffModel(_Base):
             self.arith_fallbacks += 1
             self.arithmetic = "fp32"
             with _lib.arithmetic("fp32"):
-                loop = ReverseDiffusion(self, batch, sources)
+                loop = ReverseDiffusion(self, batch, sources, mask_draws)
                 loop.run()
                 if loop.finite():
                     return loop.result()
@@ -600,7 +656,7 @@ class ReverseDiffusion:
     is replayed for every remaining step: no per-step host work and no ``(t == 0).all()``
     device->host sync (model.py:415)."""
 
-    def __init__(self, model: "ProteinReDiffModel", batch, sources: Optional[Sequence] = None):
+    def __init__(self, model: "ProteinReDiffModel", batch, sources: Optional[Sequence] = None, mask_draws: Optional[MaskDraws] = None):
         m = self.model = model
         if not m.setup_schedule:
             m.run_setup_schedule()
@@ -609,7 +665,7 @@ class ReverseDiffusion:
         b, N = batch["atom_mask"].shape
         if sources is None:
             sources = m._sources(b)
-        self.batch = batch = m.prepare_batch(batch, sources=sources)
+        self.batch = batch = m.prepare_batch(batch, sources=sources, mask_draws=mask_draws)
         self.mask = batch["residue_and_atom_mask"].contiguous()
         self.rm = batch["residue_mask"].contiguous()
         self.T = T = m.num_steps

@@ -830,6 +830,36 @@ def remove_mean(x, mask) -> torch.Tensor:
     return out
 
 
+MASK_RANDOM, MASK_SPATIAL = 0, 1        # prd_hip.h: PRD_MASK_*
+
+
+def mask_lowest_k(residue_mask, p, *, key=None, atom_pos=None, atom_mask=None, ca_pos=None, tokens=None, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The training-mode redesign mask of a batch (prd_hip.h: prd_mask_lowest_k): among the valid residues of every sample the k
+    with the smallest key leave the known set, k computed on the device from the fraction ``p`` [b] -- one launch on the current
+    stream, no host synchronisation.  ``key`` [b,N]: random mode (k = int(count * p) per sample); ``atom_pos`` / ``atom_mask`` /
+    ``ca_pos``: spatial mode (key = distance of the C-alpha to the ligand centroid, ONE k from the lower median of the counts).
+    ``ca_pos`` may be the view ``residue_atom_pos[:, :, 1]``.  ``tokens`` (int64, optional) is masked in place.
+    Returns (extra, inv) = residue_mask without the selected positions, and the selected positions (``out``: written there)."""
+    b, N = residue_mask.shape
+    spatial = key is None
+    if spatial and (atom_pos is None or atom_mask is None or ca_pos is None):
+        raise ValueError("mask_lowest_k needs either key (random mode) or atom_pos, atom_mask and ca_pos (spatial mode)")
+    ld_ca, ca_ptr = 0, None
+    if spatial:
+        if not (ca_pos.stride(2) == 1 and ca_pos.stride(0) == N * ca_pos.stride(1) and ca_pos.stride(1) >= 3):
+            ca_pos = ca_pos.contiguous()
+        if not ca_pos.is_cuda or ca_pos.dtype != F32:
+            dptr(ca_pos.contiguous())                   # raises: CPU tensor / wrong type
+        ld_ca, ca_ptr = ca_pos.stride(1), ca_pos.data_ptr()
+    extra, inv = out if out is not None else (torch.empty_like(residue_mask), torch.empty_like(residue_mask))
+    if extra.shape != residue_mask.shape or inv.shape != residue_mask.shape:
+        raise ValueError("mask_lowest_k: out must be two tensors of residue_mask's shape")
+    check(lib().prd_mask_lowest_k(dptr(extra), dptr(inv), dptr(tokens, torch.int64), dptr(residue_mask), dptr(key), dptr(atom_pos),
+                                  dptr(atom_mask), ca_ptr, ld_ca, dptr(p), MASK_SPATIAL if spatial else MASK_RANDOM, b, N, stream()),
+          "prd_mask_lowest_k")
+    return extra, inv
+
+
 def reverse_update_(z, seq_t, t, noise_pred, seq_pred, noise, mask, coef, num_steps: int):
     """noise: the whole table [T-1, b, N, 3]; the kernel picks row T-1-t and decrements t."""
     b, N, _ = z.shape

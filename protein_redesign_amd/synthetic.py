@@ -98,6 +98,15 @@ def synthetic_sample(na: int, nr: int, esm_dim: int = 1280, seed: int = 0) -> Di
     }
 
 
+def synthetic_esm_tokens(batch: Mapping[str, torch.Tensor], seed: int = 0) -> torch.Tensor:
+    """``residue_esm_tokens`` [b,N] int64 for a collated batch, the key the reference's training-mode ``prepare_batch`` masks
+    (model.py:443): an ESM alphabet index (4..23) at every residue, the padding index 1 elsewhere."""
+    g = torch.Generator().manual_seed(seed)
+    rm = batch["residue_mask"]
+    tok = torch.randint(4, 24, tuple(rm.shape), generator=g)
+    return torch.where(rm.cpu() > 0.5, tok, torch.ones_like(tok))
+
+
 def clone_batch(batch: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
 
