@@ -19,8 +19,8 @@
  *     synchronises, and is therefore capturable into a hipGraph.
  *   - Return value: 0 on success, a positive hipError_t from the launch, or a negative PRD_ERR_*.
  *   - Layouts: single [b,N,S], pair [b,N,N,P] channel-last, masks [b,N] fp32 0/1, weights in
- *     nn.Linear layout [out,in] row-major.  P must be 32 or 64; H*c must be 64 (4 heads x 16);
- *     S, dist_dim and S/4 must be multiples of 8.
+ *     nn.Linear layout [out,in] row-major.  P must be 32 or 64; 1 <= H <= 8 heads of c channels, c a multiple of 4 up
+ *     to 64 (prd_tri_attn_core_heads; the tuned kernels serve 4 heads x 16); S, dist_dim and S/4 must be multiples of 8.
  */
 #ifndef PRD_HIP_H
 #define PRD_HIP_H

@@ -2,8 +2,10 @@
 operator without the built library, or calling it on a CPU tensor, raises -- there is no fallback."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -13,134 +15,94 @@ LIB_PATH = os.environ.get("PRD_LIB", os.path.join(HERE, "libprd_hip.so"))   # PR
 vp, ci, cf, cz, cll = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong
 
 
+# ---- the binding is read from include/prd_hip.h: the header is the only statement of the C ABI ----------------------------------
+_SCALARS = {"int": ci, "float": cf, "size_t": cz, "long long": cll, "hipStream_t": vp}
+Entry = collections.namedtuple("Entry", "argtypes restype inject at")     # inject: "arith" / "tune" / None, at: its parameter index
+
+
 class PrdGemm(C.Structure):
-    _fields_ = [
-        ("A", vp), ("B", vp), ("C", vp),
-        ("M", ci), ("N", ci), ("K", ci),
-        ("lda", ci), ("ldb", ci), ("ldc", ci),
-        ("G1", ci), ("G2", ci),
-        ("sa1", cll), ("sa2", cll), ("sb1", cll), ("sb2", cll), ("sc1", cll), ("sc2", cll),
-        ("b_kn", ci), ("alpha", cf), ("colscale", vp),
-        ("bias", vp), ("act", ci), ("act_from", ci),
-        ("addmat", vp), ("sad1", cll), ("sad2", cll), ("ldadd", ci),
-        ("colmask", vp), ("scm1", cll), ("fill", cf),
-        ("rowmask", vp), ("srm1", cll),
-        ("mulmat", vp), ("smu1", cll), ("smu2", cll), ("ldmul", ci),
-        ("resid", vp), ("sr1", cll), ("sr2", cll), ("ldr", ci),
-        ("tile_hint", ci),
-        ("a_ln", ci),
-        ("ln_out", vp), ("ldlo", ci),
-        ("arith", ci),
-        ("C2", vp), ("ldc2", ci), ("n_split", ci),
-        ("rowmask_cols", ci),
-        ("rscale", vp),
-        ("ws", vp), ("ws_bytes", cz),
-        ("wsum", vp),
-        ("out_ln", vp), ("ldol", ci),
-        ("a_scale", cf),
-        ("mul_pos", ci),
-        ("a_amax", vp),
-    ]
+    pass                                    # _fields_: the header's struct, below
 
 
-# name -> argtypes (every entry point of include/prd_hip.h; tests check the export list against the header)
-SIGNATURES = {
-    "prd_version": [],
-    "prd_tri_attn_variant": [ci, ci, ci],
-    "prd_gemm": [C.POINTER(PrdGemm), vp],
-    "prd_gemm_slab_workspace": [ci, ci, ci],
-    "prd_gemm_slab_ok": [ci, ci, ci, ci],
-    "prd_single_fc1_folded_ok": [ci] * 5,
-    "prd_single_fc1_folded": [vp] * 10 + [ci] * 4 + [vp, cz, ci, vp],
-    "prd_ln_rows": [vp, vp, vp, vp, ci, ci, ci, ci, vp],
-    "prd_softmax_rows": [vp, ci, ci, ci, vp],
-    "prd_static_pair": [vp] * 13 + [ci] * 5 + [vp],
-    "prd_atom_embed": [vp] * 5 + [ci] * 4 + [vp],
-    "prd_single_init": [vp] * 5 + [ci] * 3 + [vp],
-    "prd_time_embed": [vp] * 4 + [ci] * 4 + [vp],
-    "prd_pair_init": [vp] * 7 + [ci] * 5 + [vp],
-    "prd_pair_bias": [vp] * 6 + [ci] * 4 + [vp],
-    "prd_pair_bias2": [vp] * 6 + [ci] + [vp] * 5 + [ci] * 4 + [vp],
-    "prd_opm_pair": [vp] * 6 + [ci] * 6 + [vp],
-    "prd_pair_head_supported": [ci, ci, ci, ci],
-    "prd_pair_head": [vp] * 7 + [ci] + [vp] * 3 + [ci, ci] + [vp] * 5 + [ci] + [vp] * 5 + [ci] * 5 + [vp],
-    "prd_outer_linear": [vp] * 4 + [ci] + [vp] * 2 + [ci] * 5 + [vp, ci, vp],
-    "prd_tri_mul": [vp] * 11 + [ci] * 5 + [vp, cz, vp, ci, vp],
-    "prd_tri_mul_contract": [vp, vp, ci, ci, ci, ci, vp],
-    "prd_tri_mul_contract_scaled": [vp, vp, vp, ci, ci, ci, ci, vp],
-    "prd_tri_mul_chain_supported": [ci, ci, ci],
-    "prd_tri_attn_core_fused_supported": [ci, ci, ci],
-    "prd_tri_attn_core_fused": [vp] * 12 + [ci] * 6 + [vp],
-    "prd_tri_mul_chain": [vp, vp, vp, vp, ci, ci, ci, vp, cz, ci, vp],
-    "prd_tri_mul_out_bwd": [vp] * 15 + [ci] * 4 + [vp],
-    "prd_tri_mul_out_bwd_amax": [vp] * 15 + [ci] * 4 + [vp, vp],
-    "prd_tri_mul_bwd_operands": [vp, vp, ci, ci, ci, vp],
-    "prd_tri_mul_proj_bwd": [vp] * 13 + [ci] * 5 + [vp],
-    "prd_tri_attn_bwd_core": [vp] * 9 + [ci] * 6 + [vp],
-    "prd_tri_attn_bwd_core_v2_supported": [ci, ci],
-    "prd_tri_attn_bwd_core_v2": [vp] * 12 + [ci] * 6 + [vp],
-    "prd_ln_rows_bwd": [vp, vp, vp, vp, cll, ci, vp],
-    "prd_pair_bias_bwd": [vp, vp, vp, vp, vp, vp, ci, cll, ci, ci, vp],
-    "prd_sym_transpose": [vp, vp, ci, ci, ci, vp],
-    "prd_sym_transpose_amax": [vp, vp, ci, ci, ci, vp, vp],
-    "prd_sym_rows": [vp, vp, cf, ci, ci, ci, vp],
-    "prd_outer_linear_bwd_reduce": [vp, vp, ci, vp, vp, vp, cll, ci, ci, vp],
-    "prd_pair_linear_supported": [ci, ci, ci],
-    "prd_pair_linear": [vp, vp, vp, vp, cll, ci, ci, ci, vp, ci, vp, ci, ci, vp],
-    "prd_linear_wgrad_workspace": [cll, ci, ci],
-    "prd_linear_wgrad": [vp, vp, vp, vp, cll, ci, ci, ci, ci, vp, cz, ci, vp],
-    "prd_embed_wgrad_workspace": [cll, ci, ci],
-    "prd_embed_wgrad": [vp, vp, vp, vp, cll, ci, ci, ci, vp, cz, vp],
-    "prd_rbf_rows": [vp, vp, vp, vp, ci, ci, ci, vp],
-    "prd_embed_wgrad_multi": [vp, vp, vp, vp, ci, vp, cll, ci, ci, vp, cz, vp],
-    "prd_tri_attn": [vp] * 10 + [ci] * 7 + [vp, cz, vp, ci, vp],
-    "prd_pair_transition": [vp] * 6 + [ci] * 4 + [vp, ci, vp],
-    "prd_block_tail": [vp] * 11 + [ci] * 4 + [vp, ci, vp],
-    "prd_single_attn_core": [vp, vp, ci, vp, vp] + [ci] * 4 + [vp],
-    "prd_coord_head": [vp] * 7 + [ci] * 4 + [vp],
-    "prd_remove_mean": [vp] * 3 + [ci] * 3 + [vp],
-    "prd_reverse_update": [vp] * 8 + [ci] * 4 + [vp],
-    "prd_step_boundary": [vp] * 16 + [ci] * 7 + [vp, ci, vp, ci] + [vp],
-    "prd_tri_attn_core": [vp] * 8 + [ci] * 7 + [vp],
-    "prd_tri_attn_core_v2": [vp] * 8 + [ci] * 7 + [vp],
-    "prd_tri_attn_core_v2_lse": [vp] * 9 + [ci] * 7 + [vp],
-    "prd_tri_attn_v2_form": [ci, ci, ci],
-    "prd_tri_attn_core_chunked": [vp] * 8 + [ci] * 6 + [vp, cz, vp],
-    "prd_tri_attn_stats_bytes": [ci] * 5,
-    "prd_tri_attn_v2_supported": [ci, ci, ci],
-    "prd_tri_attn_out": [vp] * 5 + [ci] * 4 + [vp, ci, vp],
-    "prd_spa_attn_core_supported": [ci, ci, ci],
-    "prd_spa_attn_core_workspace": [ci, ci, ci, ci],
-    "prd_spa_attn_core": [vp, vp, ci, vp, vp, ci, ci, ci, ci, vp, cz, ci, vp],
-    "prd_workspace_bytes": [C.c_char_p, ci, ci, ci, ci],
-    "prd_tri_attn_pair_supported": [ci, ci, ci],
-    "prd_tri_attn_pair": [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, ci, vp],
-    "prd_tri_attn_heads_supported": [ci] * 5,
-    "prd_tri_attn_heads_workspace_bytes": [ci] * 5,
-    "prd_tri_attn_core_heads": [vp] * 8 + [ci] * 6 + [vp, cz, ci, vp],
-    "prd_tri_attn_core_heads_lse": [vp] * 9 + [ci] * 6 + [vp, cz, ci, vp],
-    "prd_tri_attn_bwd_heads_supported": [ci] * 5,
-    "prd_tri_attn_bwd_heads_workspace_bytes": [ci] * 5,
-    "prd_tri_attn_bwd_core_heads": [vp] * 12 + [ci] * 6 + [vp, cz, ci, vp],
-    "prd_mask_lowest_k": [vp] * 8 + [ci, vp, ci, ci, ci, vp],
-}
+def _strip_comments(text):
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+
+
+def _declarator(decl, where):
+    """(ctypes type, name) of one C parameter or struct member such as ``const float* bias``.  A type outside the map raises."""
+    m = re.fullmatch(r"(.*?)\s*(\w+)", " ".join(decl.split()))
+    ctype = m.group(1).replace(" *", "*") if m else ""
+    if ctype == "const char*":
+        return C.c_char_p, m.group(2)
+    if ctype == "const PrdGemm*":
+        return C.POINTER(PrdGemm), m.group(2)
+    if "*" in ctype:
+        return vp, m.group(2)
+    if ctype not in _SCALARS:
+        raise TypeError(f"include/prd_hip.h, {where}: no ctypes type for {decl.strip()!r}")
+    return _SCALARS[ctype], m.group(2)
+
+
+def parse_struct(text, name):
+    """ctypes ``_fields_`` of ``typedef struct name { ... } name;`` (members such as ``int M, N, K;`` share their type)."""
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), _strip_comments(text), flags=re.S).group(1)
+    fields = []
+    for decl in filter(str.strip, body.split(";")):
+        first, *more = decl.split(",")
+        ctype, member = _declarator(first, "struct " + name)
+        fields += [(member, ctype)] + [(m.strip(), ctype) for m in more]
+    return fields
+
+
+def parse_header(text):
+    """{entry point: Entry} for every ``int`` / ``size_t prd_*(...);`` prototype of the header text.  The injection rule is the
+    header's own: a parameter named ``arith`` or ``tune`` is the last one, or the last before ``stream``; elsewhere it raises."""
+    entries = {}
+    for ret, name, params in re.findall(r"^(int|size_t)\s+(prd_\w+)\s*\(([^)]*)\)\s*;", _strip_comments(text), flags=re.M):
+        decls = [] if params.strip() in ("", "void") else [_declarator(p, name) for p in params.split(",")]
+        names = [n for _, n in decls]
+        hits = [i for i, n in enumerate(names) if n in ("arith", "tune")]
+        if len(hits) > 1 or (hits and hits[0] != len(names) - 1 and not (hits[0] == len(names) - 2 and names[-1] == "stream")):
+            raise ValueError(f"include/prd_hip.h, {name}: `arith` / `tune` must be the last parameter or the last before `stream`")
+        entries[name] = Entry([t for t, _ in decls], _SCALARS[ret], names[hits[0]] if hits else None, hits[0] if hits else None)
+    return entries
+
+
+def parse_tune(text):
+    """({macro without PRD_TUNE_: bits}, shift of PRD_TUNE(), (mask, shift) of PRD_TUNE_TA2_FLAGS()) from the header's #defines."""
+    text = _strip_comments(text)
+    bits = {n: int(a) << int(b) for n, a, b in re.findall(r"#define\s+PRD_TUNE_(\w+)\s+\((\d+)\s*<<\s*(\d+)\)", text)}
+    bits["TA_VARIANT_MASK"] = int(re.search(r"#define\s+PRD_TUNE_TA_VARIANT_MASK\s+(\d+)", text).group(1))
+    shift = int(re.search(r"#define\s+PRD_TUNE\(switches\)\s+\(\(switches\)\s*<<\s*(\d+)\)", text).group(1))
+    flags = re.search(r"#define\s+PRD_TUNE_TA2_FLAGS\(f\)\s+\(PRD_TUNE_TA2_FLAGS_SET\s*\|\s*\(\(\(f\)\s*&\s*(\d+)\)\s*<<\s*(\d+)\)\)", text)
+    return bits, shift, (int(flags.group(1)), int(flags.group(2)))
+
+
+with open(os.path.join(os.path.dirname(HERE), "include", "prd_hip.h")) as _f:
+    _HEADER = _f.read()
+PrdGemm._fields_ = parse_struct(_HEADER, "PrdGemm")
+ENTRIES = parse_header(_HEADER)
+SIGNATURES = {name: e.argtypes for name, e in ENTRIES.items()}          # name -> argtypes
+_TUNE, _TUNE_SHIFT, (_FLAGS_MASK, _FLAGS_SHIFT) = parse_tune(_HEADER)
 
 GEMM_MODES = {"fp32": 0, "split16": 1, "bf16x3": 1}      # "bf16x3": earlier name of the split-operand mode
 DEFAULT_GEMM_MODE = "split16"       # process default of the Python host side (env PRD_GEMM_MODE overrides)
 
-# entry points that take the arithmetic as their last argument before the stream ...
-_ARITH_BEFORE_STREAM = ("prd_coord_head", "prd_pair_head", "prd_pair_init", "prd_opm_pair", "prd_outer_linear", "prd_tri_mul", "prd_tri_mul_contract", "prd_tri_mul_contract_scaled", "prd_tri_mul_proj_bwd",
-                        "prd_tri_attn", "prd_tri_attn_core", "prd_tri_attn_out", "prd_pair_transition", "prd_block_tail", "prd_tri_mul_chain",
-                        "prd_linear_wgrad", "prd_pair_linear", "prd_spa_attn_core", "prd_tri_attn_pair",
-                        "prd_tri_attn_core_heads", "prd_tri_attn_core_heads_lse", "prd_tri_attn_bwd_core_heads", "prd_single_fc1_folded")
-# ... and the queries that take it as their last argument
-_ARITH_LAST = ("prd_tri_attn_variant", "prd_tri_mul_chain_supported", "prd_tri_attn_core_fused_supported", "prd_tri_attn_stats_bytes",
-               "prd_gemm_slab_ok", "prd_pair_head_supported", "prd_pair_linear_supported", "prd_spa_attn_core_supported",
-               "prd_tri_attn_pair_supported", "prd_tri_attn_heads_supported",
-               "prd_tri_attn_bwd_heads_supported", "prd_single_fc1_folded_ok")
-# entry points without an arithmetic that still dispatch between kernel generations: the PRD_TUNE_* switch word alone
-_TUNE_BEFORE_STREAM = ("prd_tri_attn_core_v2", "prd_tri_attn_core_v2_lse")
-_TUNE_LAST = ("prd_tri_attn_v2_supported", "prd_tri_attn_v2_form")
+# A/B environment variable, its default, {value: PRD_TUNE_* switch that value sets}
+_TUNE_ENV = (
+    ("PRD_TA2_V3", 1, {0: "TA2_NO_V3"}),
+    ("PRD_TA2_LONG", 1, {0: "TA2_NO_LONG"}),
+    ("PRD_OL_VARIANT", 0, {1: "OL_GEN2"}),
+    ("PRD_TMS_NW", 8, {12: "TMS_NW12", 16: "TMS_NW16"}),
+    ("PRD_GEMM_KG", 1, {0: "GEMM_NO_KG"}),
+    ("PRD_GEMM_SLAB", 1, {0: "GEMM_NO_SLAB"}),
+    ("PRD_GEMM_BRING", 1, {0: "GEMM_NO_BATCHED_RING"}),
+    ("PRD_GEMM_XCDCOLS", 0, {1: "GEMM_XCD_COLS"}),
+    ("PRD_TA2_TAIL", 1, {0: "TA2_NO_TAIL_SPLIT"}),
+    ("PRD_TA2_XCD8", 1, {0: "TA2_NO_XCD8"}),
+    ("PRD_TA2_GV", 1, {0: "TA2_NO_GV"}),
+    ("PRD_TMP_NW", 12, {16: "TMP_NW16"}),
+)
 
 
 def tune_from_env(env=None) -> int:
@@ -152,36 +114,16 @@ def tune_from_env(env=None) -> int:
         v = env.get(name)
         return default if v is None or v == "" else int(v)
 
-    t = geti("PRD_TA_VARIANT", 0) & 15
-    if geti("PRD_TA2_V3", 1) == 0:
-        t |= 1 << 4
-    if geti("PRD_TA2_LONG", 1) == 0:
-        t |= 1 << 5
+    t = geti("PRD_TA_VARIANT", 0) & _TUNE["TA_VARIANT_MASK"]
+    for name, default, switches in _TUNE_ENV:
+        switch = switches.get(geti(name, default))
+        if switch:
+            t |= _TUNE[switch]
     f = geti("PRD_TA2_FLAGS", -1)
     if f >= 0:
-        t |= (1 << 6) | ((f & 31) << 7)
-    if geti("PRD_OL_VARIANT", 0) == 1:
-        t |= 1 << 12
-    nw = geti("PRD_TMS_NW", 8)
-    t |= (1 << 13) if nw == 12 else (2 << 13) if nw == 16 else 0
-    if geti("PRD_GEMM_KG", 1) == 0:
-        t |= 1 << 15
-    if geti("PRD_GEMM_SLAB", 1) == 0:
-        t |= 1 << 16
-    if geti("PRD_GEMM_BRING", 1) == 0:
-        t |= 1 << 17
-    if geti("PRD_GEMM_XCDCOLS", 0) == 1:
-        t |= 1 << 18
-    if geti("PRD_TA2_TAIL", 1) == 0:
-        t |= 1 << 19
-    if geti("PRD_TA2_XCD8", 1) == 0:
-        t |= 1 << 20
-    if geti("PRD_TA2_GV", 1) == 0:
-        t |= 1 << 21
-    if geti("PRD_TMP_NW", 12) == 16:
-        t |= 1 << 22
-    if geti("PRD_TMS_DEPTH", 2) == 3 and nw == 8:
-        t |= 3 << 13
+        t |= _TUNE["TA2_FLAGS_SET"] | ((f & _FLAGS_MASK) << _FLAGS_SHIFT)
+    if geti("PRD_TMS_DEPTH", 2) == 3 and geti("PRD_TMS_NW", 8) == 8:         # three chunks in flight: the 8-wave contraction only
+        t |= _TUNE["TMS_DEPTH3"]
     return t
 
 
@@ -221,16 +163,18 @@ class _Library:
         fn = self._wrapped.get(name)
         if fn is None:
             raw = getattr(self._cdll, name)
-            if name in _ARITH_BEFORE_STREAM:
+            e = ENTRIES.get(name)
+            kind = (e.inject, e.at == len(e.argtypes) - 2) if e else (None, False)          # (what, before the stream?)
+            if kind == ("arith", True):
                 def fn(*args, _raw=raw):
-                    return _raw(*args[:-1], self._mode | (self._tune << 8), args[-1])
-            elif name in _ARITH_LAST:
+                    return _raw(*args[:-1], self._mode | (self._tune << _TUNE_SHIFT), args[-1])
+            elif kind == ("arith", False):
                 def fn(*args, _raw=raw):
-                    return _raw(*args, self._mode | (self._tune << 8))
-            elif name in _TUNE_BEFORE_STREAM:
+                    return _raw(*args, self._mode | (self._tune << _TUNE_SHIFT))
+            elif kind == ("tune", True):
                 def fn(*args, _raw=raw):
                     return _raw(*args[:-1], self._tune, args[-1])
-            elif name in _TUNE_LAST:
+            elif kind == ("tune", False):
                 def fn(*args, _raw=raw):
                     return _raw(*args, self._tune)
             else:
@@ -251,12 +195,9 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -m protein_redesign_amd.build` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the HIP hot path.")
         cdll = C.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, e in ENTRIES.items():
             fn = getattr(cdll, name)
-            fn.argtypes = argtypes
-            fn.restype = cz if name in ("prd_workspace_bytes", "prd_linear_wgrad_workspace", "prd_embed_wgrad_workspace", "prd_tri_attn_stats_bytes",
-                                        "prd_gemm_slab_workspace", "prd_spa_attn_core_workspace",
-                                        "prd_tri_attn_heads_workspace_bytes", "prd_tri_attn_bwd_heads_workspace_bytes") else ci
+            fn.argtypes, fn.restype = e.argtypes, e.restype
         if cdll.prd_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} reports PRD_VERSION {cdll.prd_version()}, this binding was written against {ABI_VERSION} "
                                "(include/prd_hip.h lists what changed): rebuild with `python -m protein_redesign_amd.build`")

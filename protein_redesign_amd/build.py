@@ -1,4 +1,6 @@
 """Build libprd_hip.so in-tree with hipcc for gfx950 (no CMake / JIT cache: the .so travels with the repo)."""
+import collections
+import json
 import os
 import subprocess
 import sys
@@ -11,6 +13,20 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # per-source extras.  prd_tri2: the softmax arithmetic is placed by hand between the MFMAs of the key loop; the SLP vectoriser
 # would pack its scalar fp32 adds into v_pk_add_f32 (slower beside MFMAs on gfx950) and move them out of their slots
 EXTRA_FLAGS = {"prd_tri2.hip": ["-fno-slp-vectorize"]}
+PRD_HIP_H = os.path.join(os.path.dirname(HERE), "include", "prd_hip.h")
+HEADERS = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_tri2_v3_body.inc"), PRD_HIP_H]      # every object depends on these
+
+# A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
+# that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
+Variant = collections.namedtuple("Variant", "cflags ldflags objdir lib macro")
+_ASAN = ["-fsanitize=address", "-fno-gpu-sanitize"]         # host code only: GPU ASan is not available on this pool
+VARIANTS = {
+    # (-Rpass-analysis: the per-kernel resource remarks of THIS compilation are kept in csrc/resource_usage.json)
+    "shipped": Variant(["-Rpass-analysis=kernel-resource-usage", "-fno-caret-diagnostics"], [], CSRC, LIB, None),
+    "ab": Variant(["-DPRD_AB"], [], os.path.join(CSRC, "ab"), os.path.join(HERE, "libprd_hip_ab.so"), "PRD_AB"),
+    "timing": Variant(["-DPRD_TIMING"], [], os.path.join(CSRC, "timing"), os.path.join(HERE, "libprd_hip_timing.so"), None),
+    "asan": Variant(["-g"] + _ASAN + ["-fno-omit-frame-pointer"], _ASAN, os.path.join(CSRC, "asan"), os.path.join(HERE, "libprd_hip_asan.so"), None),
+}
 
 
 RESOURCE_JSON = os.path.join(CSRC, "resource_usage.json")     # per kernel: VGPRs, AGPRs, SGPRs, scratch bytes / lane, occupancy, LDS
@@ -55,41 +71,49 @@ def parse_resource_usage(stderr_text):
     return dict(zip(_demangle(mangled), rows))
 
 
-def resource_usage(verbose: bool = False):
-    """Register / scratch / occupancy figures of every kernel of the library, as the compiler reports them for the committed flags
-    (hipcc cross-compiles without a GPU).  ``build()`` writes them next to the objects; a source whose figures are missing is
-    analysed here (device code only, nothing linked).  tests/test_build_resources.py holds the default-dispatch kernels of the
-    sampling step to ScratchSize == 0."""
-    import json
+def _hipcc():
+    return os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def _stamp(src):
+    return max(os.path.getmtime(d) for d in [os.path.join(CSRC, src)] + HEADERS)
+
+
+def _resources(update=None):
+    """csrc/resource_usage.json as a dict ({} when missing or unreadable); ``update``, if any, is merged in and stored first."""
     have = {}
-    if os.path.exists(RESOURCE_JSON):
-        try:
-            with open(RESOURCE_JSON) as f:
-                have = json.load(f)
-        except (OSError, ValueError):
-            have = {}
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_tri2_v3_body.inc"), os.path.join(os.path.dirname(HERE), "include", "prd_hip.h")]
-    changed = False
-    for src in SOURCES:
-        spath = os.path.join(CSRC, src)
-        stamp = max(os.path.getmtime(d) for d in [spath] + headers)
-        if src in have and have[src].get("stamp") == stamp:
-            continue
-        cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", spath, "-o", os.devnull]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"resource analysis of {src} failed:\n{r.stderr[-2000:]}")
-        have[src] = {"stamp": stamp, "kernels": parse_resource_usage(r.stderr)}
-        changed = True
-    if changed:
+    try:
+        with open(RESOURCE_JSON) as f:
+            have = json.load(f)
+    except (OSError, ValueError):
+        pass
+    if update:
+        have.update(update)
         try:
             with open(RESOURCE_JSON, "w") as f:
                 json.dump(have, f, indent=1, sort_keys=True)
         except OSError:
             pass
+    return have
+
+
+def resource_usage(verbose: bool = False):
+    """Register / scratch / occupancy figures of every kernel of the library, as the compiler reports them for the committed flags
+    (hipcc cross-compiles without a GPU).  ``build()`` writes them next to the objects; a source whose figures are missing is
+    analysed here (device code only, nothing linked).  tests/test_build_resources.py holds the default-dispatch kernels of the
+    sampling step to ScratchSize == 0."""
+    have, new = _resources(), {}
+    for src in SOURCES:
+        if src in have and have[src].get("stamp") == _stamp(src):
+            continue
+        cmd = [_hipcc()] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", os.path.join(CSRC, src), "-o", os.devnull]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"resource analysis of {src} failed:\n{r.stderr[-2000:]}")
+        new[src] = {"stamp": _stamp(src), "kernels": parse_resource_usage(r.stderr)}
+    have = _resources(new)
     return {k: v for src in SOURCES for k, v in have[src]["kernels"].items()}
 
 
@@ -100,79 +124,62 @@ def _stale(out, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _record_resources(src, stderr_text, deps):
-    import json
-    have = {}
-    if os.path.exists(RESOURCE_JSON):
-        try:
-            with open(RESOURCE_JSON) as f:
-                have = json.load(f)
-        except (OSError, ValueError):
-            have = {}
-    kernels = parse_resource_usage(stderr_text)
-    if not kernels:
-        return
-    have[src] = {"stamp": max(os.path.getmtime(d) for d in deps), "kernels": kernels}
-    try:
-        with open(RESOURCE_JSON, "w") as f:
-            json.dump(have, f, indent=1, sort_keys=True)
-    except OSError:
-        pass
+def _run(cmd, verbose):
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
 
 
-def build(force: bool = False, verbose: bool = True) -> str:
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_tri2_v3_body.inc"), os.path.join(os.path.dirname(HERE), "include", "prd_hip.h")]
+def _build(name: str, force: bool = False, verbose: bool = True) -> str:
+    """Compile SOURCES into the variant's object directory and link its library; only what is stale, unless ``force``."""
+    v = VARIANTS[name]
+    os.makedirs(v.objdir, exist_ok=True)
     objs = []
     for src in SOURCES:
         spath = os.path.join(CSRC, src)
         if not os.path.exists(spath):
             raise FileNotFoundError(f"HIP source listed in build.py is missing: {spath}")
-        obj = os.path.join(CSRC, src.replace(".hip", ".o"))
-        if force or _stale(obj, [spath] + headers):
-            # (-Rpass-analysis: the per-kernel resource remarks of THIS compilation are kept in csrc/resource_usage.json)
-            cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-Rpass-analysis=kernel-resource-usage", "-fno-caret-diagnostics", "-c", spath, "-o", obj]
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
-            if r.returncode != 0:
-                sys.stderr.write(r.stderr)
-                raise subprocess.CalledProcessError(r.returncode, cmd)
-            for line in r.stderr.splitlines():                      # warnings stay visible, the remarks do not
-                if "remark:" not in line and line.strip():
-                    sys.stderr.write(line + "\n")
-            _record_resources(src, r.stderr, [spath] + headers)
+        if v.macro:
+            with open(spath) as f:
+                if v.macro not in f.read():
+                    objs.append(os.path.join(CSRC, src.replace(".hip", ".o")))
+                    continue
+        obj = os.path.join(v.objdir, src.replace(".hip", ".o"))
         objs.append(obj)
-    if force or _stale(LIB, objs):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+        if not (force or _stale(obj, [spath] + HEADERS)):
+            continue
+        cmd = [_hipcc()] + FLAGS + EXTRA_FLAGS.get(src, []) + v.cflags + ["-c", spath, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-    return LIB
+        r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            sys.stderr.write(r.stderr)
+            raise subprocess.CalledProcessError(r.returncode, cmd)
+        for line in r.stderr.splitlines():                      # warnings stay visible, the remarks do not
+            if "remark:" not in line and line.strip():
+                sys.stderr.write(line + "\n")
+        kernels = parse_resource_usage(r.stderr)                  # only the shipped variant asks for the remarks
+        if kernels:
+            _resources({src: {"stamp": _stamp(src), "kernels": kernels}})
+    if force or _stale(v.lib, objs):
+        _run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + v.ldflags + ["-o", v.lib] + objs, verbose)
+    return v.lib
+
+
+def build(force: bool = False, verbose: bool = True) -> str:
+    return _build("shipped", force, verbose)
 
 
 def build_asan(verbose: bool = True) -> str:
     """Host-side AddressSanitizer build: libprd_hip_asan.so with the HOST code of every source instrumented
-    (-fsanitize=address; device code is compiled as usual: -fno-gpu-sanitize, GPU ASan is not available on this pool) and the
-    argument-validation driver tests/native/host_abi_check.c linked against it.  Runs on a machine without a GPU: every call of
+    (-fsanitize=address; device code is compiled as usual: -fno-gpu-sanitize) and the argument-validation driver
+    tests/native/host_abi_check.c linked against it.  Runs on a machine without a GPU: every call of
     the driver is rejected by the argument checks before any HIP API is used.  Returns the path of the driver binary."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out_dir = os.path.join(HERE, "csrc", "asan")
-    os.makedirs(out_dir, exist_ok=True)
-    lib = os.path.join(HERE, "libprd_hip_asan.so")
-    objs = []
-    for src in SOURCES:
-        obj = os.path.join(out_dir, src.replace(".hip", ".o"))
-        cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-g", "-fsanitize=address", "-fno-gpu-sanitize", "-fno-omit-frame-pointer", "-c", os.path.join(CSRC, src), "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-        objs.append(obj)
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address", "-fno-gpu-sanitize", "-o", lib] + objs)
-    exe = os.path.join(out_dir, "host_abi_check")
+    lib = _build("asan", verbose=verbose)
+    exe = os.path.join(VARIANTS["asan"].objdir, "host_abi_check")
     driver = os.path.join(os.path.dirname(HERE), "tests", "native", "host_abi_check.c")
-    subprocess.check_call([hipcc, "-x", "c", driver, "-x", "none", "-g", "-fsanitize=address", "-fno-gpu-sanitize", "-o", exe, lib,
-                           "-Wl,-rpath," + HERE])
+    if _stale(exe, [driver, lib, PRD_HIP_H]):
+        _run([_hipcc(), "-x", "c", driver, "-x", "none", "-g"] + _ASAN + ["-o", exe, lib, "-Wl,-rpath," + HERE], verbose)
     return exe
 
 
@@ -181,49 +188,14 @@ def build_ab(verbose: bool = True) -> str:
     first-generation split-16 attention cores of csrc/prd_tri.hip, in their three wave-count forms, and the fused form built on
     them).  For A/B measurements (PRD_LIB=<path> PRD_TA_VARIANT=10 ...) and for the parity tests of those kernels, which
     tests/test_ab_build.py runs against this library in a child process."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out_dir = os.path.join(HERE, "csrc", "ab")
-    os.makedirs(out_dir, exist_ok=True)
-    lib = os.path.join(HERE, "libprd_hip_ab.so")
-    headers = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_tri2_v3_body.inc"), os.path.join(os.path.dirname(HERE), "include", "prd_hip.h")]
     build(verbose=verbose)                                   # sources that never test PRD_AB share the shipped objects
-    objs = []
-    for src in SOURCES:
-        spath = os.path.join(CSRC, src)
-        with open(spath) as f:
-            differs = "PRD_AB" in f.read()
-        if not differs:
-            objs.append(os.path.join(CSRC, src.replace(".hip", ".o")))
-            continue
-        obj = os.path.join(out_dir, src.replace(".hip", ".o"))
-        if _stale(obj, [spath] + headers):
-            cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-DPRD_AB", "-c", spath, "-o", obj]
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            subprocess.check_call(cmd)
-        objs.append(obj)
-    if _stale(lib, objs):
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
-    return lib
+    return _build("ab", verbose=verbose)
 
 
 def build_timing(verbose: bool = True) -> str:
     """Diagnostic build with in-kernel cycle stamps (-DPRD_TIMING: tools/ta_timing.py, tools/phase_timing.py read them through
     prd_debug_read); load it with PRD_LIB=<path>.  Never the shipped library: the stamps cost ~10 % of a wave's cycles."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out_dir = os.path.join(HERE, "csrc", "timing")
-    os.makedirs(out_dir, exist_ok=True)
-    lib = os.path.join(HERE, "libprd_hip_timing.so")
-    objs = []
-    for src in SOURCES:
-        obj = os.path.join(out_dir, src.replace(".hip", ".o"))
-        cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-DPRD_TIMING", "-c", os.path.join(CSRC, src), "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-        objs.append(obj)
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
-    return lib
+    return _build("timing", verbose=verbose)
 
 
 if __name__ == "__main__":

@@ -228,6 +228,7 @@ int main(void) {
         for (int k = 0; k < 3; ++k) pthread_join(th[k], 0);
         EXPECT(t0.bad + t1.bad + t2.bad, 0);
     }
+    printf("sizeof(PrdGemm) = %zu\n", sizeof(PrdGemm));    /* tests/test_binding_cpu.py: the ctypes structure must have this size */
     printf(failures ? "host ABI check: %d failure(s)\n" : "host ABI check: OK\n", failures);
     return failures ? 1 : 0;
 }
