@@ -564,7 +564,7 @@ int prd_tri_attn_bwd_core_heads(float* dqkvg, const float* dog, const float* og,
  * (residue_mask > 0.5) mark the k with the smallest key.  One launch, one workgroup per sample, no workspace, no atomics; every
  * element of the outputs is written by one owner, so two launches give the same bits.  (csrc/prd_mask.hip.  Added without a
  * PRD_VERSION step: existing calls and structures are unchanged, a caller built against 101 runs as before.)
- * In:  residue_mask [b,N] fp32 0/1;  p [b] fp32, the fraction of every sample;  mode:
+ * In:  residue_mask [b,N] fp32 0/1;  p [b] fp32, the fraction of every sample (PRD_MASK_LIGAND_WITHIN: its radius);  mode:
  *   PRD_MASK_RANDOM   key [b,N] fp32 is given (the host's draw; read at the valid residues only; must not be NaN there).
  *                     k = (int)((double)count * (double)p[s]) per sample, count = the sample's own number of valid residues -- the
  *                     per-sample convention of the eval branch; equal to mask_utils.py:83-84 at batch size 1
@@ -581,16 +581,34 @@ int prd_tri_attn_bwd_core_heads(float* dqkvg, const float* dog, const float* og,
  *                     0-dim fp32 tensor, which PyTorch evaluates as tensor * Python scalar in the TENSOR's type (the scalar is rounded
  *                     to fp32, then one fp32 multiplication; tools/gen_golden_training_masks.py asserts this against the reference
  *                     for all 1000 fractions).  p[s] is the same value in every sample.
- *   In both modes k is then CLIPPED to the sample's own count: the reference would go on picking among padded positions whose keys
+ *   PRD_MASK_LIGAND_NEAREST  (inference: "redesign the fraction p of the residues closest to the ligand"; beyond the reference, whose
+ *                     eval branch only draws a random subset.)  key is ignored.  The launch forms the LIGAND KEY of every valid
+ *                     residue i: the minimum over the sample's ligand atoms a (atom_mask[s][a] > 0.5; atom_pos, atom_mask and ca_pos /
+ *                     ld_ca as in the spatial mode) of safe_norm(ca_pos[s][i] - atom_pos[s][a]) =
+ *                     sqrtf(((dx*dx + dy*dy) + dz*dz) + 1e-12f), every product and sum rounded on its own.  k = (int)((double)count *
+ *                     (double)p[s]) per sample, clipped to the count (the random mode's convention); the k valid residues with the
+ *                     smallest ligand key are selected, ranked as below.
+ *   PRD_MASK_LIGAND_WITHIN   (inference: "redesign the pocket".)  p[s] is a RADIUS in Angstrom: every valid residue whose ligand key
+ *                     (as above) is <= p[s] is selected; no ranking, no k.  A NaN or negative radius selects nothing.
+ *   Both ligand modes: a sample without ligand atoms selects nothing; a sample without valid residues gets extra = residue_mask,
+ *   inv = 0.  A key costs O(atoms), so it is computed once per residue (the atoms staged through the LDS in tiles) and kept: in the
+ *   LDS for N <= 2048, in the sample's row of `extra` for longer rows.  NEAREST then ranks first, every thread keeping its verdicts
+ *   as one bit per owned position in a 64-bit register, and writes the outputs after a workgroup barrier, so that no key is
+ *   overwritten before its last reader: N <= 16384 (64 bits x 256 threads), PRD_ERR_UNSUPPORTED beyond.  WITHIN compares every key
+ *   in place: any N.  No limit on b in either.
+ *   In the random and the spatial mode k is then CLIPPED to the sample's own count: the reference would go on picking among padded positions whose keys
  *   are all 1e10 in fp32 (which of them is undefined) -- a documented deviation.  A non-positive or NaN product gives k = 0.
  * Selection: the rank of a valid residue is the number of valid residues with a smaller key, ties broken by the lower index; it is
  * selected when its rank is below k (keys tiled through the LDS: any N).
  * Out: extra [b,N] = residue_mask with the selected positions zeroed;  inv [b,N] = 1 at the selected positions, 0 elsewhere;
  *      tokens [b,N] int64 (may be NULL), rewritten IN PLACE as tokens * (int)extra + esm_mask with esm_mask = 1 - residue_mask and 32
  *      at the selected positions (mask_utils.py:52-55, 65-69).
- * PRD_ERR_ARG: a NULL pointer the mode needs, b, N <= 0, ld_ca < 3, an unknown mode;  PRD_ERR_UNSUPPORTED: b > 256. */
+ * PRD_ERR_ARG: a NULL pointer the mode needs, b, N <= 0, ld_ca < 3, an unknown mode;  PRD_ERR_UNSUPPORTED: b > 256 (random and
+ * spatial mode), N > 16384 (PRD_MASK_LIGAND_NEAREST).  Nothing is launched on an error. */
 #define PRD_MASK_RANDOM 0
 #define PRD_MASK_SPATIAL 1
+#define PRD_MASK_LIGAND_NEAREST 2
+#define PRD_MASK_LIGAND_WITHIN 3
 int prd_mask_lowest_k(float* extra, float* inv, int64_t* tokens, const float* residue_mask, const float* key,
                       const float* atom_pos, const float* atom_mask, const float* ca_pos, int ld_ca, const float* p,
                       int mode, int b, int N, hipStream_t stream);

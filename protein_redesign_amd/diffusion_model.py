@@ -27,7 +27,7 @@ from torch import nn
 from . import _lib, ops
 from .constants import ATOM_FEATURE_CARDS, BOND_FEATURE_CARDS, NUM_RESIDUE_CLASSES
 from .schedule import reverse_coefficients, schedule_tables
-from .masking import MaskDraws
+from .masking import MaskDraws, Redesign
 from .synthetic import NoiseSource
 from .trunk import Denoiser, Linear
 
@@ -218,6 +218,7 @@ class ProteinReDiffModel(_Base):
         self._side = None                       # ops.SideStream of the device the model runs on (created on first use)
         self._sample_counter = 0
         self._mask_draw_counter = 0             # prepared batches that drew a training-mode mask (masking.MaskDraws)
+        self.redesign: Optional[Redesign] = None    # design region of inference where no ``redesign=`` keyword is given (masking.Redesign)
 
         self.Denoiser = Denoiser(args)
         S, P = self.single_dim, self.pair_dim
@@ -416,9 +417,9 @@ class ProteinReDiffModel(_Base):
                                   + (": outside the operand range of the split arithmetic (include/prd_hip.h); set model.arithmetic = 'fp32' "
                                      "or nonfinite_policy = 'fp32'" if cur == 1 else ": the weights / inputs themselves produce inf or NaN"))
 
-    def predict_step(self, batch, batch_idx):
+    def predict_step(self, batch, batch_idx, redesign: Optional[Redesign] = None):
         with self.ema.average_parameters(self.parameters()):
-            return self.sample(batch, batch_idx=batch_idx)
+            return self.sample(batch, batch_idx=batch_idx, redesign=redesign)
 
     # ------------------------------------------------------------------ batch preparation (model.py:424-468)
     def _sources(self, b: int, batch_idx: Optional[int] = None) -> List[NoiseSource]:
@@ -487,32 +488,67 @@ class ProteinReDiffModel(_Base):
         batch["residue_and_atom_mask"] = am + rm
         return batch
 
-    def prepare_batch(self, batch, id=None, sources: Optional[Sequence] = None, mask_draws: Optional[MaskDraws] = None):
+    def _redesign_spec(self, redesign: Optional[Redesign]) -> Optional[Redesign]:
+        """The design region in force: the keyword, else ``self.redesign``, else None (the reference's random subset).  The
+        training recipe draws its own masks: a spec under ``training_mode=True`` is an error."""
+        spec = redesign if redesign is not None else self.redesign
+        if spec is None:
+            return None
+        if not isinstance(spec, Redesign):
+            raise TypeError(f"redesign must be a masking.Redesign, got {type(spec).__name__}")
+        if self.training_mode:
+            raise ValueError("a redesign region applies to inference; under training_mode=True the training recipe draws its own masks")
+        return spec
+
+    def _redesign_mask(self, batch, spec: Redesign):
+        """(extra, inv) of a design region, built on the device without a host synchronisation.  ``within`` / ``nearest``: ONE
+        launch of prd_mask_lowest_k (PRD_MASK_LIGAND_WITHIN / _NEAREST) keyed on the distance of every C-alpha to the nearest
+        ligand atom; ``positions``: two elementwise products with ``residue_mask``."""
+        rm = batch["residue_mask"].contiguous()
+        b, N = rm.shape
+        if spec.kind == "positions":
+            m = spec.mask
+            if m.shape[-1] != N or (m.dim() == 2 and m.shape[0] not in (1, b)):
+                raise ValueError(f"Redesign.positions: a mask of shape {tuple(m.shape)} does not fit a batch of shape {(b, N)}")
+            spec = spec.to(rm.device)
+            return rm * spec.keep, rm * spec.mask
+        p = torch.full((b,), spec.value, dtype=torch.float32, device=rm.device)
+        return ops.mask_lowest_k(rm, p, atom_pos=batch["atom_pos"].contiguous(), atom_mask=batch["atom_mask"].contiguous(),
+                                 ca_pos=batch["residue_atom_pos"][:, :, 1], ligand=spec.kind)
+
+    def prepare_batch(self, batch, id=None, sources: Optional[Sequence] = None, mask_draws: Optional[MaskDraws] = None,
+                      redesign: Optional[Redesign] = None):
         """Eval branch (:459-468): ``int(n_res * mask_prob)`` residues per sample leave the known set, chosen on the host from
-        ``sources``.  Training-mode branch (:442-458, ``training_mode=True``, the paper's recipe ``--training_mode``): a
+        ``sources`` -- or, with a design region (``redesign=`` / ``self.redesign``, masking.Redesign: the pocket within a radius of
+        the ligand, the fraction of residues nearest to it, or explicit positions), the residues of that region, selected on the
+        device (``_redesign_mask``; ``sources`` and ``mask_prob`` are then not used for the mask).  Training-mode branch (:442-458, ``training_mode=True``, the paper's recipe ``--training_mode``): a
         stochastic random mask, a spatial mask around the ligand centroid, or none, drawn per prepared batch from ``mask_draws``
         (default: keyed on a running count) and selected on the device (``_training_mode_mask``).  Deviations from the reference
         (DESIGN.md §7): the random branch takes int(count * p) residues PER SAMPLE (the reference flattens the batch; equal at
         batch size 1), and k never exceeds a sample's own residue count.  ``residue_esm_tokens`` is optional."""
+        spec = self._redesign_spec(redesign)
         if self.training_mode:
             return self._prepare_batch_training_mode(batch, mask_draws)
         am, rm = batch["atom_mask"], batch["residue_mask"]
         dev = am.device
         b = am.shape[0]
-        if sources is None:
+        if spec is None and sources is None:
             sources = self._sources(b, id if isinstance(id, int) else None)
         one_hot = F.one_hot(batch["residue_type"], num_classes=NUM_RESIDUE_CLASSES) * 2.0 - 1.0
         pos = am.unsqueeze(-1) * batch["atom_pos"] + rm.unsqueeze(-1) * batch["residue_atom_pos"][:, :, 1]
-        rm_cpu = rm.detach().cpu()
-        extra = rm_cpu.clone()
-        inv = torch.zeros_like(rm_cpu)
-        for k in range(b):        # RandomMaskingModule(stochastic=False), per sample (mask_utils.py:77-102)
-            ones = torch.where(rm_cpu[k] == 1)[0]
-            n = int(ones.numel() * self.mask_prob)
-            sel = ones[sources[k].randperm(ones.numel())[:n]]
-            extra[k, sel] = 0
-            inv[k, sel] = 1
-        extra, inv = extra.to(dev), inv.to(dev)
+        if spec is not None:
+            extra, inv = self._redesign_mask(batch, spec)
+        else:
+            rm_cpu = rm.detach().cpu()
+            extra = rm_cpu.clone()
+            inv = torch.zeros_like(rm_cpu)
+            for k in range(b):        # RandomMaskingModule(stochastic=False), per sample (mask_utils.py:77-102)
+                ones = torch.where(rm_cpu[k] == 1)[0]
+                n = int(ones.numel() * self.mask_prob)
+                sel = ones[sources[k].randperm(ones.numel())[:n]]
+                extra[k, sel] = 0
+                inv[k, sel] = 1
+            extra, inv = extra.to(dev), inv.to(dev)
         batch["residue_one_hot"] = one_hot * extra.unsqueeze(-1)
         batch["residue_esm"] = batch["residue_esm"] * extra.unsqueeze(-1)
         batch["residue_type_masked"] = (batch["residue_type"] * extra).long()
@@ -608,8 +644,10 @@ class ProteinReDiffModel(_Base):
 
     # ------------------------------------------------------------------ reverse diffusion (model.py:377-422)
     @torch.inference_mode()
-    def sample(self, batch, sources: Optional[Sequence] = None, batch_idx: Optional[int] = None, mask_draws: Optional[MaskDraws] = None):
+    def sample(self, batch, sources: Optional[Sequence] = None, batch_idx: Optional[int] = None, mask_draws: Optional[MaskDraws] = None,
+               redesign: Optional[Redesign] = None):
         self.check_widths()
+        redesign = self._redesign_spec(redesign)        # deterministic: the fp32 repeat below prepares the same mask, nothing memoised
         if sources is None:
             sources = self._sources(batch["atom_mask"].shape[0], batch_idx)
         if self.training_mode and mask_draws is None:
@@ -617,7 +655,7 @@ class ProteinReDiffModel(_Base):
         # the keyed generators are consumed by a loop: remember where they stood so that a repeat draws the same noise
         states = [s.g.get_state() if hasattr(s, "g") else None for s in sources]
         with _lib.arithmetic(self.arithmetic):
-            loop = ReverseDiffusion(self, batch, sources, mask_draws)
+            loop = ReverseDiffusion(self, batch, sources, mask_draws, redesign)
             loop.run()
             cur = _lib.arith()
             if self.nonfinite_policy == "off" or loop.finite():
@@ -634,7 +672,7 @@ class ProteinReDiffModel(_Base):
             self.arith_fallbacks += 1
             self.arithmetic = "fp32"
             with _lib.arithmetic("fp32"):
-                loop = ReverseDiffusion(self, batch, sources, mask_draws)
+                loop = ReverseDiffusion(self, batch, sources, mask_draws, redesign)
                 loop.run()
                 if loop.finite():
                     return loop.result()
@@ -656,7 +694,8 @@ class ReverseDiffusion:
     is replayed for every remaining step: no per-step host work and no ``(t == 0).all()``
     device->host sync (model.py:415)."""
 
-    def __init__(self, model: "ProteinReDiffModel", batch, sources: Optional[Sequence] = None, mask_draws: Optional[MaskDraws] = None):
+    def __init__(self, model: "ProteinReDiffModel", batch, sources: Optional[Sequence] = None, mask_draws: Optional[MaskDraws] = None,
+                 redesign: Optional[Redesign] = None):
         m = self.model = model
         if not m.setup_schedule:
             m.run_setup_schedule()
@@ -665,7 +704,7 @@ class ReverseDiffusion:
         b, N = batch["atom_mask"].shape
         if sources is None:
             sources = m._sources(b)
-        self.batch = batch = m.prepare_batch(batch, sources=sources, mask_draws=mask_draws)
+        self.batch = batch = m.prepare_batch(batch, sources=sources, mask_draws=mask_draws, redesign=redesign)
         self.mask = batch["residue_and_atom_mask"].contiguous()
         self.rm = batch["residue_mask"].contiguous()
         self.T = T = m.num_steps

@@ -830,20 +830,31 @@ def remove_mean(x, mask) -> torch.Tensor:
     return out
 
 
-MASK_RANDOM, MASK_SPATIAL = 0, 1        # prd_hip.h: PRD_MASK_*
+MASK_RANDOM, MASK_SPATIAL, MASK_LIGAND_NEAREST, MASK_LIGAND_WITHIN = 0, 1, 2, 3        # prd_hip.h: PRD_MASK_*
+_LIGAND_MODES = {"nearest": MASK_LIGAND_NEAREST, "within": MASK_LIGAND_WITHIN}
 
 
-def mask_lowest_k(residue_mask, p, *, key=None, atom_pos=None, atom_mask=None, ca_pos=None, tokens=None, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """The training-mode redesign mask of a batch (prd_hip.h: prd_mask_lowest_k): among the valid residues of every sample the k
+def mask_lowest_k(residue_mask, p, *, key=None, atom_pos=None, atom_mask=None, ca_pos=None, tokens=None, out=None,
+                  ligand: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The redesign mask of a batch (prd_hip.h: prd_mask_lowest_k): among the valid residues of every sample the k
     with the smallest key leave the known set, k computed on the device from the fraction ``p`` [b] -- one launch on the current
     stream, no host synchronisation.  ``key`` [b,N]: random mode (k = int(count * p) per sample); ``atom_pos`` / ``atom_mask`` /
     ``ca_pos``: spatial mode (key = distance of the C-alpha to the ligand centroid, ONE k from the lower median of the counts).
+    ``ligand`` = "nearest" | "within", with ``atom_pos`` / ``atom_mask`` / ``ca_pos`` and no ``key``: the design regions of
+    inference -- the key is the distance of the C-alpha to the nearest ligand atom; "nearest" selects the int(count * p) residues
+    with the smallest key per sample, "within" every residue whose key is <= ``p``, a radius in Angstrom.
     ``ca_pos`` may be the view ``residue_atom_pos[:, :, 1]``.  ``tokens`` (int64, optional) is masked in place.
     Returns (extra, inv) = residue_mask without the selected positions, and the selected positions (``out``: written there)."""
     b, N = residue_mask.shape
+    if ligand is not None:
+        if ligand not in _LIGAND_MODES:
+            raise ValueError(f"mask_lowest_k: ligand must be 'nearest' or 'within', got {ligand!r}")
+        if key is not None:
+            raise ValueError("mask_lowest_k: the ligand modes form their own key; key must not be given")
     spatial = key is None
     if spatial and (atom_pos is None or atom_mask is None or ca_pos is None):
-        raise ValueError("mask_lowest_k needs either key (random mode) or atom_pos, atom_mask and ca_pos (spatial mode)")
+        raise ValueError("mask_lowest_k needs either key (random mode) or atom_pos, atom_mask and ca_pos (spatial mode, ligand modes)")
+    mode = _LIGAND_MODES[ligand] if ligand is not None else MASK_SPATIAL if spatial else MASK_RANDOM
     ld_ca, ca_ptr = 0, None
     if spatial:
         if not (ca_pos.stride(2) == 1 and ca_pos.stride(0) == N * ca_pos.stride(1) and ca_pos.stride(1) >= 3):
@@ -854,9 +865,14 @@ def mask_lowest_k(residue_mask, p, *, key=None, atom_pos=None, atom_mask=None, c
     extra, inv = out if out is not None else (torch.empty_like(residue_mask), torch.empty_like(residue_mask))
     if extra.shape != residue_mask.shape or inv.shape != residue_mask.shape:
         raise ValueError("mask_lowest_k: out must be two tensors of residue_mask's shape")
-    check(lib().prd_mask_lowest_k(dptr(extra), dptr(inv), dptr(tokens, torch.int64), dptr(residue_mask), dptr(key), dptr(atom_pos),
-                                  dptr(atom_mask), ca_ptr, ld_ca, dptr(p), MASK_SPATIAL if spatial else MASK_RANDOM, b, N, stream()),
-          "prd_mask_lowest_k")
+    err = lib().prd_mask_lowest_k(dptr(extra), dptr(inv), dptr(tokens, torch.int64), dptr(residue_mask), dptr(key), dptr(atom_pos),
+                                  dptr(atom_mask), ca_ptr, ld_ca, dptr(p), mode, b, N, stream())
+    if ligand is not None and err == -1:
+        # PRD_ERR_ARG although the pointers and sizes above are what the entry documents: the library does not know the mode -- a
+        # build from before the ligand modes, selected through PRD_LIB
+        raise RuntimeError(f"prd_mask_lowest_k: this library does not know mode {mode} (PRD_MASK_LIGAND_{ligand.upper()}): an older "
+                           "build selected through PRD_LIB? rebuild it (python -m protein_redesign_amd.build)")
+    check(err, "prd_mask_lowest_k")
     return extra, inv
 
 

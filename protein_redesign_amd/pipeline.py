@@ -389,9 +389,27 @@ def update_pos(protein: Protein, num_ligand_atoms: int, pos: np.ndarray) -> Tupl
 # generate.py:138-195 without Lightning / rdkit / TM-align
 # ---------------------------------------------------------------------------------------------------
 
+def check_complex_structure(data: Mapping[str, Any]) -> None:
+    """ValueError unless the featurised complex carries the coordinates a pocket is measured in: the C-alpha column of
+    ``residue_atom_mask`` set, C-alpha coordinates that are not all zero, and at least one ligand atom with a position.  Host data
+    only; ``protein_from_sequence`` inputs have none (their coordinates are zero)."""
+    ram = torch.as_tensor(data["residue_atom_mask"])
+    rap = torch.as_tensor(data["residue_atom_pos"])
+    what = None
+    if ram.numel() == 0 or not bool((ram[:, 1] > 0.5).any()):
+        what = "no residue has its C-alpha marked in residue_atom_mask"
+    elif not bool((rap[:, 1] != 0).any()):
+        what = "the C-alpha coordinates are all zero (a protein built from its sequence alone?)"
+    elif int(data.get("num_atoms", 0)) < 1 or "atom_pos" not in data or torch.as_tensor(data["atom_pos"]).shape[0] < 1:
+        what = "there is no ligand atom with a position"
+    if what is not None:
+        raise ValueError("Redesign.within / Redesign.nearest measure a pocket and need the complex's coordinates: " + what
+                         + "; use Redesign.positions for an input without a structure")
+
+
 @torch.inference_mode()
 def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_size: int = 1, seed: int = 0,
-                     output_dir: Optional[Union[str, Path]] = None):
+                     output_dir: Optional[Union[str, Path]] = None, redesign=None):
     """Draw ``num_samples`` samples of one featurised complex ``data`` (the dict of ligand_to_data ∪ protein_to_data).
 
     Returns (positions [S,N,3] in Angstrom, logits [S,N,21], proteins, ligand_positions).  With ``output_dir`` the CA
@@ -401,19 +419,35 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     Every sample carries its DECODED sequence (generate.py:83-91 decodes every sample): residues decoded as 'X' become
     aatype -1 and are written as UNK; the input sequence is never silently kept.  The reference strips leading / trailing X
     and raises on an inner one (``RESIDUE_TYPES.index("X")``); keeping the length and marking the residue instead keeps the
-    CA trace and the sequence aligned.  A ``UserWarning`` names the samples that contain undetermined residues."""
+    CA trace and the sequence aligned.  A ``UserWarning`` names the samples that contain undetermined residues.
+
+    ``redesign`` (masking.Redesign; default None: the model's own ``redesign`` attribute, else the reference's random subset): the
+    residues to redesign -- the pocket within a radius of the ligand, the fraction nearest to it, or explicit positions.  A pocket
+    spec on an input without coordinates (``protein_from_sequence``) is refused here, on the host data, before anything is
+    uploaded.  With a spec (keyword or attribute) the return value has a FIFTH element, the mask actually used -- [N] 0/1 over
+    the collated row, the same for every sample of the complex -- and ``output_dir`` also receives ``sample_redesign_mask.npy``."""
     import warnings
 
     from .synthetic import NoiseSource, batch_to
+    spec = redesign if redesign is not None else getattr(model, "redesign", None)
+    if spec is not None and spec.needs_structure:
+        check_complex_structure(data)
     device = model.device
+    if spec is not None:
+        spec = spec.to(device)                  # a positions mask is uploaded once, not per batch
     positions, logits = [], []
+    first_batch = None
     for start in range(0, num_samples, batch_size):
         idx = list(range(start, min(start + batch_size, num_samples)))
         batch = collate_fn([data] * len(idx))
         batch = batch_to({k: v for k, v in batch.items() if torch.is_tensor(v)}, device)
-        pos, lg = model.sample(batch, sources=[NoiseSource(seed, k) for k in idx])
+        pos, lg = model.sample(batch, sources=[NoiseSource(seed, k) for k in idx], redesign=spec)
+        if first_batch is None:
+            first_batch = batch                 # sample() prepared it in place: it carries the mask that was used
         positions.append(pos.cpu())
         logits.append(lg.cpu())
+    # every sample of the complex shares the mask: read from the first prepared batch, after the loop (no synchronisation inside it)
+    used_mask = first_batch["residue_inv_extra_mask"][0].cpu().numpy() if spec is not None and first_batch is not None else None
     positions, logits = torch.cat(positions).numpy(), torch.cat(logits).numpy()
     na, nr = int(data["num_atoms"]), int(data["num_residues"])
     template = Protein(np.asarray(data["residue_chain_index"]), np.asarray(data["residue_index"]),
@@ -434,4 +468,8 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         out.mkdir(parents=True, exist_ok=True)
         proteins_to_pdb_file(proteins, out / "sample_protein.pdb")
         np.save(out / "sample_ligand_pos.npy", np.stack(ligands))
+        if used_mask is not None:
+            np.save(out / "sample_redesign_mask.npy", used_mask)
+    if spec is not None:
+        return positions, logits, proteins, ligands, used_mask
     return positions, logits, proteins, ligands

@@ -1,0 +1,303 @@
+"""CPU checks of the design regions of inference (masking.Redesign; include/prd_hip.h: PRD_MASK_LIGAND_NEAREST / _WITHIN) without a GPU:
+
+* the torch restatement of the two ligand modes (masking.restate_lowest_k(ligand=...)) against an independent float64 brute-force
+  statement, on seeded fixtures whose decision boundaries are asserted to be at least ``GAP`` wide in float64 -- then the
+  selected SETS must be equal;
+* exactly representable ties (3-4-5 and 6-8-10 offsets): the lower index wins, a radius of exactly 5 includes the whole group,
+  the next float below excludes it;
+* ``Redesign`` validation, the model's and the pipeline's refusals, and the constants of ``ops`` against the header text.
+
+tests/test_redesign_region.py imports the fixtures from here and holds the kernel against the same restatement.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+from protein_redesign_amd import masking, ops
+from protein_redesign_amd import pipeline as PL
+from protein_redesign_amd.constants import make_args
+from protein_redesign_amd.diffusion_model import ProteinReDiffModel
+from protein_redesign_amd.masking import Redesign
+from protein_redesign_amd.synthetic import synthetic_batch, synthetic_sample
+
+GAP = 1e-3          # Angstrom, in float64, at every decision boundary: coordinates within +-50 make fp32 distances good to ~1e-5
+MID_RADIUS = 14.0   # Angstrom: a radius that cuts through the residues of every fixture below
+
+# (b, N, ligand atoms, seed).  Seeds chosen so that every boundary of every case keeps GAP (asserted in boundary_gaps).
+#   N: 5; 64; 257 crosses the 256-owner pass; 640 holds 300 atoms in one key tile; 2049 crosses the key tile (long-row key store).
+#   atoms: 1; 7; 300 crosses one atom tile (MASK_ATOMS = 256 positions per tile: csrc/prd_mask.hip).
+CASES = [(1, 5, 1, 1), (3, 5, 1, 1), (1, 64, 7, 1), (3, 64, 1, 1), (1, 257, 1, 1), (3, 257, 7, 1), (1, 640, 300, 1),
+         (1, 2049, 7, 1), (3, 2049, 300, 4), (1, 2049, 1, 1)]
+SPECIAL_CASE = (3, 64, 7, 1, True)          # sample 1 without ligand atoms, sample 2 without valid residues
+K_KINDS = ("0", "1", "mid", "count-1", "count")
+
+
+def fixture(b, N, n_atoms, seed, special=False):
+    """A ragged collated batch as ``collate_fn`` lays it out -- per sample the ligand block first, then the residues (a few holes
+    in the residue mask), then padding -- with coordinates within +-50 Angstrom.  ``special`` (b = 3): sample 1 has no ligand atom,
+    sample 2 no valid residue.  Returns rm [b,N], am [b,N], ap [b,N,3], rap [b,N,37,3], tokens [b,N] int64."""
+    g = torch.Generator().manual_seed(seed)
+    rm, am = torch.zeros(b, N), torch.zeros(b, N)
+    ap, rap = torch.zeros(b, N, 3), torch.zeros(b, N, 37, 3)
+    for s in range(b):
+        na = max(1, n_atoms - s)
+        nr = max(1, N - na - (s * N) // 7)
+        assert na + nr <= N
+        am[s, :na] = 1
+        rm[s, na:na + nr] = (torch.rand(nr, generator=g) > 0.05).float()
+        rm[s, na] = 1
+        ap[s, :na] = 8.0 * (torch.rand(na, 3, generator=g) - 0.5)              # a ligand 8 Angstrom across ...
+        rap[s, na:na + nr] = 48.0 * (torch.rand(nr, 37, 3, generator=g) - 0.5)  # ... inside a protein 48 Angstrom across
+    if special:
+        am[1] = 0
+        rm[2] = 0
+    tokens = torch.randint(4, 24, (b, N), generator=g)
+    return rm, am, ap, rap, tokens
+
+
+def brute_force_keys(rm, am, ap, ca):
+    """float64, written independently of the restatement: per sample and valid residue the nested minimum over the ligand atoms
+    of sqrt(|ca - atom|^2 + 1e-12); inf without atoms, NaN at a position that is no valid residue."""
+    rm, am, ap, ca = (np.asarray(t, dtype=np.float64) for t in (rm, am, ap, ca))
+    b, N = rm.shape
+    keys = np.full((b, N), np.nan)
+    for s in range(b):
+        atoms = [a for a in range(N) if am[s, a] > 0.5]
+        for i in range(N):
+            if rm[s, i] > 0.5:
+                keys[s, i] = np.sqrt(((ca[s, i][None] - ap[s, atoms]) ** 2).sum(-1) + 1e-12).min() if atoms else np.inf
+    return keys
+
+
+def brute_force_nearest(rm, keys, k):
+    """inv [b,N]: the k[s] valid residues with the smallest key, ties to the lower index (a stable sort)."""
+    inv = np.zeros(keys.shape, dtype=np.float32)
+    for s in range(keys.shape[0]):
+        valid = np.nonzero(np.asarray(rm[s]) > 0.5)[0]
+        if np.isfinite(keys[s, valid]).all():                          # no ligand atom: nothing is selected
+            inv[s, valid[np.argsort(keys[s, valid], kind="stable")[:int(k[s])]]] = 1
+    return torch.from_numpy(inv)
+
+
+def brute_force_within(rm, keys, radius):
+    inv = np.zeros(keys.shape, dtype=np.float32)
+    for s in range(keys.shape[0]):
+        for i in range(keys.shape[1]):
+            if rm[s, i] > 0.5 and keys[s, i] <= radius[s]:             # False for a NaN radius, for an inf key
+                inv[s, i] = 1
+    return torch.from_numpy(inv)
+
+
+def k_of(kind, counts):
+    return {"0": 0 * counts, "1": counts.clamp(max=1), "mid": counts // 3, "count-1": (counts - 1).clamp(min=0), "count": counts}[kind]
+
+
+def fraction_for(k, counts):
+    """p with int(count * p) = k: the half keeps the double product clear of an integer (k = 0 without residues: p = 0)."""
+    return torch.where(counts > 0, (k + 0.5) / counts.clamp(min=1), torch.zeros_like(counts, dtype=torch.float64)).clamp(max=1.0).float()
+
+
+def boundary_gaps(rm, keys, ks, radii):
+    """The smallest float64 distance of a decision boundary to a key: between the k-th and the (k+1)-th key for every k of
+    ``ks`` ([b] each), between each radius of ``radii`` ([b] each) and the nearest key on either side."""
+    gap = np.inf
+    for s in range(keys.shape[0]):
+        d = np.sort(keys[s][np.asarray(rm[s]) > 0.5])
+        if d.size == 0 or not np.isfinite(d).all():
+            continue
+        for k in ks:
+            if 0 < int(k[s]) < d.size:
+                gap = min(gap, d[int(k[s])] - d[int(k[s]) - 1])
+        for r in radii:
+            if np.isfinite(r[s]):
+                gap = min(gap, np.abs(d - float(r[s])).min())
+    return gap
+
+
+def case_requests(rm, b):
+    """Every request of a case: [(ligand mode, p [b] fp32, k [b] or None, label)]."""
+    counts = (rm > 0.5).sum(-1)
+    out = [("nearest", fraction_for(k_of(kind, counts), counts), k_of(kind, counts), kind) for kind in K_KINDS]
+    for label, r in (("0", 0.0), ("mid", MID_RADIUS), ("beyond", 1e4), ("nan", float("nan"))):
+        out.append(("within", torch.full((b,), r), None, label))
+    return out
+
+
+def case_id(c):
+    return "b%d-N%d-a%d" % c[:3]
+
+
+@pytest.mark.parametrize("case", CASES + [SPECIAL_CASE], ids=case_id)
+def test_restatement_equals_the_float64_brute_force(case):
+    b, N = case[0], case[1]
+    rm, am, ap, rap, tokens = fixture(*case)
+    ca = rap[:, :, 1]
+    keys = brute_force_keys(rm, am, ap, ca)
+    reqs = case_requests(rm, b)
+    gap = boundary_gaps(rm, keys, [k for m, _, k, _ in reqs if m == "nearest"], [p.double().numpy() for m, p, _, _ in reqs if m == "within"])
+    print(f"\n{case_id(case)}: smallest float64 boundary gap {gap:.2e} A")
+    assert gap >= GAP, "fixture too close to a decision boundary: pick another seed"
+    for mode, p, k, label in reqs:
+        extra, inv, tok = masking.restate_lowest_k(rm, p, atom_pos=ap, atom_mask=am, ca_pos=ca, tokens=tokens, ligand=mode)
+        want = brute_force_nearest(rm, keys, k) if mode == "nearest" else brute_force_within(rm, keys, p.double().numpy())
+        assert torch.equal(inv, want), (mode, label, int((inv != want).sum()))
+        assert torch.equal(extra, rm - inv)
+        assert torch.equal(tok, torch.where(inv > 0.5, torch.full_like(tokens, 32), tokens * rm.long() + (1 - rm).long()))
+        if mode == "nearest" and (am.sum(-1) > 0).all():
+            assert inv.sum(-1).tolist() == k.tolist(), (label, k)
+    if len(case) > 4:           # the special samples: no ligand atom -> nothing selected; no valid residue -> extra = residue_mask, inv = 0
+        for mode, p in (("nearest", 1.0), ("within", 1e4)):
+            extra, inv, _ = masking.restate_lowest_k(rm, p, atom_pos=ap, atom_mask=am, ca_pos=ca, ligand=mode)
+            assert torch.equal(inv[0], rm[0]) and float(inv[1:].sum()) == 0 and torch.equal(extra[1:], rm[1:])
+
+
+def tie_fixture():
+    """One ligand atom at (1, 2, 3); residues at integer offsets from it: four at distance exactly 5 (3-4-5), three at exactly 10
+    (6-8-10), one at 1, one at 20, and a hole in the residue mask inside the 5-group.  In fp32 25 + 1e-12 = 25 and the root is 5."""
+    offs = [(20, 0, 0), (3, 4, 0), (6, 8, 0), (0, 3, 4), (4, 0, 3), (1, 0, 0), (0, 6, 8), (-3, -4, 0), (0, -4, 3), (8, 0, -6)]
+    N = 1 + len(offs) + 2
+    rm, am = torch.zeros(1, N), torch.zeros(1, N)
+    ap, rap = torch.zeros(1, N, 3), torch.zeros(1, N, 37, 3)
+    am[0, 0] = 1
+    ap[0, 0] = torch.tensor([1.0, 2.0, 3.0])
+    rm[0, 1:1 + len(offs)] = 1
+    rap[0, 1:1 + len(offs), 1] = torch.tensor(offs, dtype=torch.float32) + ap[0, 0]
+    rm[0, 4] = 0                            # offset (0, 3, 4): at distance 5, but no valid residue
+    tokens = torch.arange(4, 4 + N).unsqueeze(0)
+    return rm, am, ap, rap, tokens
+
+
+# position: 1 -> 20, 2 -> 5, 3 -> 10, (4: hole), 5 -> 5, 6 -> 1, 7 -> 10, 8 -> 5, 9 -> 5, 10 -> 10; 9 valid residues
+TIE_NEAREST = {0: [], 1: [6], 2: [6, 2], 3: [6, 2, 5], 4: [6, 2, 5, 8], 5: [6, 2, 5, 8, 9], 6: [6, 2, 5, 8, 9, 3], 7: [6, 2, 5, 8, 9, 3, 7],
+               8: [6, 2, 5, 8, 9, 3, 7, 10], 9: [6, 2, 5, 8, 9, 3, 7, 10, 1]}
+BELOW_5 = float(np.nextafter(np.float32(5), np.float32(0)))
+TIE_WITHIN = {5.0: [6, 2, 5, 8, 9], BELOW_5: [6], 10.0: [6, 2, 5, 8, 9, 3, 7, 10], 1.0: [6], 0.5: []}
+
+
+def tie_requests():
+    """[(ligand mode, p, the positions selected)] on tie_fixture(): every k, cutting through both tie groups, and the radii at and
+    just below a tie."""
+    out = [("nearest", (k + 0.5) / 9, sel) for k, sel in TIE_NEAREST.items()]
+    return out + [("within", r, sel) for r, sel in TIE_WITHIN.items()]
+
+
+def test_exactly_representable_ties():
+    rm, am, ap, rap, tokens = tie_fixture()
+    keys = masking.ligand_keys(ap, am, rap[:, :, 1])
+    assert keys[0, [2, 5, 8, 9]].tolist() == [5.0] * 4 and keys[0, [3, 7, 10]].tolist() == [10.0] * 3 and keys[0, 4].item() == 5.0
+    assert BELOW_5 < 5.0
+    for mode, p, sel in tie_requests():
+        extra, inv, _ = masking.restate_lowest_k(rm, p, atom_pos=ap, atom_mask=am, ca_pos=rap[:, :, 1], ligand=mode)
+        assert sorted(torch.nonzero(inv[0]).flatten().tolist()) == sorted(sel), (mode, p)
+        assert torch.equal(extra, rm - inv)
+
+
+def test_redesign_validation():
+    assert Redesign.within(8).value == 8.0 and Redesign.within(0.0).kind == "within" and Redesign.within(float("inf")).value == float("inf")
+    assert Redesign.nearest(0).value == 0.0 and Redesign.nearest(1.0).kind == "nearest"
+    for bad in (float("nan"), -1.0, -1e-9):
+        with pytest.raises(ValueError, match="radius"):
+            Redesign.within(bad)
+    for bad in (float("nan"), -0.1, 1.0001, 30):
+        with pytest.raises(ValueError, match="fraction"):
+            Redesign.nearest(bad)
+    for bad in (torch.tensor([0.0, 0.5, 1.0]), torch.tensor([0, 2]), torch.tensor([float("nan")]), torch.zeros(2, 2, 2), torch.zeros(0)):
+        with pytest.raises(ValueError, match="mask"):
+            Redesign.positions(bad)
+    with pytest.raises(ValueError, match="kind"):
+        Redesign("pocket", value=1.0)
+    src = torch.tensor([0, 1, 1, 0])
+    spec = Redesign.positions(src)
+    assert spec.mask.dtype == torch.float32 and spec.mask.tolist() == [0, 1, 1, 0] and spec.keep.tolist() == [1, 0, 0, 1]
+    src[0] = 1                              # the spec keeps its own copy ...
+    assert spec.mask.tolist() == [0, 1, 1, 0]
+    with pytest.raises(Exception):          # ... and is immutable
+        spec.mask = src
+    assert Redesign.positions(torch.tensor([[True, False]])).mask.shape == (1, 2)
+    assert spec.to("cpu") is spec and Redesign.within(3.0).to("cpu").value == 3.0
+    assert not spec.needs_structure and Redesign.within(1).needs_structure and Redesign.nearest(0.1).needs_structure
+
+
+def small_model(**kw):
+    return ProteinReDiffModel(make_args(single_dim=32, pair_dim=32, head_dim=16, num_heads=4, num_blocks=1, esm_dim=16, num_steps=6,
+                                        mask_prob=0.15, **kw))
+
+
+def test_model_refuses_a_spec_under_training_mode_and_reaches_the_operator_otherwise():
+    m = small_model(training_mode=True)
+    for spec in (Redesign.within(8.0), Redesign.nearest(0.2), Redesign.positions(torch.ones(14))):
+        with pytest.raises(ValueError, match="training_mode"):
+            m.prepare_batch(synthetic_batch([(3, 9), (2, 6)], esm_dim=16, seed=5, n_total=14), redesign=spec)
+        with pytest.raises(ValueError, match="training_mode"):
+            m.sample(synthetic_batch([(3, 9)], esm_dim=16, seed=5), redesign=spec)
+    m.redesign = Redesign.within(8.0)       # the attribute counts like the keyword
+    with pytest.raises(ValueError, match="training_mode"):
+        m.prepare_batch(synthetic_batch([(3, 9)], esm_dim=16, seed=5))
+    m = small_model()
+    assert m.redesign is None
+    with pytest.raises(TypeError):
+        m.prepare_batch(synthetic_batch([(3, 9)], esm_dim=16, seed=5), redesign=8.0)
+    for spec in (Redesign.within(8.0), Redesign.nearest(0.2)):      # the pocket specs go to the HIP operator: no CPU fallback
+        with pytest.raises(RuntimeError, match="GPU only"):
+            m.prepare_batch(synthetic_batch([(3, 9), (2, 6)], esm_dim=16, seed=5, n_total=14), redesign=spec)
+    assert m._sample_counter == 0           # the noise sources are not consulted for the mask
+    # explicit positions are plain torch: the prepared batch on any device
+    batch = synthetic_batch([(3, 9), (2, 6)], esm_dim=16, seed=5, n_total=14)
+    rm, rt = batch["residue_mask"].clone(), batch["residue_type"].clone()
+    mask = torch.zeros(14)
+    mask[[1, 4, 5, 13]] = 1                 # 1: a ligand atom; 13: padding; 4, 5: residues of both samples
+    pb = m.prepare_batch(batch, redesign=Redesign.positions(mask))
+    assert torch.equal(pb["residue_inv_extra_mask"], rm * mask) and torch.equal(pb["residue_extra_mask"], rm * (1 - mask))
+    assert pb["residue_inv_extra_mask"].sum(-1).tolist() == [2, 2]
+    assert torch.equal(pb["residue_type_masked"], (rt * pb["residue_extra_mask"]).long())
+    assert float(pb["residue_one_hot"][:, [4, 5]].abs().sum()) == 0 and float(pb["residue_esm"][:, [4, 5]].abs().sum()) == 0
+    with pytest.raises(ValueError, match="shape"):
+        m.prepare_batch(synthetic_batch([(3, 9)], esm_dim=16, seed=5), redesign=Redesign.positions(torch.ones(5)))
+
+
+class _NoDevice:
+    """A model stand-in whose every attribute access fails: generate_samples must refuse before it touches the model."""
+
+    def __getattr__(self, name):
+        raise AssertionError(f"the model was touched ({name}) before the input was checked")
+
+
+def test_pipeline_refuses_a_pocket_without_coordinates():
+    lig = {k: v for k, v in synthetic_sample(5, 9, esm_dim=16, seed=8).items() if k.startswith(("atom_", "bond_")) or k == "num_atoms"}
+    data = PL.protein_to_data(PL.protein_from_sequence("ACDEFGHIK"), **lig)
+    for spec in (Redesign.within(8.0), Redesign.nearest(0.3)):
+        with pytest.raises(ValueError, match="coordinates"):
+            PL.generate_samples(_NoDevice(), data, num_samples=2, redesign=spec)
+    full = synthetic_sample(5, 9, esm_dim=16, seed=8)
+    for broken, what in ((dict(full, residue_atom_mask=torch.zeros(9, 37)), "C-alpha"), (dict(full, num_atoms=0), "ligand atom")):
+        with pytest.raises(ValueError, match=what):
+            PL.generate_samples(_NoDevice(), broken, num_samples=1, redesign=Redesign.within(8.0))
+    PL.check_complex_structure(full)        # a complex with coordinates passes
+
+
+def test_sharded_sampler_passes_the_spec_through():
+    from protein_redesign_amd.distributed import sample_sharded
+    seen = []
+
+    def sampler(batch, sources, **kw):
+        seen.append(kw)
+        b, N = batch["atom_mask"].shape
+        return torch.zeros(b, N, 3), torch.zeros(b, N, 21)
+
+    one = {k: v for k, v in synthetic_batch([(3, 9)], esm_dim=16, seed=5).items() if torch.is_tensor(v)}
+    spec = Redesign.within(8.0)
+    sample_sharded(sampler, one, 3, batch_size=2, redesign=spec)
+    sample_sharded(sampler, one, 1)
+    assert seen == [{"redesign": spec}, {"redesign": spec}, {}] and seen[0]["redesign"] is spec
+
+
+def test_constants_equal_the_header():
+    text = open(os.path.join(ROOT, "include", "prd_hip.h")).read()
+    defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define (PRD_MASK_\w+) (\d+)\s*$", text, re.M)}
+    assert defines == {"PRD_MASK_RANDOM": ops.MASK_RANDOM, "PRD_MASK_SPATIAL": ops.MASK_SPATIAL,
+                       "PRD_MASK_LIGAND_NEAREST": ops.MASK_LIGAND_NEAREST, "PRD_MASK_LIGAND_WITHIN": ops.MASK_LIGAND_WITHIN}
+    assert (ops.MASK_RANDOM, ops.MASK_SPATIAL, ops.MASK_LIGAND_NEAREST, ops.MASK_LIGAND_WITHIN) == (0, 1, 2, 3)
