@@ -1,0 +1,172 @@
+"""Superposition and TM-score of generated samples on the device: ctypes binding of libprd_align.so (include/prd_align.h) and the
+public functions on top of it.  The reference's generate.py:163-195 does this per sample with the TM-align program; here the residue
+correspondence is known, so what is left is the TM-score superposition search, run for many pairs in one call.
+
+Everything runs on the current stream with no host synchronisation.  HIP only: a missing library or a CPU tensor raises."""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import os
+
+import torch
+
+from ._lib import dptr, parse_header, stream
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "libprd_align.so")
+HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "prd_align.h")
+
+with open(HEADER_PATH) as _f:
+    ENTRIES = parse_header(_f.read())          # the header is the only statement of the C ABI
+
+ABI_VERSION = 100           # include/prd_align.h PRD_ALIGN_VERSION this binding is written against
+MAX_N = 4096                # PRD_ALIGN_MAX_N
+MODES = {"tm": 0, "rmsd": 1}
+PAIRS_CROSS, PAIRS_SELF = 0, 1
+ERR_UNSUPPORTED = -3
+
+_lib = None
+
+
+def lib():
+    """The loaded library; raises RuntimeError (never falls back) when it has not been built."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -m protein_redesign_amd.build --align` "
+                               "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
+        cdll = C.CDLL(LIB_PATH)
+        for name, e in ENTRIES.items():
+            fn = getattr(cdll, name)
+            fn.argtypes, fn.restype = e.argtypes, e.restype
+        if cdll.prd_align_version() != ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} reports PRD_ALIGN_VERSION {cdll.prd_align_version()}, this binding was written against "
+                               f"{ABI_VERSION}: rebuild with `python -m protein_redesign_amd.build --align`")
+        _lib = cdll
+    return _lib
+
+
+def _check(code: int, what: str):
+    if code == ERR_UNSUPPORTED:
+        raise ValueError(f"{what}: at most {MAX_N} positions per structure (PRD_ALIGN_MAX_N) and 65535 structures per apply")
+    if code != 0:
+        names = {-1: "PRD_ALIGN_ERR_ARG", -4: "PRD_ALIGN_ERR_WORKSPACE"}
+        raise RuntimeError(f"{what} failed: {names.get(code, 'hipError_t ' + str(code))}")
+
+
+@dataclasses.dataclass(frozen=True)
+class Superposition:
+    """Device tensors, one entry per pair: ``ref ~ translation + x @ rotation`` (row vectors, generate.py:180)."""
+    tm: torch.Tensor                # [...]
+    rmsd: torch.Tensor              # [...] Angstrom, over the masked positions under the transform
+    rotation: torch.Tensor          # [..., 3, 3]; determinant -1 where mirrored
+    translation: torch.Tensor       # [..., 3]
+    mirrored: torch.Tensor          # [...] int32
+
+
+def _structures(t, name, N=None):
+    """[K,N,3] fp32 device tensor whose last stride is 1 (made so if it is not); returns (tensor, structure stride, row stride)"""
+    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{name} must be a [K,N,3] tensor, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    if N is not None and t.shape[1] != N:
+        raise ValueError(f"{name} has {t.shape[1]} positions, expected {N}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: the alignment runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if t.stride(2) != 1 or t.stride(1) < 3 or t.stride(0) < 0:
+        t = t.contiguous()
+    return t, t.stride(0), t.stride(1)
+
+
+def _mask(mask, N, device):
+    if not torch.is_tensor(mask) or mask.shape != (N,):
+        raise ValueError(f"mask must be a [{N}] tensor, got {tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__}")
+    if mask.dtype != torch.float32:
+        raise ValueError(f"mask must be float32 (0 / 1), got {mask.dtype}")
+    if mask.device != device:
+        raise ValueError(f"mask is on {mask.device}, the structures on {device}")
+    return mask.contiguous()
+
+
+def _run(x, y, mask, S, R, N, pairs, mode, mirror):
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
+    if N > MAX_N:
+        raise ValueError(f"superimpose: {N} positions per structure, at most {MAX_N} (PRD_ALIGN_MAX_N) are supported")
+    L = lib()
+    x, xs, xr = x
+    y, ys, yr = y if y is not None else (None, 0, 0)
+    dev = x.device
+    nbytes = L.prd_align_workspace_bytes(S, R, N, pairs, MODES[mode], int(bool(mirror)))
+    if nbytes == 0:
+        raise ValueError(f"superimpose: {S} x {R} structures of {N} positions are outside what the library takes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = Superposition(torch.empty(S, R, **f32), torch.empty(S, R, **f32), torch.empty(S, R, 3, 3, **f32), torch.empty(S, R, 3, **f32),
+                        torch.empty(S, R, dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        _check(L.prd_align_superimpose(dptr(out.tm), dptr(out.rmsd), dptr(out.rotation), dptr(out.translation), dptr(out.mirrored, torch.int32),
+                                       x.data_ptr(), xs, xr, y.data_ptr() if y is not None else None, ys, yr, dptr(mask),
+                                       S, R, N, pairs, MODES[mode], int(bool(mirror)), ws.data_ptr(), nbytes, stream()),
+               "prd_align_superimpose")
+    return out
+
+
+def superimpose(x, ref, mask, mirror: bool = True, mode: str = "tm") -> Superposition:
+    """Superimpose every structure of ``x`` [S,N,3] on ``ref`` -- [N,3] (results [S]) or [R,N,3] (results [S,R]) -- over the positions
+    where ``mask`` [N] is 1.  ``mode="tm"``: the TM-score superposition search; ``"rmsd"``: one Kabsch fit over all masked positions.
+    ``mirror``: also try the mirror image of ``x`` and keep the better fit (the network is equivariant under reflections).  ``ref``
+    may be a strided view such as ``residue_atom_pos[:, 1]``.  fp32 device tensors; one call, no host synchronisation."""
+    x = _structures(x, "x")
+    S, N = x[0].shape[:2]
+    if not torch.is_tensor(ref) or ref.dim() not in (2, 3):
+        raise ValueError("ref must be a [N,3] or [R,N,3] tensor")
+    single = ref.dim() == 2
+    y = _structures(ref.unsqueeze(0) if single else ref, "ref", N)
+    if y[0].device != x[0].device:
+        raise ValueError(f"ref is on {y[0].device}, x on {x[0].device}")
+    R = y[0].shape[0]
+    out = _run(x, y, _mask(mask, N, x[0].device), S, R, N, PAIRS_CROSS, mode, mirror)
+    if single:
+        out = Superposition(out.tm[:, 0], out.rmsd[:, 0], out.rotation[:, 0], out.translation[:, 0], out.mirrored[:, 0])
+    return out
+
+
+def pairwise(x, mask, mirror: bool = True, mode: str = "tm") -> Superposition:
+    """All pairs of the structures ``x`` [S,N,3] among themselves ([S,S] results): only s < r is searched, (r, s) is its inverse,
+    the diagonal is tm 1, rmsd 0, identity."""
+    x = _structures(x, "x")
+    S, N = x[0].shape[:2]
+    return _run(x, None, _mask(mask, N, x[0].device), S, S, N, PAIRS_SELF, mode, mirror)
+
+
+def pairwise_tm(x, mask, mirror: bool = True) -> torch.Tensor:
+    """[S,S] TM-scores of the structures ``x`` [S,N,3] among themselves (symmetric, diagonal 1)."""
+    return pairwise(x, mask, mirror=mirror).tm
+
+
+def diversity(x, mask, mirror: bool = True) -> torch.Tensor:
+    """Mean pairwise TM-score over s != r (a 0-dim device tensor; NaN for a single structure): the paper's diversity figure."""
+    tm = pairwise_tm(x, mask, mirror=mirror)
+    S = tm.shape[0]
+    return (tm.sum() - tm.diagonal().sum()) / float(S * (S - 1)) if S > 1 else torch.full((), float("nan"), device=tm.device)
+
+
+def apply(pos, rotation, translation) -> torch.Tensor:
+    """``translation + pos @ rotation`` for ``pos`` [S,N,3] (or [N,3]) with one transform per structure: whole rows, ligand atoms
+    included.  A new tensor."""
+    single = pos.dim() == 2
+    p = pos.unsqueeze(0) if single else pos
+    if p.dim() != 3 or p.shape[2] != 3:
+        raise ValueError(f"pos must be [S,N,3] or [N,3], got {tuple(pos.shape)}")
+    S, N = p.shape[:2]
+    rot, tr = rotation.reshape(-1, 3, 3), translation.reshape(-1, 3)
+    if rot.shape[0] != S or tr.shape[0] != S:
+        raise ValueError(f"{S} structures but {rot.shape[0]} rotations and {tr.shape[0]} translations")
+    p, rot, tr = p.contiguous(), rot.contiguous(), tr.contiguous()
+    out = torch.empty_like(p)
+    with torch.cuda.device(p.device):
+        _check(lib().prd_align_apply(dptr(out), dptr(p), dptr(rot), dptr(tr), S, N, stream()), "prd_align_apply")
+    return out[0] if single else out

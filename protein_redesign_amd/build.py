@@ -15,6 +15,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 EXTRA_FLAGS = {"prd_tri2.hip": ["-fno-slp-vectorize"]}
 PRD_HIP_H = os.path.join(os.path.dirname(HERE), "include", "prd_hip.h")
 HEADERS = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_tri2_v3_body.inc"), PRD_HIP_H]      # every object depends on these
+# libprd_align.so (include/prd_align.h): superposition and TM-score of generated samples -- post-processing, not part of the denoiser
+# ABI, hence a library of its own with its own header; same flags, same compile routine
+LIB_ALIGN = os.path.join(HERE, "libprd_align.so")
+ALIGN_SOURCES = ["prd_align.hip"]
+PRD_ALIGN_H = os.path.join(os.path.dirname(HERE), "include", "prd_align.h")
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -28,6 +33,8 @@ VARIANTS = {
     "asan": Variant(["-g"] + _ASAN + ["-fno-omit-frame-pointer"], _ASAN, os.path.join(CSRC, "asan"), os.path.join(HERE, "libprd_hip_asan.so"), None),
 }
 
+
+ALIGN = Variant(VARIANTS["shipped"].cflags, [], CSRC, LIB_ALIGN, None)       # built from ALIGN_SOURCES; not a variant of libprd_hip.so
 
 RESOURCE_JSON = os.path.join(CSRC, "resource_usage.json")     # per kernel: VGPRs, AGPRs, SGPRs, scratch bytes / lane, occupancy, LDS
 
@@ -75,8 +82,13 @@ def _hipcc():
     return os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
+def _headers(src):
+    """the headers an object of ``src`` depends on"""
+    return [PRD_ALIGN_H] if src in ALIGN_SOURCES else HEADERS
+
+
 def _stamp(src):
-    return max(os.path.getmtime(d) for d in [os.path.join(CSRC, src)] + HEADERS)
+    return max(os.path.getmtime(d) for d in [os.path.join(CSRC, src)] + _headers(src))
 
 
 def _resources(update=None):
@@ -97,13 +109,14 @@ def _resources(update=None):
     return have
 
 
-def resource_usage(verbose: bool = False):
+def resource_usage(verbose: bool = False, sources=None):
     """Register / scratch / occupancy figures of every kernel of the library, as the compiler reports them for the committed flags
     (hipcc cross-compiles without a GPU).  ``build()`` writes them next to the objects; a source whose figures are missing is
     analysed here (device code only, nothing linked).  tests/test_build_resources.py holds the default-dispatch kernels of the
-    sampling step to ScratchSize == 0."""
+    sampling step to ScratchSize == 0.  ``sources``: another list than the denoiser library's (ALIGN_SOURCES)."""
+    sources = SOURCES if sources is None else sources
     have, new = _resources(), {}
-    for src in SOURCES:
+    for src in sources:
         if src in have and have[src].get("stamp") == _stamp(src):
             continue
         cmd = [_hipcc()] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", os.path.join(CSRC, src), "-o", os.devnull]
@@ -114,7 +127,7 @@ def resource_usage(verbose: bool = False):
             raise RuntimeError(f"resource analysis of {src} failed:\n{r.stderr[-2000:]}")
         new[src] = {"stamp": _stamp(src), "kernels": parse_resource_usage(r.stderr)}
     have = _resources(new)
-    return {k: v for src in SOURCES for k, v in have[src]["kernels"].items()}
+    return {k: v for src in sources for k, v in have[src]["kernels"].items()}
 
 
 def _stale(out, deps):
@@ -130,12 +143,11 @@ def _run(cmd, verbose):
     subprocess.check_call(cmd)
 
 
-def _build(name: str, force: bool = False, verbose: bool = True) -> str:
-    """Compile SOURCES into the variant's object directory and link its library; only what is stale, unless ``force``."""
-    v = VARIANTS[name]
+def _build(v: Variant, sources, force: bool = False, verbose: bool = True) -> str:
+    """Compile ``sources`` into the variant's object directory and link its library; only what is stale, unless ``force``."""
     os.makedirs(v.objdir, exist_ok=True)
     objs = []
-    for src in SOURCES:
+    for src in sources:
         spath = os.path.join(CSRC, src)
         if not os.path.exists(spath):
             raise FileNotFoundError(f"HIP source listed in build.py is missing: {spath}")
@@ -146,7 +158,7 @@ def _build(name: str, force: bool = False, verbose: bool = True) -> str:
                     continue
         obj = os.path.join(v.objdir, src.replace(".hip", ".o"))
         objs.append(obj)
-        if not (force or _stale(obj, [spath] + HEADERS)):
+        if not (force or _stale(obj, [spath] + _headers(src))):
             continue
         cmd = [_hipcc()] + FLAGS + EXTRA_FLAGS.get(src, []) + v.cflags + ["-c", spath, "-o", obj]
         if verbose:
@@ -167,7 +179,13 @@ def _build(name: str, force: bool = False, verbose: bool = True) -> str:
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
-    return _build("shipped", force, verbose)
+    return _build(VARIANTS["shipped"], SOURCES, force, verbose)
+
+
+def build_align(force: bool = False, verbose: bool = True) -> str:
+    """libprd_align.so (include/prd_align.h, protein_redesign_amd/align.py): the one source csrc/prd_align.hip with the committed
+    FLAGS.  ``build()`` does not compile it: the denoiser library and its recorded command lines stay what they are."""
+    return _build(ALIGN, ALIGN_SOURCES, force, verbose)
 
 
 def build_asan(verbose: bool = True) -> str:
@@ -175,7 +193,7 @@ def build_asan(verbose: bool = True) -> str:
     (-fsanitize=address; device code is compiled as usual: -fno-gpu-sanitize) and the argument-validation driver
     tests/native/host_abi_check.c linked against it.  Runs on a machine without a GPU: every call of
     the driver is rejected by the argument checks before any HIP API is used.  Returns the path of the driver binary."""
-    lib = _build("asan", verbose=verbose)
+    lib = _build(VARIANTS["asan"], SOURCES, verbose=verbose)
     exe = os.path.join(VARIANTS["asan"].objdir, "host_abi_check")
     driver = os.path.join(os.path.dirname(HERE), "tests", "native", "host_abi_check.c")
     if _stale(exe, [driver, lib, PRD_HIP_H]):
@@ -189,13 +207,13 @@ def build_ab(verbose: bool = True) -> str:
     them).  For A/B measurements (PRD_LIB=<path> PRD_TA_VARIANT=10 ...) and for the parity tests of those kernels, which
     tests/test_ab_build.py runs against this library in a child process."""
     build(verbose=verbose)                                   # sources that never test PRD_AB share the shipped objects
-    return _build("ab", verbose=verbose)
+    return _build(VARIANTS["ab"], SOURCES, verbose=verbose)
 
 
 def build_timing(verbose: bool = True) -> str:
     """Diagnostic build with in-kernel cycle stamps (-DPRD_TIMING: tools/ta_timing.py, tools/phase_timing.py read them through
     prd_debug_read); load it with PRD_LIB=<path>.  Never the shipped library: the stamps cost ~10 % of a wave's cycles."""
-    return _build("timing", verbose=verbose)
+    return _build(VARIANTS["timing"], SOURCES, verbose=verbose)
 
 
 if __name__ == "__main__":
@@ -205,8 +223,11 @@ if __name__ == "__main__":
     if "--timing" in sys.argv:
         print(build_timing())
         sys.exit(0)
+    if "--align" in sys.argv:
+        print(build_align(force="--force" in sys.argv))
+        sys.exit(0)
     if "--resources" in sys.argv:
-        for name, u in sorted(resource_usage(verbose=True).items()):
+        for name, u in sorted({**resource_usage(verbose=True), **resource_usage(verbose=True, sources=ALIGN_SOURCES)}.items()):
             print(f"{u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}")
         sys.exit(0)
     if "--asan" in sys.argv:

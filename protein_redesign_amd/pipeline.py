@@ -407,9 +407,36 @@ def check_complex_structure(data: Mapping[str, Any]) -> None:
                          + "; use Redesign.positions for an input without a structure")
 
 
+def _alignment_reference(data: Mapping[str, Any], align_to) -> Optional[np.ndarray]:
+    """The [nr,3] C-alpha coordinates that ``generate_samples(align_to=...)`` superimposes on (None: the first sample), from host
+    data alone; ValueError for a request that cannot be served."""
+    nr = int(data["num_residues"])
+    if isinstance(align_to, str):
+        if align_to == "first":
+            return None
+        if align_to != "input":
+            raise ValueError(f"align_to must be 'input', 'first', a Protein or an [{nr},3] array, got {align_to!r}")
+        ram, rap = torch.as_tensor(data["residue_atom_mask"]), torch.as_tensor(data["residue_atom_pos"])
+        what = None
+        if ram.numel() == 0 or not bool((ram[:, 1] > 0.5).any()):
+            what = "no residue has its C-alpha marked in residue_atom_mask"
+        elif not bool((rap[:, 1] != 0).any()):
+            what = "the C-alpha coordinates are all zero (a protein built from its sequence alone?)"
+        if what is not None:
+            raise ValueError("align_to='input' superimposes the samples on the complex's own C-alpha coordinates: " + what
+                             + "; use align_to='first' or pass a reference structure")
+        return np.asarray(rap[:, 1], dtype=np.float32)
+    ref = align_to.atom_pos[:, 1] if isinstance(align_to, Protein) else align_to
+    ref = np.asarray(ref, dtype=np.float32)
+    if ref.shape != (nr, 3):
+        raise ValueError(f"align_to: the reference has shape {ref.shape}, the complex has {nr} residues ([{nr},3] expected; chains of "
+                         "another length need a sequence alignment, which is out of scope)")
+    return ref
+
+
 @torch.inference_mode()
 def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_size: int = 1, seed: int = 0,
-                     output_dir: Optional[Union[str, Path]] = None, redesign=None):
+                     output_dir: Optional[Union[str, Path]] = None, redesign=None, align_to=None, mirror: bool = True):
     """Draw ``num_samples`` samples of one featurised complex ``data`` (the dict of ligand_to_data ∪ protein_to_data).
 
     Returns (positions [S,N,3] in Angstrom, logits [S,N,21], proteins, ligand_positions).  With ``output_dir`` the CA
@@ -425,10 +452,24 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     residues to redesign -- the pocket within a radius of the ligand, the fraction nearest to it, or explicit positions.  A pocket
     spec on an input without coordinates (``protein_from_sequence``) is refused here, on the host data, before anything is
     uploaded.  With a spec (keyword or attribute) the return value has a FIFTH element, the mask actually used -- [N] 0/1 over
-    the collated row, the same for every sample of the complex -- and ``output_dir`` also receives ``sample_redesign_mask.npy``."""
+    the collated row, the same for every sample of the complex -- and ``output_dir`` also receives ``sample_redesign_mask.npy``.
+
+    ``align_to`` (default None: nothing below happens, every return value and file is what it was): superimpose every sample on a
+    reference and score it, as generate.py:163-195 does with TM-align -- here with the TM-score superposition search of
+    ``protein_redesign_amd.align`` on the device, on the samples as ``model.sample`` returned them, before they are copied to the
+    host.  ``"input"``: the complex's own C-alpha coordinates (refused, before anything is uploaded, for an input without
+    coordinates such as ``protein_from_sequence``); ``"first"``: the first sample, the reference's fallback (a ``UserWarning``: the
+    structures may then all be mirror images); a ``Protein``; or an ``[nr,3]`` array of C-alpha coordinates.  The positions that
+    count are the residues whose C-alpha is marked in ``residue_atom_mask``.  ``mirror`` (default True): also fit the mirror image
+    of the sample and keep the better one, as the reference does.  The transform is applied to whole rows -- the C-alpha trace and
+    the ligand atoms -- so ``positions``, ``proteins`` and ``ligand_positions`` come back in the reference's frame.  The return
+    value gains one trailing ``dict``: ``tmscore`` [S], ``rmsd`` [S], ``mirrored`` [S], ``rotation`` [S,3,3], ``translation`` [S,3]
+    (``reference ~ translation + sample @ rotation``) and ``diversity``, the mean pairwise TM-score of the S samples among themselves (a
+    float; NaN for S = 1).  ``output_dir`` also receives ``sample_tmscores.txt`` (one score per line) and ``sample_alignment.npz``."""
     import warnings
 
     from .synthetic import NoiseSource, batch_to
+    align_ref = _alignment_reference(data, align_to) if align_to is not None else None      # refuses on the host data alone
     spec = redesign if redesign is not None else getattr(model, "redesign", None)
     if spec is not None and spec.needs_structure:
         check_complex_structure(data)
@@ -437,6 +478,7 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         spec = spec.to(device)                  # a positions mask is uploaded once, not per batch
     positions, logits = [], []
     first_batch = None
+    on_device = []                              # align_to: the samples stay on the device until they are scored
     for start in range(0, num_samples, batch_size):
         idx = list(range(start, min(start + batch_size, num_samples)))
         batch = collate_fn([data] * len(idx))
@@ -444,12 +486,35 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         pos, lg = model.sample(batch, sources=[NoiseSource(seed, k) for k in idx], redesign=spec)
         if first_batch is None:
             first_batch = batch                 # sample() prepared it in place: it carries the mask that was used
-        positions.append(pos.cpu())
+        if align_to is not None:
+            on_device.append(pos)
+        else:
+            positions.append(pos.cpu())
         logits.append(lg.cpu())
     # every sample of the complex shares the mask: read from the first prepared batch, after the loop (no synchronisation inside it)
     used_mask = first_batch["residue_inv_extra_mask"][0].cpu().numpy() if spec is not None and first_batch is not None else None
-    positions, logits = torch.cat(positions).numpy(), torch.cat(logits).numpy()
     na, nr = int(data["num_atoms"]), int(data["num_residues"])
+    alignment = None
+    if align_to is not None:
+        from . import align as AL
+        pos = torch.cat(on_device).float()
+        n = pos.shape[1]
+        ca_mask = torch.zeros(n)
+        ca_mask[na: na + nr] = (torch.as_tensor(data["residue_atom_mask"])[:, 1] > 0.5).float()
+        ca_mask = ca_mask.to(device)
+        if align_ref is None:
+            warnings.warn("Using the first sample as a reference. The resulting structures may be mirror images.", UserWarning)
+            ref = pos[0].clone()
+        else:
+            ref = torch.zeros(n, 3)
+            ref[na: na + nr] = torch.from_numpy(align_ref)
+            ref = ref.to(device)
+        fit = AL.superimpose(pos, ref, ca_mask, mirror=mirror)
+        div = AL.diversity(pos, ca_mask, mirror=mirror)
+        positions = [AL.apply(pos, fit.rotation, fit.translation).cpu()]
+        alignment = {"tmscore": fit.tm.cpu().numpy(), "rmsd": fit.rmsd.cpu().numpy(), "mirrored": fit.mirrored.cpu().numpy(),
+                     "rotation": fit.rotation.cpu().numpy(), "translation": fit.translation.cpu().numpy(), "diversity": float(div.cpu())}
+    positions, logits = torch.cat(positions).numpy(), torch.cat(logits).numpy()
     template = Protein(np.asarray(data["residue_chain_index"]), np.asarray(data["residue_index"]),
                        np.asarray(data["residue_type"]), np.asarray(data["residue_atom_pos"], dtype=np.float32),
                        np.asarray(data["residue_atom_mask"], dtype=np.float32))
@@ -470,6 +535,10 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         np.save(out / "sample_ligand_pos.npy", np.stack(ligands))
         if used_mask is not None:
             np.save(out / "sample_redesign_mask.npy", used_mask)
-    if spec is not None:
-        return positions, logits, proteins, ligands, used_mask
-    return positions, logits, proteins, ligands
+        if alignment is not None:
+            with open(out / "sample_tmscores.txt", "w") as f:
+                for tmscore in alignment["tmscore"]:
+                    f.write(str(float(tmscore)) + "\n")
+            np.savez(out / "sample_alignment.npz", **alignment)
+    result = (positions, logits, proteins, ligands) + ((used_mask,) if spec is not None else ())
+    return result + ((alignment,) if alignment is not None else ())

@@ -1,0 +1,187 @@
+"""CPU: the yardstick of the alignment tests (tests/align_ref.py) on planted cases, the header / build / export list of
+libprd_align.so, and the ``align_to`` argument of pipeline.generate_samples as far as it goes without a GPU."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import align_ref as AR
+from conftest import ROOT
+from protein_redesign_amd import _lib, build
+from protein_redesign_amd import pipeline as PL
+from protein_redesign_amd.synthetic import synthetic_sample
+from test_binding_cpu import Recorder, exported
+
+LENGTHS = [3, 4, 5, 21, 22, 63, 64, 65, 130, 257, 1025]
+HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
+
+
+def cases(L):
+    """core fractions per length: at L = 3, 4 only the fully rigid case is meaningful"""
+    return [1.0] if L < 5 else [1.0, 0.6, 0.35]
+
+
+@pytest.mark.parametrize("L", LENGTHS)
+def test_reference_search_recovers_the_planted_transform(L):
+    rng = np.random.default_rng(1000 + L)
+    for frac in cases(L):
+        x, y, R0, t0, core = AR.planted(rng, L, frac)
+        got = AR.superimpose(x, y, mirror=False)
+        R, t = got["rotation"], got["translation"]
+        assert got["tm"] >= AR.tm_of(x, y, R0, t0) - 1e-4, (L, frac)
+        assert abs(got["tm"] - AR.tm_of(x, y, R, t)) < 1e-12 and abs(got["rmsd"] - AR.rmsd_of(x, y, R, t)) < 1e-12
+        assert np.abs(R.T @ R - np.eye(3)).max() < 1e-12 and abs(np.linalg.det(R) - 1.0) < 1e-12
+        Rk, tk = AR.kabsch(x, y)
+        assert got["tm"] >= AR.tm_of(x, y, Rk, tk) - 1e-12          # the first seed is the whole-set fit
+        if frac < 1.0 and L >= 21:
+            assert AR.tm_of(x, y, Rk, tk) < got["tm"]                # the search is really exercised
+        assert AR.superimpose(x, y, mirror=False, mode="rmsd")["rmsd"] <= got["rmsd"] + 1e-12
+
+
+@pytest.mark.parametrize("L", [63, 130])
+def test_reference_mirror(L):
+    rng = np.random.default_rng(2000 + L)
+    x, y, R0, t0, _ = AR.planted(rng, L, 1.0, mirrored=True)
+    on, off = AR.superimpose(x, y, mirror=True), AR.superimpose(x, y, mirror=False)
+    assert on["mirrored"] == 1 and abs(np.linalg.det(on["rotation"]) + 1.0) < 1e-12 and on["tm"] >= AR.tm_of(x, y, R0, t0) - 1e-4
+    assert off["mirrored"] == 0 and on["tm"] - off["tm"] > 0.3
+    x, y, *_ = AR.planted(rng, L, 1.0)
+    assert AR.superimpose(x, y, mirror=True)["mirrored"] == 0
+
+
+def test_reference_seeds_and_short_chains():
+    assert AR.seeds(3) == [(0, 3)] and AR.seeds(4) == [(0, 4), (0, 3), (1, 3)]
+    assert AR.seeds(5) == [(0, 5), (0, 4), (1, 4), (0, 3), (1, 3), (2, 3)]
+    assert AR.seeds(22)[:6] == [(0, 22), (0, 11), (5, 11), (10, 11), (11, 11), (0, 5)] and min(Lf for _, Lf in AR.seeds(22)) == 4
+    s = AR.seeds(320)
+    assert [Lf for _, Lf in s if _ == 0] == [320, 160, 80, 40, 20, 10, 5, 4] and all(0 <= a and a + Lf <= 320 for a, Lf in s)
+    assert AR.superimpose(np.zeros((2, 3)), np.ones((2, 3))) == dict(tm=0.0, rmsd=0.0, rotation=pytest.approx(np.eye(3)),
+                                                                      translation=pytest.approx(np.zeros(3)), mirrored=0)
+    assert AR.d0_of(21) == 0.5 and abs(AR.d0_of(22) - (1.24 * 7 ** (1 / 3) - 1.8)) < 1e-12
+
+
+# ---- header, build, export list ---------------------------------------------------------------------------------------------------
+
+def header_entries():
+    with open(os.path.join(ROOT, "include", "prd_align.h")) as f:
+        return _lib.parse_header(f.read())
+
+
+def test_header_parses_with_the_derived_binding():
+    e = header_entries()
+    assert sorted(e) == ["prd_align_apply", "prd_align_superimpose", "prd_align_version", "prd_align_workspace_bytes"]
+    assert all(x.inject is None for x in e.values())            # no parameter is an injected word
+    assert e["prd_align_workspace_bytes"].restype is _lib.cz and len(e["prd_align_superimpose"].argtypes) == 21
+    from protein_redesign_amd import align
+    assert align.ENTRIES == e
+    assert not set(e) & set(_lib.ENTRIES)                       # nothing of it is part of the denoiser ABI
+
+
+@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
+def test_build_align_compiles_exports_the_header_and_is_incremental(monkeypatch):
+    lib = build.build_align(verbose=False)
+    assert lib == build.LIB_ALIGN == os.path.join(ROOT, "protein_redesign_amd", "libprd_align.so") and os.path.exists(lib)
+    assert exported(lib) == set(header_entries())
+    rec = Recorder(execute=True)
+    rec.install(monkeypatch)
+    assert build.build_align(verbose=False) == lib
+    assert rec.cmds == []                                       # a second build starts no compiler
+
+
+def test_build_issues_the_commands_it_issued_before(monkeypatch):
+    """build() knows nothing of the new library; build_align() is the same routine on the one source with the committed flags"""
+    monkeypatch.delenv("HIPCC", raising=False)
+    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
+    rec = Recorder(execute=False)
+    rec.install(monkeypatch)
+    build.build(verbose=False)
+    assert len(rec.cmds) == len(build.SOURCES) + 1 and not any("align" in t for c in rec.cmds for t in c)
+    assert [c[-3] for c in rec.cmds[:-1]] == ["{ROOT}/protein_redesign_amd/csrc/" + s for s in build.SOURCES]
+    shipped = rec.cmds[0]
+    rec.cmds = []
+    build.build_align(verbose=False)
+    src, obj = "{ROOT}/protein_redesign_amd/csrc/prd_align.hip", "{ROOT}/protein_redesign_amd/csrc/prd_align.o"
+    assert rec.cmds == [shipped[:-3] + [src, "-o", obj],
+                        shipped[:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_align.so", obj]]
+    assert build.SOURCES == ["prd_gemm.hip", "prd_pair.hip", "prd_tri.hip", "prd_tri2.hip", "prd_bwd.hip", "prd_spa.hip", "prd_tri_heads.hip",
+                             "prd_tri_heads_bwd.hip", "prd_mask.hip"] and sorted(build.VARIANTS) == ["ab", "asan", "shipped", "timing"]
+
+
+@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
+def test_resources_of_the_new_kernels_are_reported_apart():
+    mine = build.resource_usage(sources=build.ALIGN_SOURCES)
+    assert sorted(mine) == ["align_apply_kernel", "align_compact_kernel", "align_finalize_kernel", "align_search_kernel"]
+    assert all(u["scratch"] == 0 for u in mine.values())
+    assert mine["align_search_kernel"]["occupancy"] >= 2        # 8 waves per workgroup, one workgroup per CU at the least
+    assert not set(mine) & set(build.resource_usage())          # the denoiser library's table is what it was
+
+
+def test_host_argument_checks_of_the_python_side():
+    from protein_redesign_amd import align
+    x, m = torch.zeros(2, 5, 3), torch.ones(5)
+    with pytest.raises(RuntimeError, match="GPU only"):
+        align.superimpose(x, x[0], m)
+    with pytest.raises(ValueError, match="float32"):
+        align.superimpose(x.double(), x[0], m)
+    with pytest.raises(ValueError, match=r"\[K,N,3\]"):
+        align.superimpose(torch.zeros(5, 3), x[0], m)
+    with pytest.raises(ValueError, match="mode"):
+        align._run((x, 15, 3), None, m, 2, 2, 5, align.PAIRS_SELF, "gdt", True)
+    with pytest.raises(ValueError, match="4096"):
+        align._run((x, 15, 3), None, m, 2, 2, 4097, align.PAIRS_SELF, "tm", True)
+
+
+# ---- pipeline.generate_samples(align_to=...) ---------------------------------------------------------------------------------------
+
+class _NoDevice:
+    def __getattr__(self, name):
+        raise AssertionError(f"the model was touched ({name}) before the input was checked")
+
+
+class _Stub:
+    """a model whose samples are a function of the keyed noise source alone"""
+    device = torch.device("cpu")
+
+    def sample(self, batch, sources, redesign=None):
+        n = batch["atom_mask"].shape[1]
+        return (torch.stack([torch.randn(n, 3, generator=s.g) for s in sources]), torch.stack([torch.randn(n, 21, generator=s.g) for s in sources]))
+
+
+def test_align_to_input_is_refused_without_coordinates_before_the_model_is_touched():
+    lig = {k: v for k, v in synthetic_sample(5, 9, esm_dim=16, seed=8).items() if k.startswith(("atom_", "bond_")) or k == "num_atoms"}
+    data = PL.protein_to_data(PL.protein_from_sequence("ACDEFGHIK"), **lig)
+    with pytest.raises(ValueError, match="coordinates"):
+        PL.generate_samples(_NoDevice(), data, num_samples=2, align_to="input")
+    full = synthetic_sample(5, 9, esm_dim=16, seed=8)
+    with pytest.raises(ValueError, match="C-alpha"):
+        PL.generate_samples(_NoDevice(), dict(full, residue_atom_mask=torch.zeros(9, 37)), num_samples=1, align_to="input")
+
+
+def test_unknown_align_to_raises():
+    full = synthetic_sample(5, 9, esm_dim=16, seed=8)
+    with pytest.raises(ValueError, match="align_to"):
+        PL.generate_samples(_NoDevice(), full, num_samples=1, align_to="reference")
+    with pytest.raises(ValueError, match="9 residues"):
+        PL.generate_samples(_NoDevice(), full, num_samples=1, align_to=np.zeros((8, 3)))
+    with pytest.raises(ValueError, match="9 residues"):
+        PL.generate_samples(_NoDevice(), full, num_samples=1, align_to=PL.protein_from_sequence("ACD"))
+
+
+def test_align_to_none_takes_the_old_path(tmp_path, monkeypatch):
+    import warnings
+    from protein_redesign_amd import align
+    for name in ("superimpose", "pairwise", "apply", "lib"):
+        monkeypatch.setattr(align, name, lambda *a, **k: (_ for _ in ()).throw(AssertionError("the alignment ran")))
+    data = synthetic_sample(5, 9, esm_dim=16, seed=8)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)
+        out = PL.generate_samples(_Stub(), data, num_samples=3, batch_size=2, seed=1, output_dir=tmp_path)
+    assert len(out) == 4
+    pos, logits, proteins, ligands = out
+    from protein_redesign_amd.synthetic import NoiseSource
+    want = torch.stack([torch.randn(14, 3, generator=NoiseSource(1, k).g) for k in range(3)]).numpy()
+    assert np.array_equal(pos, want) and logits.shape == (3, 14, 21)
+    assert np.array_equal(proteins[2].atom_pos[:, 1], want[2, 5:14]) and np.array_equal(ligands[1], want[1, :5])
+    assert sorted(os.listdir(tmp_path)) == ["sample_ligand_pos.npy", "sample_protein.pdb"]
