@@ -512,7 +512,12 @@ AlignPlan align_plan(int S, int R, int N, int pairs, int mode, int mirror) {
     P.off_planes = AL_HDR * sizeof(int);
     P.off_rec = P.off_planes + (size_t)P.nstruct * 3 * N * sizeof(float);
     P.off_rec = (P.off_rec + 15) & ~(size_t)15;
-    P.bytes = P.off_rec + (size_t)P.npairs * P.nm * P.G * AL_REC * sizeof(float);
+    // room for the records of 4-wave workgroups at every N: G halves where the workgroups go from 4 to 8 waves (N = 1025), and a
+    // workspace sized for the longest row of a run has to do for every shorter one
+    const int per4 = 4 * AL_SEEDS_PER_WAVE;
+    int Ga = (kmax + per4 - 1) / per4;
+    Ga = Ga > AL_MAX_G ? AL_MAX_G : Ga;
+    P.bytes = P.off_rec + (size_t)P.npairs * P.nm * Ga * AL_REC * sizeof(float);
     P.bytes = P.bytes ? P.bytes : 16;
     P.ok = 1;
     return P;
@@ -547,14 +552,17 @@ extern "C" int prd_align_superimpose(float* tm, float* rmsd, float* rot, float* 
     float* planes = reinterpret_cast<float*>(static_cast<char*>(ws) + P.off_planes);
     float* rec = reinterpret_cast<float*>(static_cast<char*>(ws) + P.off_rec);
 
+    const size_t lds = (size_t)6 * N * sizeof(float);
+    if (P.npairs > 0 && lds > 48 * 1024) {              // before anything is enqueued: a refusal leaves nothing launched
+        const hipError_t ea = hipFuncSetAttribute((const void*)align_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  6 * PRD_ALIGN_MAX_N * (int)sizeof(float));
+        if (ea != hipSuccess) return (int)ea;
+    }
     hipLaunchKernelGGL(align_compact_kernel, dim3(P.nstruct), dim3(AL_COMPACT_WG), 0, stream, planes, hdr, x, x_struct_stride, x_row_stride,
                        self ? x : y, self ? x_struct_stride : y_struct_stride, self ? x_row_stride : y_row_stride, mask, S, N);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     if (P.npairs > 0) {
-        const size_t lds = (size_t)6 * N * sizeof(float);
-        if (lds > 48 * 1024)
-            (void)hipFuncSetAttribute((const void*)align_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 6 * PRD_ALIGN_MAX_N * (int)sizeof(float));
         hipLaunchKernelGGL(align_search_kernel, dim3((unsigned)(P.npairs * P.nm), P.G), dim3(64 * P.nw), lds, stream, rec, planes, hdr, S, R, N,
                            self ? 1 : 0, mode, P.nm, P.G);
         e = hipGetLastError();

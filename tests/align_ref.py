@@ -55,13 +55,17 @@ def seeds(L):
     return out
 
 
-def tm_search(x, y):
-    """(tm, R, t) of the search on the rows given (all of them count: pass compacted, masked coordinates)"""
+def tm_search(x, y, seed_filter=None, with_seed=False):
+    """(tm, R, t) of the search on the rows given (all of them count: pass compacted, masked coordinates).  ``seed_filter``: a
+    predicate on the seed index (position in ``seeds(L)``); seeds it rejects are left out -- the tests' model of a search that skips
+    seeds.  ``with_seed``: also return the index of the winning seed (the lowest one among equal scores)."""
     L = len(x)
     d0 = d0_of(L)
     d0s = min(max(d0, 4.5), 8.0)
-    best = (-1.0, None, None)
-    for start, Lf in seeds(L):
+    best = (-1.0, None, None, -1)
+    for k, (start, Lf) in enumerate(seeds(L)):
+        if seed_filter is not None and not seed_filter(k):
+            continue
         sub = np.zeros(L, bool)
         sub[start:start + Lf] = True
         for it in range(20):
@@ -69,7 +73,7 @@ def tm_search(x, y):
             d = dist(x, y, R, t)
             tm = float((1.0 / (1.0 + (d / d0) ** 2)).sum() / L)
             if tm > best[0]:
-                best = (tm, R, t)
+                best = (tm, R, t, k)
             cut = d0s - 1.0 if it == 0 else d0s + 1.0
             while (d < cut).sum() < 3:
                 cut += 0.5
@@ -77,7 +81,7 @@ def tm_search(x, y):
             if np.array_equal(new, sub):
                 break
             sub = new
-    return best
+    return best if with_seed else best[:3]
 
 
 def superimpose(x, y, mirror=True, mode="tm"):
@@ -135,3 +139,28 @@ def planted(rng, L, core_fraction, mirrored=False, noise=0.3):
     xm = x @ MIRROR if mirrored else x
     y[core] = (t0 + xm @ R0 + noise * rng.normal(size=(L, 3)))[core]
     return x, y, (MIRROR @ R0 if mirrored else R0), t0, core
+
+
+def core3_case(L, p):
+    """(x, y) float32-rounded [L,3]: two unrelated chains, y moved 20 to 30 Angstrom away, except that y[p:p+3] is the exact image of
+    x[p:p+3] under a random rigid motion -- a core that only a seed lying on it can find"""
+    rng = np.random.default_rng(900 + 100 * L + p)
+    x, y = chain(rng, L), chain(rng, L)
+    u = rng.normal(size=3)
+    y += u / np.linalg.norm(u) * rng.uniform(20.0, 30.0)
+    y[p:p + 3] = rng.uniform(-8.0, 8.0, size=3) + x[p:p + 3] @ random_rotation(rng)
+    return x.astype(np.float32).astype(np.float64), y.astype(np.float32).astype(np.float64)
+
+
+def decisive_cases(lengths=(12, 20, 21), drop=1e-3):
+    """the core3_case's in which ONE seed decides: the search without its own winning seed ends at least ``drop`` lower.
+    [dict(L, p, x, y, tm, seed, tm_without)]"""
+    out = []
+    for L in lengths:
+        for p in range(L - 2):
+            x, y = core3_case(L, p)
+            tm, _, _, k = tm_search(x, y, with_seed=True)
+            without = tm_search(x, y, seed_filter=lambda j: j != k)[0]
+            if tm - without >= drop:
+                out.append(dict(L=L, p=p, x=x, y=y, tm=tm, seed=k, tm_without=without))
+    return out

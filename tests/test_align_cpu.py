@@ -62,6 +62,27 @@ def test_reference_seeds_and_short_chains():
     assert AR.d0_of(21) == 0.5 and abs(AR.d0_of(22) - (1.24 * 7 ** (1 / 3) - 1.8)) < 1e-12
 
 
+def test_seed_filter_leaves_the_default_search_alone_and_decisive_seeds_exist():
+    """The condition tests/test_align_range.py relies on, without a GPU: among the planted 3-residue cores (AR.core3_case, L = 12, 20,
+    21) there are at least 8 in which the float64 search drops by 1e-3 or more once its own winning seed is left out, with at least 5
+    distinct winning seeds.  A later change of the yardstick cannot hollow the device test out without failing here."""
+    rng = np.random.default_rng(3000)
+    x, y, *_ = AR.planted(rng, 21, 0.35)
+    full = AR.tm_search(x, y)
+    same = AR.tm_search(x, y, seed_filter=lambda k: True, with_seed=True)
+    assert len(full) == 3 and full[0] == same[0] and np.array_equal(full[1], same[1]) and 0 <= same[3] < len(AR.seeds(21))
+    assert AR.tm_search(x, y, seed_filter=lambda k: k == 0)[0] == pytest.approx(AR.tm_of(x, y, *AR.kabsch(x, y)), abs=1e-12) or \
+        AR.tm_search(x, y, seed_filter=lambda k: k == 0)[0] > AR.tm_of(x, y, *AR.kabsch(x, y))     # seed 0, round 0 is the Kabsch fit
+    cases = AR.decisive_cases()
+    seeds = {c["seed"] for c in cases}
+    assert len(cases) >= 8 and len(seeds) >= 5, (len(cases), sorted(seeds))
+    for c in cases:
+        assert c["tm"] - c["tm_without"] >= 1e-3 and np.abs(c["x"]).max() < 100.0 and np.abs(c["y"]).max() < 100.0
+        start, Lf = AR.seeds(c["L"])[c["seed"]]
+        assert AR.tm_search(c["x"], c["y"], seed_filter=lambda k: k == c["seed"])[0] == c["tm"]     # that seed alone reaches it
+        assert np.array_equal(c["x"], c["x"].astype(np.float32)) and Lf <= c["L"]
+
+
 # ---- header, build, export list ---------------------------------------------------------------------------------------------------
 
 def header_entries():
@@ -116,6 +137,27 @@ def test_resources_of_the_new_kernels_are_reported_apart():
     assert all(u["scratch"] == 0 for u in mine.values())
     assert mine["align_search_kernel"]["occupancy"] >= 2        # 8 waves per workgroup, one workgroup per CU at the least
     assert not set(mine) & set(build.resource_usage())          # the denoiser library's table is what it was
+
+
+@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
+def test_workspace_bytes_refusals_growth_and_lower_bound():
+    """prd_align_workspace_bytes is host code: 0 for what prd_align_superimpose refuses, never smaller for a longer row, and in the cross
+    mode at least the header and the (S + R) x 3 planes of N floats that the kernels index."""
+    from protein_redesign_amd import align
+    build.build_align(verbose=False)
+    ws = align.lib().prd_align_workspace_bytes
+    TM, RMSD, CROSS, SELF = align.MODES["tm"], align.MODES["rmsd"], align.PAIRS_CROSS, align.PAIRS_SELF
+    assert ws(2, 3, 4096, CROSS, TM, 1) > 0 and ws(2, 3, 4097, CROSS, TM, 1) == 0
+    assert ws(3, 3, 64, SELF, TM, 1) > 0 and ws(3, 2, 64, SELF, TM, 1) == 0 and ws(2, 3, 64, SELF, RMSD, 0) == 0
+    assert ws(2, 3, 64, CROSS, 2, 1) == 0 and ws(2, 3, 64, CROSS, -1, 1) == 0          # unknown mode
+    assert ws(2, 3, 64, 2, TM, 1) == 0 and ws(2, 3, 64, -1, TM, 1) == 0                # unknown pairs
+    assert ws(0, 3, 64, CROSS, TM, 1) == 0 and ws(2, 0, 64, CROSS, TM, 1) == 0 and ws(2, 3, 0, CROSS, TM, 1) == 0
+    for S, R, pairs, mode, mirror in ((1, 1, CROSS, TM, 1), (2, 3, CROSS, TM, 0), (2, 3, CROSS, RMSD, 1), (4, 4, SELF, TM, 1), (1, 1, SELF, TM, 1)):
+        sizes = [ws(S, R, N, pairs, mode, mirror) for N in range(3, 4097)]
+        assert all(b > 0 and b % 16 == 0 for b in sizes), (S, R, pairs, mode)
+        assert all(a <= b for a, b in zip(sizes, sizes[1:])), (S, R, pairs, mode)
+        if pairs == CROSS:
+            assert all(b >= 16 * 4 + (S + R) * 3 * N * 4 for N, b in zip(range(3, 4097), sizes)), (S, R, mode)
 
 
 def test_host_argument_checks_of_the_python_side():
