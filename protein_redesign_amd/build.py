@@ -20,6 +20,11 @@ HEADERS = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_tri2_v3_b
 LIB_ALIGN = os.path.join(HERE, "libprd_align.so")
 ALIGN_SOURCES = ["prd_align.hip"]
 PRD_ALIGN_H = os.path.join(os.path.dirname(HERE), "include", "prd_align.h")
+# libprd_tmalign.so (include/prd_tmalign.h): structural alignment of samples to a reference of another length -- a third library, so
+# that libprd_align.so, its header and its recorded command lines stay what they are; same flags, same compile routine
+LIB_TMALIGN = os.path.join(HERE, "libprd_tmalign.so")
+TMALIGN_SOURCES = ["prd_tmalign.hip"]
+PRD_TMALIGN_H = os.path.join(os.path.dirname(HERE), "include", "prd_tmalign.h")
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -35,6 +40,7 @@ VARIANTS = {
 
 
 ALIGN = Variant(VARIANTS["shipped"].cflags, [], CSRC, LIB_ALIGN, None)       # built from ALIGN_SOURCES; not a variant of libprd_hip.so
+TMALIGN = Variant(VARIANTS["shipped"].cflags, [], CSRC, LIB_TMALIGN, None)   # built from TMALIGN_SOURCES
 
 RESOURCE_JSON = os.path.join(CSRC, "resource_usage.json")     # per kernel: VGPRs, AGPRs, SGPRs, scratch bytes / lane, occupancy, LDS
 
@@ -84,7 +90,7 @@ def _hipcc():
 
 def _headers(src):
     """the headers an object of ``src`` depends on"""
-    return [PRD_ALIGN_H] if src in ALIGN_SOURCES else HEADERS
+    return [PRD_ALIGN_H] if src in ALIGN_SOURCES else [PRD_TMALIGN_H] if src in TMALIGN_SOURCES else HEADERS
 
 
 def _stamp(src):
@@ -188,6 +194,12 @@ def build_align(force: bool = False, verbose: bool = True) -> str:
     return _build(ALIGN, ALIGN_SOURCES, force, verbose)
 
 
+def build_tmalign(force: bool = False, verbose: bool = True) -> str:
+    """libprd_tmalign.so (include/prd_tmalign.h, protein_redesign_amd/tmalign.py): the one source csrc/prd_tmalign.hip with the
+    committed FLAGS.  Neither ``build()`` nor ``build_align()`` compiles it."""
+    return _build(TMALIGN, TMALIGN_SOURCES, force, verbose)
+
+
 def build_asan(verbose: bool = True) -> str:
     """Host-side AddressSanitizer build: libprd_hip_asan.so with the HOST code of every source instrumented
     (-fsanitize=address; device code is compiled as usual: -fno-gpu-sanitize) and the argument-validation driver
@@ -226,8 +238,12 @@ if __name__ == "__main__":
     if "--align" in sys.argv:
         print(build_align(force="--force" in sys.argv))
         sys.exit(0)
+    if "--tmalign" in sys.argv:
+        print(build_tmalign(force="--force" in sys.argv))
+        sys.exit(0)
     if "--resources" in sys.argv:
-        for name, u in sorted({**resource_usage(verbose=True), **resource_usage(verbose=True, sources=ALIGN_SOURCES)}.items()):
+        for name, u in (sorted({**resource_usage(verbose=True), **resource_usage(verbose=True, sources=ALIGN_SOURCES)}.items())
+                        + sorted(resource_usage(verbose=True, sources=TMALIGN_SOURCES).items())):
             print(f"{u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}")
         sys.exit(0)
     if "--asan" in sys.argv:

@@ -434,9 +434,36 @@ def _alignment_reference(data: Mapping[str, Any], align_to) -> Optional[np.ndarr
     return ref
 
 
+def _structural_reference(align_to):
+    """The [m,3] C-alpha coordinates that ``generate_samples(align_to=..., correspondence="structure")`` aligns to by structure: the
+    residues of a ``Protein`` whose C-alpha is marked in ``atom_mask[:,1]``, or the rows of an ``[m,3]`` array.  From host data alone;
+    ValueError for a request that cannot be served."""
+    from .tmalign import MAX_N
+    if isinstance(align_to, str) or align_to is None:
+        raise ValueError(f"correspondence='structure' needs a reference structure in align_to (a Protein or an [m,3] array), got {align_to!r}: "
+                         "the correspondence to 'input' and to 'first' is known, use correspondence='index'")
+    if isinstance(align_to, Protein):
+        ca = np.asarray(align_to.atom_mask)[:, 1] > 0.5
+        if int(ca.sum()) < 5:
+            raise ValueError(f"align_to: the reference has {int(ca.sum())} residues with a C-alpha marked in atom_mask[:,1], "
+                             "an alignment by structure needs at least 5")
+        ref = np.asarray(align_to.atom_pos, dtype=np.float32)[:, 1]
+    else:
+        ref = np.asarray(align_to, dtype=np.float32)
+        if ref.ndim != 2 or ref.shape[1] != 3 or ref.shape[0] < 5:
+            raise ValueError(f"align_to: the reference has shape {ref.shape}, an [m,3] array of at least 5 C-alpha coordinates is expected")
+        ca = np.ones(ref.shape[0], bool)
+    if ref.shape[0] > MAX_N:
+        raise ValueError(f"align_to: the reference has {ref.shape[0]} residues, an alignment by structure takes at most {MAX_N} (PRD_TMALIGN_MAX_N)")
+    if not bool((ref[ca] != 0).any()):
+        raise ValueError("align_to: the C-alpha coordinates of the reference are all zero (a protein built from its sequence alone?)")
+    return ref, ca
+
+
 @torch.inference_mode()
 def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_size: int = 1, seed: int = 0,
-                     output_dir: Optional[Union[str, Path]] = None, redesign=None, align_to=None, mirror: bool = True):
+                     output_dir: Optional[Union[str, Path]] = None, redesign=None, align_to=None, mirror: bool = True,
+                     correspondence: str = "index"):
     """Draw ``num_samples`` samples of one featurised complex ``data`` (the dict of ligand_to_data ∪ protein_to_data).
 
     Returns (positions [S,N,3] in Angstrom, logits [S,N,21], proteins, ligand_positions).  With ``output_dir`` the CA
@@ -465,11 +492,29 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     the ligand atoms -- so ``positions``, ``proteins`` and ``ligand_positions`` come back in the reference's frame.  The return
     value gains one trailing ``dict``: ``tmscore`` [S], ``rmsd`` [S], ``mirrored`` [S], ``rotation`` [S,3,3], ``translation`` [S,3]
     (``reference ~ translation + sample @ rotation``) and ``diversity``, the mean pairwise TM-score of the S samples among themselves (a
-    float; NaN for S = 1).  ``output_dir`` also receives ``sample_tmscores.txt`` (one score per line) and ``sample_alignment.npz``."""
+    float; NaN for S = 1).  ``output_dir`` also receives ``sample_tmscores.txt`` (one score per line) and ``sample_alignment.npz``.
+
+    ``correspondence`` (default ``"index"``: residue i of the sample against residue i of the reference, everything above, a reference
+    of another length is refused): ``"structure"`` aligns to a reference of ANY length -- a ``Protein`` (its residues with a C-alpha
+    marked in ``atom_mask[:,1]``) or an ``[m,3]`` array, m <= 2048 -- by structure, as TM-align does, with
+    ``protein_redesign_amd.tmalign`` on the device; ``"input"`` and ``"first"`` are refused (their correspondence is known), so are,
+    before the model is touched, a reference with fewer than 5 C-alphas, all-zero coordinates or more than 2048 residues.  The scores
+    are then TM-align's: ``tmscore`` is normalised by the reference and ``rmsd`` runs over the aligned pairs; the dict and
+    ``sample_alignment.npz`` gain ``n_aligned`` [S] and ``mapping`` [S,nr] (the residue index into the reference aligned to residue
+    i of the complex, -1 for none)."""
     import warnings
 
     from .synthetic import NoiseSource, batch_to
-    align_ref = _alignment_reference(data, align_to) if align_to is not None else None      # refuses on the host data alone
+    if correspondence not in ("index", "structure"):
+        raise ValueError(f"correspondence must be 'index' or 'structure', got {correspondence!r}")
+    struct_ref = _structural_reference(align_to) if correspondence == "structure" else None  # refuses on the host data alone
+    if struct_ref is not None:
+        from .tmalign import MAX_N
+        rows = int(data["num_atoms"]) + int(data["num_residues"])
+        if rows > MAX_N:                        # the sample side of the alignment: refused now, not after the samples are drawn
+            raise ValueError(f"correspondence='structure': the complex has {rows} rows (ligand atoms + residues), an alignment by "
+                             f"structure takes at most {MAX_N} (PRD_TMALIGN_MAX_N)")
+    align_ref = _alignment_reference(data, align_to) if align_to is not None and struct_ref is None else None      # likewise
     spec = redesign if redesign is not None else getattr(model, "redesign", None)
     if spec is not None and spec.needs_structure:
         check_complex_structure(data)
@@ -502,18 +547,26 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         ca_mask = torch.zeros(n)
         ca_mask[na: na + nr] = (torch.as_tensor(data["residue_atom_mask"])[:, 1] > 0.5).float()
         ca_mask = ca_mask.to(device)
-        if align_ref is None:
-            warnings.warn("Using the first sample as a reference. The resulting structures may be mirror images.", UserWarning)
-            ref = pos[0].clone()
+        if struct_ref is not None:
+            from . import tmalign as TM
+            fit = TM.align(pos, torch.from_numpy(struct_ref[0]).to(device), ca_mask, torch.from_numpy(struct_ref[1].astype(np.float32)).to(device),
+                           mirror=mirror)
         else:
-            ref = torch.zeros(n, 3)
-            ref[na: na + nr] = torch.from_numpy(align_ref)
-            ref = ref.to(device)
-        fit = AL.superimpose(pos, ref, ca_mask, mirror=mirror)
+            if align_ref is None:
+                warnings.warn("Using the first sample as a reference. The resulting structures may be mirror images.", UserWarning)
+                ref = pos[0].clone()
+            else:
+                ref = torch.zeros(n, 3)
+                ref[na: na + nr] = torch.from_numpy(align_ref)
+                ref = ref.to(device)
+            fit = AL.superimpose(pos, ref, ca_mask, mirror=mirror)
         div = AL.diversity(pos, ca_mask, mirror=mirror)
         positions = [AL.apply(pos, fit.rotation, fit.translation).cpu()]
         alignment = {"tmscore": fit.tm.cpu().numpy(), "rmsd": fit.rmsd.cpu().numpy(), "mirrored": fit.mirrored.cpu().numpy(),
                      "rotation": fit.rotation.cpu().numpy(), "translation": fit.translation.cpu().numpy(), "diversity": float(div.cpu())}
+        if struct_ref is not None:
+            alignment["n_aligned"] = fit.n_aligned.cpu().numpy()
+            alignment["mapping"] = fit.mapping[:, na: na + nr].cpu().numpy()         # rows of the reference ARE its residue indices
     positions, logits = torch.cat(positions).numpy(), torch.cat(logits).numpy()
     template = Protein(np.asarray(data["residue_chain_index"]), np.asarray(data["residue_index"]),
                        np.asarray(data["residue_type"]), np.asarray(data["residue_atom_pos"], dtype=np.float32),
