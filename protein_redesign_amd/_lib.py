@@ -28,7 +28,7 @@ def _strip_comments(text):
     return re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
 
 
-def _declarator(decl, where):
+def _declarator(decl, where, header="include/prd_hip.h"):
     """(ctypes type, name) of one C parameter or struct member such as ``const float* bias``.  A type outside the map raises."""
     m = re.fullmatch(r"(.*?)\s*(\w+)", " ".join(decl.split()))
     ctype = m.group(1).replace(" *", "*") if m else ""
@@ -39,7 +39,7 @@ def _declarator(decl, where):
     if "*" in ctype:
         return vp, m.group(2)
     if ctype not in _SCALARS:
-        raise TypeError(f"include/prd_hip.h, {where}: no ctypes type for {decl.strip()!r}")
+        raise TypeError(f"{header}, {where}: no ctypes type for {decl.strip()!r}")
     return _SCALARS[ctype], m.group(2)
 
 
@@ -54,18 +54,24 @@ def parse_struct(text, name):
     return fields
 
 
-def parse_header(text):
+def parse_header(text, header="include/prd_hip.h"):
     """{entry point: Entry} for every ``int`` / ``size_t prd_*(...);`` prototype of the header text.  The injection rule is the
-    header's own: a parameter named ``arith`` or ``tune`` is the last one, or the last before ``stream``; elsewhere it raises."""
+    header's own: a parameter named ``arith`` or ``tune`` is the last one, or the last before ``stream``; elsewhere it raises.
+    ``header``: the name the text goes by in those messages."""
     entries = {}
     for ret, name, params in re.findall(r"^(int|size_t)\s+(prd_\w+)\s*\(([^)]*)\)\s*;", _strip_comments(text), flags=re.M):
-        decls = [] if params.strip() in ("", "void") else [_declarator(p, name) for p in params.split(",")]
+        decls = [] if params.strip() in ("", "void") else [_declarator(p, name, header) for p in params.split(",")]
         names = [n for _, n in decls]
         hits = [i for i, n in enumerate(names) if n in ("arith", "tune")]
         if len(hits) > 1 or (hits and hits[0] != len(names) - 1 and not (hits[0] == len(names) - 2 and names[-1] == "stream")):
-            raise ValueError(f"include/prd_hip.h, {name}: `arith` / `tune` must be the last parameter or the last before `stream`")
+            raise ValueError(f"{header}, {name}: `arith` / `tune` must be the last parameter or the last before `stream`")
         entries[name] = Entry([t for t, _ in decls], _SCALARS[ret], names[hits[0]] if hits else None, hits[0] if hits else None)
     return entries
+
+
+def parse_defines(text, prefix):
+    """{macro without ``prefix``: value} of the header's ``#define <prefix>NAME <integer>`` lines (``(-3)`` is an integer too)."""
+    return {n: int(v) for n, v in re.findall(r"^[ \t]*#define[ \t]+%s(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$" % re.escape(prefix), _strip_comments(text), flags=re.M)}
 
 
 def parse_tune(text):
@@ -183,6 +189,24 @@ class _Library:
         return fn
 
 
+def load_library(path, entries, version_export, version, flag=""):
+    """The C library at ``path`` with the argtypes / restype of ``entries`` (a parsed header) set on its entry points.  Raises
+    RuntimeError (never falls back) when it has not been built, or when ``version_export()`` is not the ``version`` the binding
+    was written against.  ``flag``: what ``python -m protein_redesign_amd.build`` takes to build it."""
+    how = " ".join(["python -m protein_redesign_amd.build"] + [flag] * bool(flag))
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: build it with `{how}` (hipcc --offload-arch=gfx950).  There is no CPU fallback.")
+    cdll = C.CDLL(path)
+    for name, e in entries.items():
+        fn = getattr(cdll, name)
+        fn.argtypes, fn.restype = e.argtypes, e.restype
+    got = getattr(cdll, version_export)()
+    if got != version:
+        raise RuntimeError(f"{path} reports {version_export.upper()} {got}, this binding was written against {version} "
+                           f"(the header lists what changed): rebuild with `{how}`")
+    return cdll
+
+
 _lib = None
 
 
@@ -190,17 +214,7 @@ def lib():
     """The loaded library; raises RuntimeError (never falls back) when it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: build it with `python -m protein_redesign_amd.build` "
-                "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the HIP hot path.")
-        cdll = C.CDLL(LIB_PATH)
-        for name, e in ENTRIES.items():
-            fn = getattr(cdll, name)
-            fn.argtypes, fn.restype = e.argtypes, e.restype
-        if cdll.prd_version() != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH} reports PRD_VERSION {cdll.prd_version()}, this binding was written against {ABI_VERSION} "
-                               "(include/prd_hip.h lists what changed): rebuild with `python -m protein_redesign_amd.build`")
+        cdll = load_library(LIB_PATH, ENTRIES, "prd_version", ABI_VERSION)
         mode = os.environ.get("PRD_GEMM_MODE", DEFAULT_GEMM_MODE)
         if os.environ.get("PRD_BF16X3"):                               # older spelling of PRD_GEMM_MODE=bf16x3
             mode = "bf16x3"
@@ -260,10 +274,18 @@ def row_gemm_description(b3: bool) -> str:
     return "fp32-mfma"
 
 
-def check(code: int, what: str):
+_DEFINES = parse_defines(_HEADER, "PRD_")
+
+
+def check(code: int, what: str, defines=_DEFINES, prefix: str = "PRD_", unsupported: str = None):
+    """Raise for the non-zero return ``code`` of the entry point ``what``: a RuntimeError that names the ``ERR_*`` macro of the header
+    (``defines``: its parsed #defines, ``prefix``: what parse_defines took off their names) or the hipError_t.  ``unsupported``, if
+    given: ERR_UNSUPPORTED is a limit the caller can act on, and becomes a ValueError that states it."""
     if code != 0:
-        names = {-1: "PRD_ERR_ARG", -2: "PRD_ERR_ALIGN", -3: "PRD_ERR_UNSUPPORTED", -4: "PRD_ERR_WORKSPACE"}
-        raise RuntimeError(f"{what} failed: {names.get(code, 'hipError_t ' + str(code))}")
+        name = next((n for n, v in defines.items() if n.startswith("ERR_") and v == code), None)
+        if unsupported and name == "ERR_UNSUPPORTED":
+            raise ValueError(f"{what}: {unsupported}")
+        raise RuntimeError(f"{what} failed: {prefix + name if name else 'hipError_t ' + str(code)}")
 
 
 def dptr(t, dtype=torch.float32):

@@ -5,26 +5,26 @@ correspondence is known, so what is left is the TM-score superposition search, r
 Everything runs on the current stream with no host synchronisation.  HIP only: a missing library or a CPU tensor raises."""
 from __future__ import annotations
 
-import ctypes as C
 import dataclasses
 import os
 
 import torch
 
-from ._lib import dptr, parse_header, stream
+from ._lib import check, dptr, load_library, parse_defines, parse_header, stream
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libprd_align.so")
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "prd_align.h")
 
 with open(HEADER_PATH) as _f:
-    ENTRIES = parse_header(_f.read())          # the header is the only statement of the C ABI
+    _HEADER = _f.read()                         # the header is the only statement of the C ABI and of its constants
+ENTRIES = parse_header(_HEADER, "include/prd_align.h")
+_DEFINES = parse_defines(_HEADER, "PRD_ALIGN_")
 
 ABI_VERSION = 100           # include/prd_align.h PRD_ALIGN_VERSION this binding is written against
-MAX_N = 4096                # PRD_ALIGN_MAX_N
-MODES = {"tm": 0, "rmsd": 1}
-PAIRS_CROSS, PAIRS_SELF = 0, 1
-ERR_UNSUPPORTED = -3
+MAX_N = _DEFINES["MAX_N"]
+MODES = {"tm": _DEFINES["MODE_TM"], "rmsd": _DEFINES["MODE_RMSD"]}
+PAIRS_CROSS, PAIRS_SELF = _DEFINES["PAIRS_CROSS"], _DEFINES["PAIRS_SELF"]
 
 _lib = None
 
@@ -33,26 +33,12 @@ def lib():
     """The loaded library; raises RuntimeError (never falls back) when it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -m protein_redesign_amd.build --align` "
-                               "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
-        cdll = C.CDLL(LIB_PATH)
-        for name, e in ENTRIES.items():
-            fn = getattr(cdll, name)
-            fn.argtypes, fn.restype = e.argtypes, e.restype
-        if cdll.prd_align_version() != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH} reports PRD_ALIGN_VERSION {cdll.prd_align_version()}, this binding was written against "
-                               f"{ABI_VERSION}: rebuild with `python -m protein_redesign_amd.build --align`")
-        _lib = cdll
+        _lib = load_library(LIB_PATH, ENTRIES, "prd_align_version", ABI_VERSION, "--align")
     return _lib
 
 
 def _check(code: int, what: str):
-    if code == ERR_UNSUPPORTED:
-        raise ValueError(f"{what}: at most {MAX_N} positions per structure (PRD_ALIGN_MAX_N) and 65535 structures per apply")
-    if code != 0:
-        names = {-1: "PRD_ALIGN_ERR_ARG", -4: "PRD_ALIGN_ERR_WORKSPACE"}
-        raise RuntimeError(f"{what} failed: {names.get(code, 'hipError_t ' + str(code))}")
+    check(code, what, _DEFINES, "PRD_ALIGN_", f"at most {MAX_N} positions per structure (PRD_ALIGN_MAX_N) and 65535 structures per apply")
 
 
 @dataclasses.dataclass(frozen=True)

@@ -15,16 +15,20 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 EXTRA_FLAGS = {"prd_tri2.hip": ["-fno-slp-vectorize"]}
 PRD_HIP_H = os.path.join(os.path.dirname(HERE), "include", "prd_hip.h")
 HEADERS = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_tri2_v3_body.inc"), PRD_HIP_H]      # every object depends on these
-# libprd_align.so (include/prd_align.h): superposition and TM-score of generated samples -- post-processing, not part of the denoiser
-# ABI, hence a library of its own with its own header; same flags, same compile routine
-LIB_ALIGN = os.path.join(HERE, "libprd_align.so")
-ALIGN_SOURCES = ["prd_align.hip"]
-PRD_ALIGN_H = os.path.join(os.path.dirname(HERE), "include", "prd_align.h")
-# libprd_tmalign.so (include/prd_tmalign.h): structural alignment of samples to a reference of another length -- a third library, so
-# that libprd_align.so, its header and its recorded command lines stay what they are; same flags, same compile routine
-LIB_TMALIGN = os.path.join(HERE, "libprd_tmalign.so")
-TMALIGN_SOURCES = ["prd_tmalign.hip"]
-PRD_TMALIGN_H = os.path.join(os.path.dirname(HERE), "include", "prd_tmalign.h")
+# The side libraries: post-processing of samples, not part of the denoiser ABI, hence each a library of its own with its own header, so
+# that libprd_hip.so, prd_hip.h and their recorded command lines stay what they are; same flags, same compile routine.  Per library:
+# its sources, the headers every object of it depends on, the library, and the flag of this module's command line that builds it.
+#   align    libprd_align.so (include/prd_align.h): superposition and TM-score of generated samples
+#   tmalign  libprd_tmalign.so (include/prd_tmalign.h): structural alignment of samples to a reference of another length
+# csrc/prd_superpose.h is the fit that the two share: touching it makes both stale and no object of the denoiser.
+SideLib = collections.namedtuple("SideLib", "sources headers lib flag")
+_INCLUDE, PRD_SUPERPOSE_H = os.path.join(os.path.dirname(HERE), "include"), os.path.join(CSRC, "prd_superpose.h")
+SIDE_LIBS = {
+    "align": SideLib(["prd_align.hip"], [os.path.join(_INCLUDE, "prd_align.h"), PRD_SUPERPOSE_H], os.path.join(HERE, "libprd_align.so"), "--align"),
+    "tmalign": SideLib(["prd_tmalign.hip"], [os.path.join(_INCLUDE, "prd_tmalign.h"), PRD_SUPERPOSE_H], os.path.join(HERE, "libprd_tmalign.so"), "--tmalign"),
+}
+LIB_ALIGN, ALIGN_SOURCES = SIDE_LIBS["align"].lib, SIDE_LIBS["align"].sources
+LIB_TMALIGN, TMALIGN_SOURCES = SIDE_LIBS["tmalign"].lib, SIDE_LIBS["tmalign"].sources
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -37,10 +41,6 @@ VARIANTS = {
     "timing": Variant(["-DPRD_TIMING"], [], os.path.join(CSRC, "timing"), os.path.join(HERE, "libprd_hip_timing.so"), None),
     "asan": Variant(["-g"] + _ASAN + ["-fno-omit-frame-pointer"], _ASAN, os.path.join(CSRC, "asan"), os.path.join(HERE, "libprd_hip_asan.so"), None),
 }
-
-
-ALIGN = Variant(VARIANTS["shipped"].cflags, [], CSRC, LIB_ALIGN, None)       # built from ALIGN_SOURCES; not a variant of libprd_hip.so
-TMALIGN = Variant(VARIANTS["shipped"].cflags, [], CSRC, LIB_TMALIGN, None)   # built from TMALIGN_SOURCES
 
 RESOURCE_JSON = os.path.join(CSRC, "resource_usage.json")     # per kernel: VGPRs, AGPRs, SGPRs, scratch bytes / lane, occupancy, LDS
 
@@ -90,7 +90,7 @@ def _hipcc():
 
 def _headers(src):
     """the headers an object of ``src`` depends on"""
-    return [PRD_ALIGN_H] if src in ALIGN_SOURCES else [PRD_TMALIGN_H] if src in TMALIGN_SOURCES else HEADERS
+    return next((s.headers for s in SIDE_LIBS.values() if src in s.sources), HEADERS)
 
 
 def _stamp(src):
@@ -119,7 +119,7 @@ def resource_usage(verbose: bool = False, sources=None):
     """Register / scratch / occupancy figures of every kernel of the library, as the compiler reports them for the committed flags
     (hipcc cross-compiles without a GPU).  ``build()`` writes them next to the objects; a source whose figures are missing is
     analysed here (device code only, nothing linked).  tests/test_build_resources.py holds the default-dispatch kernels of the
-    sampling step to ScratchSize == 0.  ``sources``: another list than the denoiser library's (ALIGN_SOURCES)."""
+    sampling step to ScratchSize == 0.  ``sources``: another list than the denoiser library's (that of a side library)."""
     sources = SOURCES if sources is None else sources
     have, new = _resources(), {}
     for src in sources:
@@ -188,16 +188,21 @@ def build(force: bool = False, verbose: bool = True) -> str:
     return _build(VARIANTS["shipped"], SOURCES, force, verbose)
 
 
+def build_side(name: str, force: bool = False, verbose: bool = True) -> str:
+    """The side library ``name`` of SIDE_LIBS: its sources with the committed FLAGS and the shipped variant's extras, objects beside
+    the denoiser's.  Not a variant of libprd_hip.so: ``build()`` compiles none of it, and no side library compiles another."""
+    s = SIDE_LIBS[name]
+    return _build(Variant(VARIANTS["shipped"].cflags, [], CSRC, s.lib, None), s.sources, force, verbose)
+
+
 def build_align(force: bool = False, verbose: bool = True) -> str:
-    """libprd_align.so (include/prd_align.h, protein_redesign_amd/align.py): the one source csrc/prd_align.hip with the committed
-    FLAGS.  ``build()`` does not compile it: the denoiser library and its recorded command lines stay what they are."""
-    return _build(ALIGN, ALIGN_SOURCES, force, verbose)
+    """libprd_align.so (include/prd_align.h, protein_redesign_amd/align.py)"""
+    return build_side("align", force, verbose)
 
 
 def build_tmalign(force: bool = False, verbose: bool = True) -> str:
-    """libprd_tmalign.so (include/prd_tmalign.h, protein_redesign_amd/tmalign.py): the one source csrc/prd_tmalign.hip with the
-    committed FLAGS.  Neither ``build()`` nor ``build_align()`` compiles it."""
-    return _build(TMALIGN, TMALIGN_SOURCES, force, verbose)
+    """libprd_tmalign.so (include/prd_tmalign.h, protein_redesign_amd/tmalign.py)"""
+    return build_side("tmalign", force, verbose)
 
 
 def build_asan(verbose: bool = True) -> str:
@@ -235,16 +240,14 @@ if __name__ == "__main__":
     if "--timing" in sys.argv:
         print(build_timing())
         sys.exit(0)
-    if "--align" in sys.argv:
-        print(build_align(force="--force" in sys.argv))
-        sys.exit(0)
-    if "--tmalign" in sys.argv:
-        print(build_tmalign(force="--force" in sys.argv))
-        sys.exit(0)
-    if "--resources" in sys.argv:
-        for name, u in (sorted({**resource_usage(verbose=True), **resource_usage(verbose=True, sources=ALIGN_SOURCES)}.items())
-                        + sorted(resource_usage(verbose=True, sources=TMALIGN_SOURCES).items())):
-            print(f"{u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}")
+    for side, s in SIDE_LIBS.items():
+        if s.flag in sys.argv:
+            print(build_side(side, force="--force" in sys.argv))
+            sys.exit(0)
+    if "--resources" in sys.argv:                   # the denoiser's kernels, then those of each side library
+        for sources in [SOURCES] + [s.sources for s in SIDE_LIBS.values()]:
+            for name, u in sorted(resource_usage(verbose=True, sources=sources).items()):
+                print(f"{u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}")
         sys.exit(0)
     if "--asan" in sys.argv:
         exe = build_asan()

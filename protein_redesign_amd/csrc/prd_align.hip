@@ -10,70 +10,26 @@
 //                             the search are fp32.  Every workgroup writes ONE record (its best seed) to the workspace.
 //   3. align_finalize_kernel  one wave per pair picks the best record (ties: unmirrored, then the lowest seed), evaluates tm and
 //                             rmsd in fp64 from the fp32 transform it returns, and writes the outputs.
+// The seeds, d0 and the fit itself are in prd_superpose.h, which prd_tmalign.hip includes as well.
 // One owner per output element, plain vector stores, no atomics; every loop over rounds or cut-offs is bounded.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/prd_align.h"
+#include "prd_superpose.h"
 
 namespace {
 
 #define AL_DEV __device__ __forceinline__
 
-constexpr int AL_COMPACT_WG = 256;      // threads of a compaction workgroup; each owns AL_MAX_N / 256 consecutive positions
+constexpr int AL_COMPACT_WG = SP_COMPACT_WG;    // threads of a compaction workgroup; each owns AL_OWN consecutive positions
 constexpr int AL_OWN = PRD_ALIGN_MAX_N / AL_COMPACT_WG;
-constexpr int AL_REC = 16;              // floats of a record: score, seed (bits), rot[9], trans[3], 2 unused
+constexpr int AL_REC = SP_REC;          // floats of a record; its key is the seed
 constexpr int AL_ROUNDS = 20;
 constexpr int AL_HDR = 16;              // ints at the head of the workspace; [0] = L
 constexpr int AL_MAX_WAVES = 8;         // waves of a search workgroup: 4 (N <= 1024) or 8
 constexpr int AL_SEEDS_PER_WAVE = 4;    // seeds a wave is meant to walk (sizes the second grid dimension)
 constexpr int AL_MAX_G = 1024;          // records per (pair, mirror) at most
 constexpr int AL_CUT_RAISES = 4096;     // d_cut is raised at most this often (2048 Angstrom: beyond any finite input in range)
-
-AL_DEV double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-AL_DEV float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// ---- the seeds of the search (prd_align.h, TM mode, steps 1 and 2) --------------------------------------------------------------
-// fragment lengths L, L/2, L/4, ... as long as they exceed 4, then 4 itself (TM-score's own convention: the shortest fragment is 4),
-// and for L <= 21 fragments of 3 as well: there d0 is 0.5 while d_cut is never below 3.5, so the rounds cannot shed an outlier of a
-// chain that small and the seed itself has to be able to be free of them
-__host__ __device__ inline int al_next_level(int Lf, int L) { return Lf > 4 ? (Lf / 2 > 4 ? Lf / 2 : 4) : (Lf == 4 && L <= 21 ? 3 : 0); }
-__host__ __device__ inline int al_level_count(int L, int Lf) {
-    const int step = Lf / 2 > 1 ? Lf / 2 : 1, span = L - Lf;
-    return span / step + 1 + (span % step ? 1 : 0);
-}
-__host__ __device__ inline int al_seed_count(int L) {
-    if (L < 4) return 1;
-    int K = 0;
-    for (int Lf = L; Lf >= 3; Lf = al_next_level(Lf, L)) K += al_level_count(L, Lf);
-    return K;
-}
-// seed -> (first position, length) of its fragment; seed < al_seed_count(L)
-AL_DEV void al_seed_decode(int L, int seed, int& start, int& len) {
-    start = 0;
-    len = L;
-    if (L < 4) return;
-    for (int Lf = L; Lf >= 3; Lf = al_next_level(Lf, L)) {
-        const int c = al_level_count(L, Lf);
-        if (seed < c) {
-            const int step = Lf / 2 > 1 ? Lf / 2 : 1;
-            const int s = seed * step;
-            start = s < L - Lf ? s : L - Lf;        // the last one is the last possible start
-            len = Lf;
-            return;
-        }
-        seed -= c;
-    }
-}
-
-AL_DEV double al_d0(int L) { return L > 21 ? 1.24 * cbrt((double)L - 15.0) - 1.8 : 0.5; }
 
 // pair index -> (s, r): row-major S x R, or the pairs s < r of the self mode in row order
 AL_DEV void al_pair_decode(long pair, int S, int R, int self, int& s, int& r) {
@@ -101,144 +57,11 @@ __global__ __launch_bounds__(AL_COMPACT_WG) void align_compact_kernel(float* __r
     const float* src = st < nx ? x + (long long)st * x_ss : y + (long long)(st - nx) * y_ss;
     const int rs = st < nx ? x_rs : y_rs;
     const int i0 = tid * AL_OWN;
-    int c = 0;
-    for (int i = i0; i < i0 + AL_OWN && i < N; ++i) c += mask[i] > 0.5f ? 1 : 0;
-    cnt[tid] = c;
-    __syncthreads();
-    int pos = 0, total = 0;
-    for (int j = 0; j < AL_COMPACT_WG; ++j) {
-        const int v = cnt[j];
-        pos += j < tid ? v : 0;
-        total += v;
-    }
+    int total, pos = sp_compact_start(cnt, mask, AL_OWN, N, total);
     float* dst = planes + (size_t)st * 3 * N;
-    for (int i = i0; i < i0 + AL_OWN && i < N; ++i) {
-        if (mask[i] > 0.5f) {                       // pos < total <= N
-            const float* p = src + (long long)i * rs;
-            dst[pos] = p[0];
-            dst[N + pos] = p[1];
-            dst[2 * N + pos] = p[2];
-            ++pos;
-        }
-    }
+    for (int i = i0; i < i0 + AL_OWN && i < N; ++i)
+        if (mask[i] > 0.5f) sp_put_row(dst, N, pos++, src + (long long)i * rs);     // pos < total <= N
     if (st == 0 && tid == 0) hdr[0] = total;
-}
-
-// ---- the fit -----------------------------------------------------------------------------------------------------------------------
-// One Jacobi rotation of the symmetric 4 x 4 matrix A in the (P, Q) plane, accumulated into V.  The ANGLE is computed in fp32 (hardware
-// reciprocal and reciprocal square root), the pair (c, s) is then brought back to c^2 + s^2 = 1 in fp64 (first-order correction:
-// the fp32 pair is within 1e-7 of the unit circle, what is left is 1e-14) and applied in fp64 with the exact update of A[P][Q] -- an
-// orthogonal similarity that merely does not annihilate the element completely.  The eigenvector is normalised in fp64 at the end,
-// so the orthogonality of the rotation matrix does not depend on any of this.
-template <int P, int Q>
-AL_DEV void jacobi_rotate(double (&A)[4][4], double (&V)[4][4]) {
-    const double apq = A[P][Q];
-    const float f = (float)apq;
-    if (f == 0.f) return;
-    const float th = 0.5f * (float)(A[Q][Q] - A[P][P]) * __builtin_amdgcn_rcpf(f);
-    const float t = __builtin_copysignf(1.f, th) * __builtin_amdgcn_rcpf(__builtin_fabsf(th) + __builtin_sqrtf(th * th + 1.f));
-    const float cf = __builtin_amdgcn_rsqf(t * t + 1.f), sf = t * cf;
-    if (!(cf == cf) || !(sf == sf)) return;         // a NaN angle (non-finite input) rotates nothing
-    double c = (double)cf, s = (double)sf;
-    const double k = 1.5 - 0.5 * (c * c + s * s);
-    c *= k;
-    s *= k;
-    const double app = A[P][P], aqq = A[Q][Q];
-    A[P][P] = c * c * app - 2.0 * c * s * apq + s * s * aqq;
-    A[Q][Q] = s * s * app + 2.0 * c * s * apq + c * c * aqq;
-    A[P][Q] = A[Q][P] = (c * c - s * s) * apq + c * s * (app - aqq);
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) {
-        if (k2 != P && k2 != Q) {
-            const double akp = A[k2][P], akq = A[k2][Q];
-            A[k2][P] = A[P][k2] = c * akp - s * akq;
-            A[k2][Q] = A[Q][k2] = s * akp + c * akq;
-        }
-        const double vkp = V[k2][P], vkq = V[k2][Q];
-        V[k2][P] = c * vkp - s * vkq;
-        V[k2][Q] = s * vkp + c * vkq;
-    }
-}
-
-// sums over a subset of n >= 3 positions: sx[a] = sum x_a, sy[b] = sum y_b, sxy[3 a + b] = sum x_a y_b  ->  the proper rotation and
-// translation of least squares, row-vector convention y ~ tr + x @ rot (Horn's quaternion form: the eigenvector of the largest
-// eigenvalue of a symmetric 4 x 4 matrix; rank-deficient subsets -- three points are always coplanar -- are no special case)
-AL_DEV void kabsch_from_sums(const double (&sx)[3], const double (&sy)[3], const double (&sxy)[9], double n, float (&rot)[9], float (&tr)[3]) {
-    const double inv = 1.0 / n;
-    double mx[3], my[3], M[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        mx[a] = sx[a] * inv;
-        my[a] = sy[a] * inv;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) M[a][b] = sxy[3 * a + b] - sx[a] * my[b];
-    double A[4][4], V[4][4];
-    A[0][0] = M[0][0] + M[1][1] + M[2][2];
-    A[1][1] = M[0][0] - M[1][1] - M[2][2];
-    A[2][2] = -M[0][0] + M[1][1] - M[2][2];
-    A[3][3] = -M[0][0] - M[1][1] + M[2][2];
-    A[0][1] = A[1][0] = M[1][2] - M[2][1];
-    A[0][2] = A[2][0] = M[2][0] - M[0][2];
-    A[0][3] = A[3][0] = M[0][1] - M[1][0];
-    A[1][2] = A[2][1] = M[0][1] + M[1][0];
-    A[1][3] = A[3][1] = M[2][0] + M[0][2];
-    A[2][3] = A[3][2] = M[1][2] + M[2][1];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 6; ++sweep) {
-        jacobi_rotate<0, 1>(A, V);
-        jacobi_rotate<0, 2>(A, V);
-        jacobi_rotate<0, 3>(A, V);
-        jacobi_rotate<1, 2>(A, V);
-        jacobi_rotate<1, 3>(A, V);
-        jacobi_rotate<2, 3>(A, V);
-    }
-    // the column of the largest diagonal element (selects: no dynamic register index)
-    double best = A[0][0], q[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
-#pragma unroll
-    for (int j = 1; j < 4; ++j) {
-        const bool up = A[j][j] > best;
-        best = up ? A[j][j] : best;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) q[i] = up ? V[i][j] : q[i];
-    }
-    const double qn = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    const double w = q[0] * qn, a = q[1] * qn, b = q[2] * qn, c = q[3] * qn;
-    // column convention y = Qm x; rot = Qm^T
-    double Qm[3][3];
-    Qm[0][0] = 1.0 - 2.0 * (b * b + c * c); Qm[0][1] = 2.0 * (a * b - w * c);       Qm[0][2] = 2.0 * (a * c + w * b);
-    Qm[1][0] = 2.0 * (a * b + w * c);       Qm[1][1] = 1.0 - 2.0 * (a * a + c * c); Qm[1][2] = 2.0 * (b * c - w * a);
-    Qm[2][0] = 2.0 * (a * c - w * b);       Qm[2][1] = 2.0 * (b * c + w * a);       Qm[2][2] = 1.0 - 2.0 * (a * a + b * b);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) rot[3 * i + j] = (float)Qm[j][i];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) tr[j] = (float)(my[j] - (mx[0] * Qm[j][0] + mx[1] * Qm[j][1] + mx[2] * Qm[j][2]));
-}
-
-// squared distance of position i under (rot, tr), fp32
-AL_DEV float al_d2(const float* X0, const float* X1, const float* X2, const float* Y0, const float* Y1, const float* Y2, int i,
-                   const float (&rot)[9], const float (&tr)[3]) {
-    const float x0 = X0[i], x1 = X1[i], x2 = X2[i];
-    const float e0 = (tr[0] + (x0 * rot[0] + x1 * rot[3] + x2 * rot[6])) - Y0[i];
-    const float e1 = (tr[1] + (x0 * rot[1] + x1 * rot[4] + x2 * rot[7])) - Y1[i];
-    const float e2 = (tr[2] + (x0 * rot[2] + x1 * rot[5] + x2 * rot[8])) - Y2[i];
-    return e0 * e0 + e1 * e1 + e2 * e2;
-}
-
-// keep the three smallest of (a <= b <= c) and v
-AL_DEV void keep3(float& a, float& b, float& c, float v) {
-    if (v < c) {
-        c = v;
-        if (c < b) { const float t = b; b = c; c = t; }
-        if (b < a) { const float t = a; a = b; b = t; }
-    }
 }
 
 // ---- 2. the search ---------------------------------------------------------------------------------------------------------------
@@ -268,9 +91,10 @@ __global__ __launch_bounds__(64 * AL_MAX_WAVES) void align_search_kernel(float* 
         Y2[i] = ys[2 * N + i];
     }
     __syncthreads();
+    const Coords c = {X0, X1, X2, Y0, Y1, Y2};
 
-    const int K = mode == PRD_ALIGN_MODE_RMSD ? 1 : al_seed_count(L);
-    const float d0 = (float)al_d0(L);
+    const int K = mode == PRD_ALIGN_MODE_RMSD ? 1 : sp_seed_count(L);
+    const float d0 = (float)sp_d0(L);
     const float inv_d02 = 1.f / (d0 * d0);
     const float d0s = fminf(fmaxf(d0, 4.5f), 8.f);
     const float inf = __builtin_inff();
@@ -279,12 +103,13 @@ __global__ __launch_bounds__(64 * AL_MAX_WAVES) void align_search_kernel(float* 
 
     for (int seed = blockIdx.y * nw + wave; seed < K; seed += G * nw) {     // wave-uniform
         int start, len;
-        al_seed_decode(L, seed, start, len);
+        sp_seed_decode(L, seed, start, len);
         unsigned long long mem = 0ull;                                       // bit k: position lane + 64 k is in the subset (L <= 4096)
         for (int i = lane, k = 0; i < L; i += 64, ++k) mem |= (i >= start && i < start + len) ? 1ull << k : 0ull;
         float rot[9], tr[3];
         for (int it = 0; it < AL_ROUNDS; ++it) {
-            // ---- the 15 sums of the subset, fp64
+            // ---- the 15 sums of the subset, fp64 (plain arrays, not the Sums of prd_tmalign.hip: that takes this kernel from 158 to 156
+            // registers, and its figures stay what they are: DESIGN 7.2)
             double sx[3] = {0., 0., 0.}, sy[3] = {0., 0., 0.}, sxy[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
             float cnt = 0.f;
             for (int i = lane, k = 0; i < L; i += 64, ++k) {
@@ -309,12 +134,12 @@ __global__ __launch_bounds__(64 * AL_MAX_WAVES) void align_search_kernel(float* 
             }
 #pragma unroll
             for (int a = 0; a < 9; ++a) sxy[a] = wave_sum(sxy[a]);
-            kabsch_from_sums(sx, sy, sxy, (double)cnt, rot, tr);
+            kabsch_from_sums<false>(sx, sy, sxy, (double)cnt, rot, tr);
 
             // ---- score all positions; the three smallest squared distances of the wave
             float sc = 0.f, m0 = inf, m1 = inf, m2 = inf;
             for (int i = lane; i < L; i += 64) {
-                const float d2 = al_d2(X0, X1, X2, Y0, Y1, Y2, i, rot, tr);
+                const float d2 = sp_d2(c, i, i, rot, tr);
                 sc += mode == PRD_ALIGN_MODE_RMSD ? -d2 : __builtin_amdgcn_rcpf(1.f + d2 * inv_d02);
                 keep3(m0, m1, m2, d2);
             }
@@ -341,19 +166,14 @@ __global__ __launch_bounds__(64 * AL_MAX_WAVES) void align_search_kernel(float* 
             const float cut2 = cut * cut;
             unsigned long long next = 0ull;
             for (int i = lane, k = 0; i < L; i += 64, ++k)
-                next |= al_d2(X0, X1, X2, Y0, Y1, Y2, i, rot, tr) < cut2 ? 1ull << k : 0ull;
+                next |= sp_d2(c, i, i, rot, tr) < cut2 ? 1ull << k : 0ull;
             if (!__any(next != mem)) break;
             mem = next;
         }
     }
 
     if (lane == 0) {
-        wrec[wave][0] = best;
-        wrec[wave][1] = __int_as_float(bseed);
-#pragma unroll
-        for (int a = 0; a < 9; ++a) wrec[wave][2 + a] = brot[a];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) wrec[wave][11 + a] = btr[a];
+        sp_record_write(wrec[wave], best, bseed, brot, btr);
         wrec[wave][14] = wrec[wave][15] = 0.f;
     }
     __syncthreads();
@@ -431,22 +251,15 @@ __global__ __launch_bounds__(64) void align_finalize_kernel(float* __restrict__ 
     }
     const int mir = bj / G;
     float m[9], t[3];
-#pragma unroll
-    for (int a = 0; a < 9; ++a) m[a] = recs[(size_t)bj * AL_REC + 2 + a];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) t[a] = recs[(size_t)bj * AL_REC + 11 + a];
-    if (mir) { m[6] = -m[6]; m[7] = -m[7]; m[8] = -m[8]; }      // diag(1, 1, -1) @ rot: the fit saw x with its third coordinate negated
+    sp_record_transform(recs + (size_t)bj * AL_REC, m, t);
+    if (mir) sp_unmirror(m);
     // ---- tm and rmsd under the fp32 transform that is returned, fp64
     const float* xs = planes + (size_t)s * 3 * N;
     const float* ys = planes + (size_t)(self ? r : S + r) * 3 * N;
-    const double d0 = al_d0(L), inv_d02 = 1.0 / (d0 * d0);
+    const double d0 = sp_d0(L), inv_d02 = 1.0 / (d0 * d0);
     double stm = 0.0, sd2 = 0.0;
     for (int i = lane; i < L; i += 64) {
-        const double x0 = xs[i], x1 = xs[N + i], x2 = xs[2 * N + i];
-        const double e0 = ((double)t[0] + (x0 * m[0] + x1 * m[3] + x2 * m[6])) - (double)ys[i];
-        const double e1 = ((double)t[1] + (x0 * m[1] + x1 * m[4] + x2 * m[7])) - (double)ys[N + i];
-        const double e2 = ((double)t[2] + (x0 * m[2] + x1 * m[5] + x2 * m[8])) - (double)ys[2 * N + i];
-        const double d2 = e0 * e0 + e1 * e1 + e2 * e2;
+        const double d2 = sp_d2_f64(xs, N, i, ys, N, i, m, t);
         sd2 += d2;
         stm += 1.0 / (1.0 + d2 * inv_d02);
     }
@@ -500,7 +313,7 @@ AlignPlan align_plan(int S, int R, int N, int pairs, int mode, int mirror) {
     int kmax = 1;                                       // the seed count is not monotonic in L: the largest one up to N
     if (mode == PRD_ALIGN_MODE_TM)
         for (int L = 3; L <= N; ++L) {
-            const int k = al_seed_count(L);
+            const int k = sp_seed_count(L);
             kmax = k > kmax ? k : kmax;
         }
     const int per = P.nw * AL_SEEDS_PER_WAVE;

@@ -8,26 +8,28 @@
 //                               current diagonal; three diagonals of val (fp64) / diag live in the LDS, indexed by row; scores are
 //                               formed on the fly from the transformed coordinates; directions are packed 2 bits per cell into the
 //                               workspace (a thread collects the 16 cells of a word of its row in a register and stores the word
-//                               once); one lane walks the traceback.  The fits are the waves' seed walks of prd_align.hip over the
+//                               once); one lane walks the traceback.  The fits are the waves' seed walks of prd_align.h over the
 //                               aligned pairs.  No workgroup waits on another.
 //   3. tmalign_search_kernel    one workgroup per (pair, mirror): the best of the three refinements, the d8 filter, the full search.
 //   4. tmalign_finalize_kernel  one wave per pair: the better mirror, tm / rmsd / n_aligned in fp64, the mapping in the caller's rows.
-// The fit and the seed walk are a COPY of those of prd_align.hip (DESIGN 7.2 says why they are not shared).
+// The seeds, d0, the fit and the record are those of prd_align.hip: both include prd_superpose.h, and this source asks the fit for
+// its outputs in scalar registers (kabsch_from_sums<true>).  The walk over the seeds is its own.
 // One owner per output element, plain vector stores, no atomics; every loop over rounds, cut-offs or traceback steps is bounded.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/prd_tmalign.h"
+#include "prd_superpose.h"
 
 namespace {
 
 #define TA_DEV __device__ __forceinline__
 
-constexpr int TA_COMPACT_WG = 256;      // threads of a compaction workgroup; each owns TA_OWN consecutive rows
+constexpr int TA_COMPACT_WG = SP_COMPACT_WG;    // threads of a compaction workgroup; each owns TA_OWN consecutive rows
 constexpr int TA_OWN = PRD_TMALIGN_MAX_N / TA_COMPACT_WG;
 constexpr int TA_WG = 512;              // threads of a refine / search workgroup
 constexpr int TA_NW = TA_WG / 64;
 constexpr int TA_ROWS = PRD_TMALIGN_MAX_N / TA_WG;      // DP rows a thread owns at most
-constexpr int TA_REC = 16;              // floats of a record: score, n (bits), rot[9], trans[3], 2 unused
+constexpr int TA_REC = SP_REC;          // floats of a record; its key is a seed, a threading offset or a number of pairs
 constexpr int TA_HDR = 16;              // ints at the head of the workspace; [0] = Lx, [1] = Ly
 constexpr int TA_INITS = 3;
 constexpr int TA_MIN_L = 5;
@@ -36,163 +38,8 @@ constexpr int TA_ROUNDS = 20;
 constexpr int TA_CUT_RAISES = 4096;
 constexpr int TA_ALL_LEVELS = 64;
 
-TA_DEV double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-TA_DEV float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// ---- the seeds of the search (prd_align.h, TM mode, steps 1 and 2), cut to the first `maxlev` fragment lengths -------------------
-TA_DEV int ta_next_level(int Lf, int L) { return Lf > 4 ? (Lf / 2 > 4 ? Lf / 2 : 4) : (Lf == 4 && L <= 21 ? 3 : 0); }
-TA_DEV int ta_level_count(int L, int Lf) {
-    const int step = Lf / 2 > 1 ? Lf / 2 : 1, span = L - Lf;
-    return span / step + 1 + (span % step ? 1 : 0);
-}
-TA_DEV int ta_seed_count(int L, int maxlev) {
-    if (L < 4) return 1;
-    int K = 0, lev = 0;
-    for (int Lf = L; Lf >= 3 && lev < maxlev; Lf = ta_next_level(Lf, L), ++lev) K += ta_level_count(L, Lf);
-    return K;
-}
-TA_DEV void ta_seed_decode(int L, int seed, int& start, int& len) {
-    start = 0;
-    len = L;
-    if (L < 4) return;
-    for (int Lf = L; Lf >= 3; Lf = ta_next_level(Lf, L)) {
-        const int c = ta_level_count(L, Lf);
-        if (seed < c) {
-            const int step = Lf / 2 > 1 ? Lf / 2 : 1;
-            const int s = seed * step;
-            start = s < L - Lf ? s : L - Lf;
-            len = Lf;
-            return;
-        }
-        seed -= c;
-    }
-}
-
-// a value that is the same in every lane of the wave, moved to a scalar register
-TA_DEV float ta_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-
-TA_DEV double ta_d0(int L) { return L > 21 ? 1.24 * cbrt((double)L - 15.0) - 1.8 : 0.5; }
-
-// ---- the fit (as in prd_align.hip) -------------------------------------------------------------------------------------------------
-template <int P, int Q>
-TA_DEV void jacobi_rotate(double (&A)[4][4], double (&V)[4][4]) {
-    const double apq = A[P][Q];
-    const float f = (float)apq;
-    if (f == 0.f) return;
-    const float th = 0.5f * (float)(A[Q][Q] - A[P][P]) * __builtin_amdgcn_rcpf(f);
-    const float t = __builtin_copysignf(1.f, th) * __builtin_amdgcn_rcpf(__builtin_fabsf(th) + __builtin_sqrtf(th * th + 1.f));
-    const float cf = __builtin_amdgcn_rsqf(t * t + 1.f), sf = t * cf;
-    if (!(cf == cf) || !(sf == sf)) return;         // a NaN angle (non-finite input) rotates nothing
-    double c = (double)cf, s = (double)sf;
-    const double k = 1.5 - 0.5 * (c * c + s * s);
-    c *= k;
-    s *= k;
-    const double app = A[P][P], aqq = A[Q][Q];
-    A[P][P] = c * c * app - 2.0 * c * s * apq + s * s * aqq;
-    A[Q][Q] = s * s * app + 2.0 * c * s * apq + c * c * aqq;
-    A[P][Q] = A[Q][P] = (c * c - s * s) * apq + c * s * (app - aqq);
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) {
-        if (k2 != P && k2 != Q) {
-            const double akp = A[k2][P], akq = A[k2][Q];
-            A[k2][P] = A[P][k2] = c * akp - s * akq;
-            A[k2][Q] = A[Q][k2] = s * akp + c * akq;
-        }
-        const double vkp = V[k2][P], vkq = V[k2][Q];
-        V[k2][P] = c * vkp - s * vkq;
-        V[k2][Q] = s * vkp + c * vkq;
-    }
-}
-
-// sums over n >= 3 pairs -> the proper rotation and translation of least squares, y ~ tr + x @ rot (Horn's quaternion form)
-TA_DEV void kabsch_from_sums(const double (&sx)[3], const double (&sy)[3], const double (&sxy)[9], double n, float (&rot)[9], float (&tr)[3]) {
-    const double inv = 1.0 / n;
-    double mx[3], my[3], M[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        mx[a] = sx[a] * inv;
-        my[a] = sy[a] * inv;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) M[a][b] = sxy[3 * a + b] - sx[a] * my[b];
-    double A[4][4], V[4][4];
-    A[0][0] = M[0][0] + M[1][1] + M[2][2];
-    A[1][1] = M[0][0] - M[1][1] - M[2][2];
-    A[2][2] = -M[0][0] + M[1][1] - M[2][2];
-    A[3][3] = -M[0][0] - M[1][1] + M[2][2];
-    A[0][1] = A[1][0] = M[1][2] - M[2][1];
-    A[0][2] = A[2][0] = M[2][0] - M[0][2];
-    A[0][3] = A[3][0] = M[0][1] - M[1][0];
-    A[1][2] = A[2][1] = M[0][1] + M[1][0];
-    A[1][3] = A[3][1] = M[2][0] + M[0][2];
-    A[2][3] = A[3][2] = M[1][2] + M[2][1];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 6; ++sweep) {
-        jacobi_rotate<0, 1>(A, V);
-        jacobi_rotate<0, 2>(A, V);
-        jacobi_rotate<0, 3>(A, V);
-        jacobi_rotate<1, 2>(A, V);
-        jacobi_rotate<1, 3>(A, V);
-        jacobi_rotate<2, 3>(A, V);
-    }
-    double best = A[0][0], q[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
-#pragma unroll
-    for (int j = 1; j < 4; ++j) {
-        const bool up = A[j][j] > best;
-        best = up ? A[j][j] : best;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) q[i] = up ? V[i][j] : q[i];
-    }
-    const double qn = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    const double w = q[0] * qn, a = q[1] * qn, b = q[2] * qn, c = q[3] * qn;
-    double Qm[3][3];
-    Qm[0][0] = 1.0 - 2.0 * (b * b + c * c); Qm[0][1] = 2.0 * (a * b - w * c);       Qm[0][2] = 2.0 * (a * c + w * b);
-    Qm[1][0] = 2.0 * (a * b + w * c);       Qm[1][1] = 1.0 - 2.0 * (a * a + c * c); Qm[1][2] = 2.0 * (b * c - w * a);
-    Qm[2][0] = 2.0 * (a * c - w * b);       Qm[2][1] = 2.0 * (b * c + w * a);       Qm[2][2] = 1.0 - 2.0 * (a * a + b * b);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) rot[3 * i + j] = ta_uniform((float)Qm[j][i]);       // every lane computed the same fit
-#pragma unroll
-    for (int j = 0; j < 3; ++j) tr[j] = ta_uniform((float)(my[j] - (mx[0] * Qm[j][0] + mx[1] * Qm[j][1] + mx[2] * Qm[j][2])));
-}
-
-// the two coordinate sets of a workgroup in the LDS, as planes
-struct Coords {
-    const float *X0, *X1, *X2, *Y0, *Y1, *Y2;
-};
-
-// squared distance of x_i and y_j under (rot, tr), fp32
-TA_DEV float ta_d2(const Coords& c, int i, int j, const float (&rot)[9], const float (&tr)[3]) {
-    const float x0 = c.X0[i], x1 = c.X1[i], x2 = c.X2[i];
-    const float e0 = (tr[0] + (x0 * rot[0] + x1 * rot[3] + x2 * rot[6])) - c.Y0[j];
-    const float e1 = (tr[1] + (x0 * rot[1] + x1 * rot[4] + x2 * rot[7])) - c.Y1[j];
-    const float e2 = (tr[2] + (x0 * rot[2] + x1 * rot[5] + x2 * rot[8])) - c.Y2[j];
-    return e0 * e0 + e1 * e1 + e2 * e2;
-}
-
-TA_DEV void keep3(float& a, float& b, float& c, float v) {
-    if (v < c) {
-        c = v;
-        if (c < b) { const float t = b; b = c; c = t; }
-        if (b < a) { const float t = a; a = b; b = t; }
-    }
-}
-
-// fit of the pairs (xi0 + k, yj0 + k), k in the lanes' share of [0, n), or of the pairs of a list: the 15 sums, fp64, one wave
+// the 15 sums of a fit over the pairs (x_i, y_j) that the lanes of one wave add, fp64 (align_search_kernel of prd_align.hip keeps
+// them as plain arrays: with this struct it takes 156 registers instead of its 158, and its figures are held where they are)
 struct Sums {
     double sx[3], sy[3], sxy[9];
 };
@@ -226,26 +73,19 @@ TA_DEV void sums_reduce(Sums& s) {
 TA_DEV float pick_wave_record(float (*wrec)[TA_REC], float best, int key, const float (&brot)[9], const float (&btr)[3], float (&rot)[9],
                               float (&tr)[3], int& okey) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        wrec[wave][0] = best;
-        wrec[wave][1] = __int_as_float(key);
-#pragma unroll
-        for (int a = 0; a < 9; ++a) wrec[wave][2 + a] = brot[a];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) wrec[wave][11 + a] = btr[a];
-    }
+    if (lane == 0) sp_record_write(wrec[wave], best, key, brot, btr);
     __syncthreads();
     int w = 0;
     for (int j = 1; j < TA_NW; ++j) {
         const float sj = wrec[j][0], sw = wrec[w][0];
         if (sj > sw || (sj == sw && __float_as_int(wrec[j][1]) < __float_as_int(wrec[w][1]))) w = j;
     }
-    const float sc = ta_uniform(wrec[w][0]);
+    const float sc = sp_uniform(wrec[w][0]);
     okey = __builtin_amdgcn_readfirstlane(__float_as_int(wrec[w][1]));
 #pragma unroll
-    for (int a = 0; a < 9; ++a) rot[a] = ta_uniform(wrec[w][2 + a]);
+    for (int a = 0; a < 9; ++a) rot[a] = sp_uniform(wrec[w][2 + a]);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) tr[a] = ta_uniform(wrec[w][11 + a]);
+    for (int a = 0; a < 3; ++a) tr[a] = sp_uniform(wrec[w][11 + a]);
     __syncthreads();
     return sc;
 }
@@ -255,13 +95,13 @@ TA_DEV float pick_wave_record(float (*wrec)[TA_REC], float best, int key, const 
 TA_DEV float wg_search(const Coords& c, const int* pl, const int* amap, int n, int maxlev, float inv_d02, float d0s, float (*wrec)[TA_REC],
                        float (&rot_out)[9], float (&tr_out)[3]) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int K = ta_seed_count(n, maxlev);
+    const int K = sp_seed_count(n, maxlev);
     const float inf = __builtin_inff();
     float best = -inf, brot[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, btr[3] = {0.f, 0.f, 0.f};
     int bseed = 0x7fffffff;
     for (int seed = wave; seed < K; seed += TA_NW) {                        // wave-uniform
         int start, len;
-        ta_seed_decode(n, seed, start, len);
+        sp_seed_decode(n, seed, start, len);
         unsigned mem = 0u;                                                   // bit k: pair lane + 64 k is in the subset (n <= 2048)
         for (int i = lane, k = 0; i < n; i += 64, ++k) mem |= (i >= start && i < start + len) ? 1u << k : 0u;
         float rot[9], tr[3];
@@ -279,11 +119,11 @@ TA_DEV float wg_search(const Coords& c, const int* pl, const int* amap, int n, i
             cnt = wave_sum(cnt);
             if (cnt < 3.f) break;                                            // only after non-finite input
             sums_reduce(s);
-            kabsch_from_sums(s.sx, s.sy, s.sxy, (double)cnt, rot, tr);
+            kabsch_from_sums<true>(s.sx, s.sy, s.sxy, (double)cnt, rot, tr);
             float sc = 0.f, m0 = inf, m1 = inf, m2 = inf;
             for (int i = lane; i < n; i += 64) {
                 const int xi = pl[i];
-                const float d2 = ta_d2(c, xi, amap[xi], rot, tr);
+                const float d2 = sp_d2(c, xi, amap[xi], rot, tr);
                 sc += __builtin_amdgcn_rcpf(1.f + d2 * inv_d02);
                 keep3(m0, m1, m2, d2);
             }
@@ -309,7 +149,7 @@ TA_DEV float wg_search(const Coords& c, const int* pl, const int* amap, int n, i
             unsigned next = 0u;
             for (int i = lane, k = 0; i < n; i += 64, ++k) {
                 const int xi = pl[i];
-                next |= ta_d2(c, xi, amap[xi], rot, tr) < cut2 ? 1u << k : 0u;
+                next |= sp_d2(c, xi, amap[xi], rot, tr) < cut2 ? 1u << k : 0u;
             }
             if (!__any(next != mem)) break;
             mem = next;
@@ -333,9 +173,9 @@ TA_DEV int wg_threading(const Coords& c, int Lx, int Ly, float inv_d02, float (*
         for (int i = i0 + lane; i < i1; i += 64) sums_add(s, c, i, i + k);
         sums_reduce(s);
         float rot[9], tr[3];
-        kabsch_from_sums(s.sx, s.sy, s.sxy, (double)(i1 - i0), rot, tr);
+        kabsch_from_sums<true>(s.sx, s.sy, s.sxy, (double)(i1 - i0), rot, tr);
         float sc = 0.f;
-        for (int i = i0 + lane; i < i1; i += 64) sc += __builtin_amdgcn_rcpf(1.f + ta_d2(c, i, i + k, rot, tr) * inv_d02);
+        for (int i = i0 + lane; i < i1; i += 64) sc += __builtin_amdgcn_rcpf(1.f + sp_d2(c, i, i + k, rot, tr) * inv_d02);
         sc = wave_sum(sc);
         if (sc > best) {
             best = sc;
@@ -481,23 +321,11 @@ __global__ __launch_bounds__(TA_COMPACT_WG) void tmalign_compact_kernel(float* _
     const int rs = isx ? x_rs : y_rs, N = isx ? Nx : Ny;
     float* dst = isx ? px + (size_t)st * 3 * Nx : py + (size_t)(st - S) * 3 * Ny;
     const int i0 = tid * TA_OWN;
-    int c = 0;
-    for (int i = i0; i < i0 + TA_OWN && i < N; ++i) c += mask[i] > 0.5f ? 1 : 0;
-    cnt[tid] = c;
-    __syncthreads();
-    int pos = 0, total = 0;
-    for (int j = 0; j < TA_COMPACT_WG; ++j) {
-        const int v = cnt[j];
-        pos += j < tid ? v : 0;
-        total += v;
-    }
+    int total, pos = sp_compact_start(cnt, mask, TA_OWN, N, total);
     for (int i = i0; i < i0 + TA_OWN && i < N; ++i) {
         const bool in = mask[i] > 0.5f;
         if (in) {                                       // pos < total <= N
-            const float* p = src + (long long)i * rs;
-            dst[pos] = p[0];
-            dst[N + pos] = p[1];
-            dst[2 * N + pos] = p[2];
+            sp_put_row(dst, N, pos, src + (long long)i * rs);
             if (st == S) idxy[pos] = i;
         }
         if (st == 0) cposx[i] = in ? pos : -1;
@@ -560,12 +388,7 @@ TA_DEV void ta_load(const Lds& l, const float* xs, const float* ys, int Nx, int 
 
 TA_DEV void ta_write_record(float* rec, float score, int n, const float (&rot)[9], const float (&tr)[3]) {
     if (threadIdx.x == 0) {
-        rec[0] = score;
-        rec[1] = __int_as_float(n);
-#pragma unroll
-        for (int a = 0; a < 9; ++a) rec[2 + a] = rot[a];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) rec[11 + a] = tr[a];
+        sp_record_write(rec, score, n, rot, tr);
         rec[14] = rec[15] = 0.f;
     }
 }
@@ -595,7 +418,7 @@ __global__ __launch_bounds__(TA_WG) void tmalign_refine_kernel(float* __restrict
     unsigned* dirs = dirs_all + (size_t)prob * Nx * ((Ny + 15) >> 4);
     float* rec = rec1 + (size_t)prob * TA_REC;
     int* mapout = maps1 + (size_t)prob * Nx;
-    const float d0 = (float)ta_d0(Ly), inv_d02 = 1.f / (d0 * d0), d0s = fminf(fmaxf(d0, 4.5f), 8.f);
+    const float d0 = (float)sp_d0(Ly), inv_d02 = 1.f / (d0 * d0), d0s = fminf(fmaxf(d0, 4.5f), 8.f);
     const float inf = __builtin_inff();
 
     float rot[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, tr[3] = {0.f, 0.f, 0.f};
@@ -689,11 +512,7 @@ __global__ __launch_bounds__(TA_WG) void tmalign_search_kernel(float* __restrict
         ta_write_record(rec, -inf, 0, rot, tr);
         return;
     }
-    const float* br = rec1 + ((size_t)pm * TA_INITS + bi) * TA_REC;
-#pragma unroll
-    for (int a = 0; a < 9; ++a) rot[a] = br[2 + a];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) tr[a] = br[11 + a];
+    sp_record_transform(rec1 + ((size_t)pm * TA_INITS + bi) * TA_REC, rot, tr);
     const Lds l = ta_carve(lds_raw, Nx, Ny, false, &nslot);
     ta_load(l, px + (size_t)s * 3 * Nx, py + (size_t)r * 3 * Ny, Nx, Ny, Lx, Ly, mir);
     const int* bm = maps1 + ((size_t)pm * TA_INITS + bi) * Nx;
@@ -703,12 +522,12 @@ __global__ __launch_bounds__(TA_WG) void tmalign_search_kernel(float* __restrict
     }
     __syncthreads();
     const Coords c = {l.X0, l.X1, l.X2, l.Y0, l.Y1, l.Y2};
-    const float d0 = (float)ta_d0(Ly), inv_d02 = 1.f / (d0 * d0), d0s = fminf(fmaxf(d0, 4.5f), 8.f);
+    const float d0 = (float)sp_d0(Ly), inv_d02 = 1.f / (d0 * d0), d0s = fminf(fmaxf(d0, 4.5f), 8.f);
     const float d8 = 1.5f * __builtin_powf((float)Ly, 0.3f) + 3.5f;
     int near = 0;
     for (int i = tid; i < Lx; i += TA_WG) {
         const int j = l.dp.amap[i];
-        near += (j >= 0 && ta_d2(c, i, j, rot, tr) <= d8 * d8) ? 1 : 0;
+        near += (j >= 0 && sp_d2(c, i, j, rot, tr) <= d8 * d8) ? 1 : 0;
     }
     // (a thread owns at most TA_ROWS positions: the count of a thread fits the predicate sum below)
     int total = 0;
@@ -716,7 +535,7 @@ __global__ __launch_bounds__(TA_WG) void tmalign_search_kernel(float* __restrict
     if (total >= 3) {
         for (int i = tid; i < Lx; i += TA_WG) {
             const int j = l.dp.amap[i];
-            if (j >= 0 && !(ta_d2(c, i, j, rot, tr) <= d8 * d8)) l.dp.amap[i] = -1;
+            if (j >= 0 && !(sp_d2(c, i, j, rot, tr) <= d8 * d8)) l.dp.amap[i] = -1;
         }
     }
     wg_list_pairs(l.dp, Lx, Nx);
@@ -769,26 +588,18 @@ __global__ __launch_bounds__(64) void tmalign_finalize_kernel(float* __restrict_
         }
         return;
     }
-    const float* br = rec2 + ((size_t)pair * nm + bj) * TA_REC;
-#pragma unroll
-    for (int a = 0; a < 9; ++a) m[a] = br[2 + a];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) t[a] = br[11 + a];
-    if (bj) { m[6] = -m[6]; m[7] = -m[7]; m[8] = -m[8]; }      // diag(1, 1, -1) @ rot: the fit saw x with its third coordinate negated
+    sp_record_transform(rec2 + ((size_t)pair * nm + bj) * TA_REC, m, t);
+    if (bj) sp_unmirror(m);
     const int* am = maps2 + ((size_t)pair * nm + bj) * Nx;
     const float* xs = px + (size_t)s * 3 * Nx;
     const float* ys = py + (size_t)r * 3 * Ny;
-    const double d0 = ta_d0(Ly), inv_d02 = 1.0 / (d0 * d0);
+    const double d0 = sp_d0(Ly), inv_d02 = 1.0 / (d0 * d0);
     double stm = 0.0, sd2 = 0.0;
     float cnt = 0.f;
     for (int i = lane; i < Lx; i += 64) {
         const int j = am[i];
         if (j < 0 || j >= Ly) continue;
-        const double x0 = xs[i], x1 = xs[Nx + i], x2 = xs[2 * Nx + i];
-        const double e0 = ((double)t[0] + (x0 * m[0] + x1 * m[3] + x2 * m[6])) - (double)ys[j];
-        const double e1 = ((double)t[1] + (x0 * m[1] + x1 * m[4] + x2 * m[7])) - (double)ys[Ny + j];
-        const double e2 = ((double)t[2] + (x0 * m[2] + x1 * m[5] + x2 * m[8])) - (double)ys[2 * Ny + j];
-        const double d2 = e0 * e0 + e1 * e1 + e2 * e2;
+        const double d2 = sp_d2_f64(xs, Nx, i, ys, Ny, j, m, t);
         sd2 += d2;
         stm += 1.0 / (1.0 + d2 * inv_d02);
         cnt += 1.f;

@@ -6,13 +6,12 @@ fits, the TM-score search of ``protein_redesign_amd.align`` on the aligned pairs
 Everything runs on the current stream with no host synchronisation.  HIP only: a missing library or a CPU tensor raises."""
 from __future__ import annotations
 
-import ctypes as C
 import dataclasses
 import os
 
 import torch
 
-from ._lib import dptr, parse_header, stream
+from ._lib import check, dptr, load_library, parse_defines, parse_header, stream
 from .align import _mask, _structures
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,11 +19,12 @@ LIB_PATH = os.path.join(HERE, "libprd_tmalign.so")
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "prd_tmalign.h")
 
 with open(HEADER_PATH) as _f:
-    ENTRIES = parse_header(_f.read())          # the header is the only statement of the C ABI
+    _HEADER = _f.read()                         # the header is the only statement of the C ABI and of its constants
+ENTRIES = parse_header(_HEADER, "include/prd_tmalign.h")
+_DEFINES = parse_defines(_HEADER, "PRD_TMALIGN_")
 
 ABI_VERSION = 100           # include/prd_tmalign.h PRD_TMALIGN_VERSION this binding is written against
-MAX_N = 2048                # PRD_TMALIGN_MAX_N
-ERR_UNSUPPORTED = -3
+MAX_N = _DEFINES["MAX_N"]
 
 _lib = None
 
@@ -33,26 +33,12 @@ def lib():
     """The loaded library; raises RuntimeError (never falls back) when it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -m protein_redesign_amd.build --tmalign` "
-                               "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
-        cdll = C.CDLL(LIB_PATH)
-        for name, e in ENTRIES.items():
-            fn = getattr(cdll, name)
-            fn.argtypes, fn.restype = e.argtypes, e.restype
-        if cdll.prd_tmalign_version() != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH} reports PRD_TMALIGN_VERSION {cdll.prd_tmalign_version()}, this binding was written against "
-                               f"{ABI_VERSION}: rebuild with `python -m protein_redesign_amd.build --tmalign`")
-        _lib = cdll
+        _lib = load_library(LIB_PATH, ENTRIES, "prd_tmalign_version", ABI_VERSION, "--tmalign")
     return _lib
 
 
 def _check(code: int, what: str):
-    if code == ERR_UNSUPPORTED:
-        raise ValueError(f"{what}: at most {MAX_N} positions per structure (PRD_TMALIGN_MAX_N)")
-    if code != 0:
-        names = {-1: "PRD_TMALIGN_ERR_ARG", -4: "PRD_TMALIGN_ERR_WORKSPACE"}
-        raise RuntimeError(f"{what} failed: {names.get(code, 'hipError_t ' + str(code))}")
+    check(code, what, _DEFINES, "PRD_TMALIGN_", f"at most {MAX_N} positions per structure (PRD_TMALIGN_MAX_N)")
 
 
 @dataclasses.dataclass(frozen=True)

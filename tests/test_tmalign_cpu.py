@@ -2,6 +2,7 @@
 workspace query of libprd_tmalign.so, the Python-side argument checks and the ``correspondence`` keyword of pipeline.generate_samples as
 far as it goes without a GPU."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -122,6 +123,45 @@ def test_the_other_builds_issue_the_commands_they_issued_before(monkeypatch):
     assert rec.cmds == [shipped[:-3] + [src, "-o", obj],
                         shipped[:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_tmalign.so", obj]]
     assert build.ALIGN_SOURCES == ["prd_align.hip"] and build.TMALIGN_SOURCES == ["prd_tmalign.hip"]
+
+
+@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
+def test_the_shared_fit_header_makes_both_side_libraries_stale_and_not_the_denoiser(monkeypatch):
+    """``_stale`` is the real one and no compiler runs: the header of the fit (csrc/prd_superpose.h) is given the newest time stamp, and
+    a command that is recorded makes its output newer still, as the compiler would have."""
+    build.build(verbose=False)
+    build.build_align(verbose=False)
+    build.build_tmalign(verbose=False)
+    header, real, written = os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_superpose.h"), os.path.getmtime, []
+    assert os.path.exists(header)
+    newest = max(real(p) for p in (build.LIB, build.LIB_ALIGN, build.LIB_TMALIGN)) + 10.0
+    monkeypatch.setattr(os.path, "getmtime", lambda p: newest + 10.0 * (1 + written.index(p)) if p in written else newest if p == header else real(p))
+
+    class Touching(Recorder):
+        def __call__(self, kind, cmd, *a, **kw):
+            written.extend(cmd[cmd.index("-o") + 1:][:1] if "-o" in cmd else [])
+            return super().__call__(kind, cmd, *a, **kw)
+    rec = Touching(execute=False)
+    rec.install(monkeypatch)
+    build.build(verbose=False)
+    assert rec.cmds == []
+    for fn, name in ((build.build_align, "align"), (build.build_tmalign, "tmalign")):
+        fn(verbose=False)
+        obj = "{ROOT}/protein_redesign_amd/csrc/prd_%s.o" % name
+        assert [c[-3:] for c in rec.cmds] == [["{ROOT}/protein_redesign_amd/csrc/prd_%s.hip" % name, "-o", obj],
+                                              ["-o", "{ROOT}/protein_redesign_amd/libprd_%s.so" % name, obj]]
+        rec.cmds = []
+
+
+def test_the_fit_is_defined_in_one_file():
+    csrc = os.path.join(ROOT, "protein_redesign_amd", "csrc")
+    for fn in ("jacobi_rotate", "kabsch_from_sums"):
+        defined = []
+        for name in sorted(os.listdir(csrc)):
+            if name.endswith((".hip", ".h", ".inc")):
+                with open(os.path.join(csrc, name)) as f:
+                    defined += [name] * len(re.findall(r"\bvoid\s+%s\s*\(" % fn, f.read()))
+        assert defined == ["prd_superpose.h"], (fn, defined)
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
