@@ -14,7 +14,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # would pack its scalar fp32 adds into v_pk_add_f32 (slower beside MFMAs on gfx950) and move them out of their slots
 EXTRA_FLAGS = {"prd_tri2.hip": ["-fno-slp-vectorize"]}
 PRD_HIP_H = os.path.join(os.path.dirname(HERE), "include", "prd_hip.h")
-HEADERS = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_tri2_v3_body.inc"), PRD_HIP_H]      # every object depends on these
+# every object depends on these (prd_launch.h: the host half of every launch -- the checked launch, the pair_dim dispatch, the geometry)
+HEADERS = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_launch.h"), os.path.join(CSRC, "prd_tri2_v3_body.inc"), PRD_HIP_H]
 # The side libraries: post-processing of samples, not part of the denoiser ABI, hence each a library of its own with its own header, so
 # that libprd_hip.so, prd_hip.h and their recorded command lines stay what they are; same flags, same compile routine.  Per library:
 # its sources, the headers every object of it depends on, the library, and the flag of this module's command line that builds it.

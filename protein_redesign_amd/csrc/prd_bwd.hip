@@ -16,7 +16,7 @@
 #include "prd_common.h"
 #include <type_traits>
 #include "../../include/prd_hip.h"
-#include <mutex>
+#include "prd_launch.h"
 
 namespace {
 
@@ -44,13 +44,6 @@ PRD_DEV void ln_cll_bwd(float (&dy)[KH], const float (&y)[KH], float rstd) {
     const float m1 = xhalf_sum(s1) * (1.0f / (2 * KH)), m2 = xhalf_sum(s2) * (1.0f / (2 * KH));
 #pragma unroll
     for (int k = 0; k < KH; ++k) dy[k] = rstd * (dy[k] - m1 - y[k] * m2);
-}
-
-int grid_for(long tasks, int per_wg, int cap) {
-    long g = (tasks + per_wg - 1) / per_wg;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 template <int P, int NW>
@@ -1134,14 +1127,6 @@ __global__ __launch_bounds__(256) void linear_wgrad_reduce_kernel(float* __restr
 
 }  // namespace
 
-#define PRD_BWD_SET_LDS(kernel)                                                                                 \
-    do {                                                                                                        \
-        static std::once_flag once_;                                                                            \
-        std::call_once(once_, [] {                                                                              \
-            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        });                                                                                                     \
-    } while (0)
-
 // Operands of the two gradient contractions of TriangleMultiplication as ONE stacked contraction (prd_tri_mul_contract with 2P
 // channel pairs): ops [b][4P][N][ldn] = dO | dO^T | B^T | A^T by channel block, so that
 //   out[c]     = dO[c]   (B^T[c])^T  = dA[c]      (dA[i][k] = sum_j dO[i][j] B[j][k])
@@ -1277,8 +1262,7 @@ extern "C" int prd_rbf_rows(float* out, const float* z, const float* centers, co
     if (R % 4) return PRD_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(centers)) & 15) return PRD_ERR_ALIGN;
     const long npos = (long)b * N * N, nthr = npos * (R / 4);
-    hipLaunchKernelGGL(rbf_rows_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, out, z, centers, mask, npos, N, R);
-    return (int)hipGetLastError();
+    return prd_launch<rbf_rows_kernel>(dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, out, z, centers, mask, npos, N, R);
 }
 
 // out[b][i][j][:] = scale (x[b][i][j][:] + x[b][j][i][:]): the pair symmetrisation in front of the coordinate head (modules.py:403)
@@ -1340,11 +1324,10 @@ __global__ __launch_bounds__(256) void outer_linear_bwd_dw1_kernel(float* __rest
 extern "C" int prd_outer_linear_bwd_reduce(float* dx, float* dw1_part, int chunks, const float* T, const float* w1, const float* x,
                                            long long R, int P, int S, hipStream_t stream) {
     if (!dx || !dw1_part || !T || !w1 || !x || R <= 0 || P <= 0 || S <= 0 || chunks <= 0) return PRD_ERR_ARG;
-    hipLaunchKernelGGL(outer_linear_bwd_dx_kernel, dim3((unsigned)((R * S + 255) / 256)), dim3(256), 0, stream, dx, T, w1, (long)R, P, S);
+    PRD_TRY(prd_launch<outer_linear_bwd_dx_kernel>(dim3((unsigned)((R * S + 255) / 256)), dim3(256), 0, stream, dx, T, w1, (long)R, P, S));
     const int rpc = (int)((R + chunks - 1) / chunks);
-    hipLaunchKernelGGL(outer_linear_bwd_dw1_kernel, dim3((unsigned)(((long)P * S + 255) / 256), chunks), dim3(256), 0, stream, dw1_part, T, x,
-                       (long)R, P, S, rpc);
-    return (int)hipGetLastError();
+    return prd_launch<outer_linear_bwd_dw1_kernel>(dim3((unsigned)(((long)P * S + 255) / 256), chunks), dim3(256), 0, stream, dw1_part, T, x,
+                                                   (long)R, P, S, rpc);
 }
 
 extern "C" int prd_sym_rows(float* out, const float* x, float scale, int b, int N, int P, hipStream_t stream) {
@@ -1352,8 +1335,7 @@ extern "C" int prd_sym_rows(float* out, const float* x, float scale, int b, int 
     if (P % 4 || out == x) return PRD_ERR_UNSUPPORTED;                  // (not in place: position (j, i) is read by another thread)
     if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(x)) & 15) return PRD_ERR_ALIGN;
     const long npos = (long)b * N * N, nthr = npos * (P / 4);
-    hipLaunchKernelGGL(sym_rows_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, out, x, npos, N, P / 4, scale);
-    return (int)hipGetLastError();
+    return prd_launch<sym_rows_kernel>(dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, out, x, npos, N, P / 4, scale);
 }
 
 extern "C" int prd_sym_transpose(float* out, const float* dy, int b, int N, int P, hipStream_t stream) {
@@ -1367,8 +1349,7 @@ extern "C" int prd_sym_transpose_amax(float* out, const float* dy, int b, int N,
     const int T = prd_ceil_div(N, 64);
     const long ntask = (long)b * N * T;
     const int grid = (int)(ntask < 256 * 8 ? ntask : 256 * 8);
-    hipLaunchKernelGGL(sym_transpose_kernel, dim3(grid), dim3(256), 0, stream, out, dy, N, P, T, ntask, amax);
-    return (int)hipGetLastError();
+    return prd_launch<sym_transpose_kernel>(dim3(grid), dim3(256), 0, stream, out, dy, N, P, T, ntask, amax);
 }
 
 extern "C" int prd_tri_mul_bwd_operands(float* ops, const float* AB, int b, int N, int P, hipStream_t stream) {
@@ -1377,8 +1358,7 @@ extern "C" int prd_tri_mul_bwd_operands(float* ops, const float* AB, int b, int 
     const int ldn = prd_round_up(N, 32), T = prd_ceil_div(ldn, 64);
     const long ntask = (long)b * P * T * T * 3;
     const int grid = (int)(ntask < 256 * 8 ? ntask : 256 * 8);
-    hipLaunchKernelGGL(tri_mul_bwd_operands_kernel, dim3(grid), dim3(256), 0, stream, ops, AB, N, ldn, P, T, ntask);
-    return (int)hipGetLastError();
+    return prd_launch<tri_mul_bwd_operands_kernel>(dim3(grid), dim3(256), 0, stream, ops, AB, N, ldn, P, T, ntask);
 }
 
 extern "C" int prd_tri_mul_out_bwd(float* dz, float* dgp, float* dO, float* dx1, const float* dy, const float* pair, const float* O,
@@ -1401,16 +1381,9 @@ extern "C" int prd_tri_mul_out_bwd_amax(float* dz, float* dgp, float* dO, float*
     const int ldn = prd_round_up(N, 32);
     const size_t lds = ((size_t)4 * P * (P + 4) + 2 * P) * sizeof(float);
     const int grid = grid_for((long)b * N * prd_ceil_div(N, 32), 4, 256);
-    if (P == 64) {
-        PRD_BWD_SET_LDS((tri_mul_out_bwd_kernel<64, NWB>));
-        hipLaunchKernelGGL((tri_mul_out_bwd_kernel<64, NWB>), dim3(grid), dim3(NWB * 64), lds, stream, dz, dgp, dO, dx1, dy, pair, O, w_out,
-                           b_out, w_ogate, b_ogate, w_out_t, w_ogate_t, b, N, ldn, x_out, lo_out, dO_batch_channels, dO_amax);
-    } else {
-        PRD_BWD_SET_LDS((tri_mul_out_bwd_kernel<32, NWB>));
-        hipLaunchKernelGGL((tri_mul_out_bwd_kernel<32, NWB>), dim3(grid), dim3(NWB * 64), lds, stream, dz, dgp, dO, dx1, dy, pair, O, w_out,
-                           b_out, w_ogate, b_ogate, w_out_t, w_ogate_t, b, N, ldn, x_out, lo_out, dO_batch_channels, dO_amax);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<tri_mul_out_bwd_kernel<PP, NWB>>(dim3(grid), dim3(NWB * 64), lds, stream, dz, dgp, dO, dx1, dy, pair, O,
+                                                                        w_out, b_out, w_ogate, b_ogate, w_out_t, w_ogate_t, b, N, ldn, x_out,
+                                                                        lo_out, dO_batch_channels, dO_amax));
 }
 
 extern "C" int prd_tri_mul_proj_bwd(float* dpair, float* dpp, float* dpg, const float* dAB, const float* dx1, const float* pair,
@@ -1427,16 +1400,9 @@ extern "C" int prd_tri_mul_proj_bwd(float* dpair, float* dpp, float* dpg, const 
                           : ((size_t)2 * 2 * P * (P + 4) + (size_t)2 * P * (2 * P + 4) + 4 * P) * sizeof(float);
     if (lds > 160 * 1024) return PRD_ERR_UNSUPPORTED;
     const int grid = grid_for((long)b * N * prd_ceil_div(N, 32), 4, 256);
-#define PRD_PBW(PP, BB)                                                                                              \
-    do {                                                                                                             \
-        PRD_BWD_SET_LDS((tri_mul_proj_bwd_kernel<PP, NWB, BB>));                                                     \
-        hipLaunchKernelGGL((tri_mul_proj_bwd_kernel<PP, NWB, BB>), dim3(grid), dim3(NWB * 64), lds, stream, dpair, dpp, dpg, dAB, dx1, pair, \
-                           mask, w_proj, b_proj, w_gate, b_gate, w_proj_t, w_gate_t, b, N, ldn, incoming);           \
-    } while (0)
-    if (P == 64) { if (b3) PRD_PBW(64, true); else PRD_PBW(64, false); }
-    else { if (b3) PRD_PBW(32, true); else PRD_PBW(32, false); }
-#undef PRD_PBW
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3, BB,
+        prd_launch<tri_mul_proj_bwd_kernel<PP, NWB, BB>>(dim3(grid), dim3(NWB * 64), lds, stream, dpair, dpp, dpg, dAB, dx1, pair,
+                                                         mask, w_proj, b_proj, w_gate, b_gate, w_proj_t, w_gate_t, b, N, ldn, incoming)));
 }
 
 extern "C" int prd_tri_attn_bwd_core(float* dqkvg, const float* dog, const float* pair, const float* mask, const float* wq,
@@ -1450,14 +1416,8 @@ extern "C" int prd_tri_attn_bwd_core(float* dqkvg, const float* dog, const float
     const long nwork = (long)b * N * H;
     const int grid = (int)(nwork < 256 ? nwork : 256);
     const int nthreads = 512;                                   // 8 waves: two per SIMD cover each other's dependent MFMA chains
-    if (P == 64) {
-        PRD_BWD_SET_LDS(tri_attn_bwd_core_kernel<64>);
-        hipLaunchKernelGGL(tri_attn_bwd_core_kernel<64>, dim3(grid), dim3(nthreads), lds, stream, dqkvg, dog, pair, mask, wq, wk, wv, wg, bg, b, N, npad, H, ending);
-    } else {
-        PRD_BWD_SET_LDS(tri_attn_bwd_core_kernel<32>);
-        hipLaunchKernelGGL(tri_attn_bwd_core_kernel<32>, dim3(grid), dim3(nthreads), lds, stream, dqkvg, dog, pair, mask, wq, wk, wv, wg, bg, b, N, npad, H, ending);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<tri_attn_bwd_core_kernel<PP>>(dim3(grid), dim3(nthreads), lds, stream, dqkvg, dog, pair, mask, wq, wk, wv,
+                                                                     wg, bg, b, N, npad, H, ending));
 }
 
 // ---- a linear at every pair position as a ROW kernel (the GEMMs of the training backward with 2e5 rows and K, N <= 256) --------
@@ -1604,26 +1564,17 @@ extern "C" int prd_pair_linear(float* out, const float* x, const float* w, const
     const size_t lds = ((size_t)OUT * K + OUT) * sizeof(float);
     const long ntask = (rows + 31) / 32;
     const int grid = grid_for(ntask, NWP, 256);          // one persistent workgroup per CU (the register budget allows two waves per SIMD)
-    if (K == 64) {
-        PRD_BWD_SET_LDS((pair_linear_rows_kernel<64, NWP>));
-        hipLaunchKernelGGL((pair_linear_rows_kernel<64, NWP>), dim3(grid), dim3(NWP * 64), lds, stream, out, xn_out, x, w, bias, mask_pos,
-                           (long)rows, OUT, ln_in, act, w_kn);
-    } else {
-        PRD_BWD_SET_LDS((pair_linear_rows_kernel<256, NWP>));
-        hipLaunchKernelGGL((pair_linear_rows_kernel<256, NWP>), dim3(grid), dim3(NWP * 64), lds, stream, out, xn_out, x, w, bias, mask_pos,
-                           (long)rows, OUT, ln_in, act, w_kn);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_2(K, KK, 64, 256,
+        prd_launch<pair_linear_rows_kernel<KK, NWP>>(dim3(grid), dim3(NWP * 64), lds, stream, out, xn_out, x, w, bias, mask_pos,
+                                                     (long)rows, OUT, ln_in, act, w_kn));
 }
 
 extern "C" int prd_ln_rows_bwd(float* dx, const float* dy, const float* x, const float* res, long long rows, int C, hipStream_t stream) {
     if (!dx || !dy || !x || rows <= 0 || C <= 0) return PRD_ERR_ARG;
     const bool al16 = ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(res)) & 15) == 0;
     if (C == 64 && al16)
-        hipLaunchKernelGGL(ln_rows_bwd64_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, stream, dx, dy, x, res, (long)rows);
-    else
-        hipLaunchKernelGGL(ln_rows_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, dx, dy, x, res, (long)rows, C);
-    return (int)hipGetLastError();
+        return prd_launch<ln_rows_bwd64_kernel>(dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, stream, dx, dy, x, res, (long)rows);
+    return prd_launch<ln_rows_bwd_kernel>(dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, dx, dy, x, res, (long)rows, C);
 }
 
 extern "C" int prd_pair_bias_bwd(float* dx, float* xn, float* d2, const float* dbias, const float* wf, const float* x, int b, long long nn,
@@ -1633,9 +1584,7 @@ extern "C" int prd_pair_bias_bwd(float* dx, float* xn, float* d2, const float* d
     if ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(xn) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wf)) & 15) return PRD_ERR_ALIGN;
     const long rows = (long)b * nn;
     const dim3 grid((unsigned)((rows + 15) / 16));
-    if (H == 4) hipLaunchKernelGGL(pair_bias_bwd64_kernel<4>, grid, dim3(256), 0, stream, dx, xn, d2, dbias, wf, x, rows, (long)nn);
-    else hipLaunchKernelGGL(pair_bias_bwd64_kernel<8>, grid, dim3(256), 0, stream, dx, xn, d2, dbias, wf, x, rows, (long)nn);
-    return (int)hipGetLastError();
+    return PRD_FOR_2(H, HH, 4, 8, prd_launch<pair_bias_bwd64_kernel<HH>>(grid, dim3(256), 0, stream, dx, xn, d2, dbias, wf, x, rows, (long)nn));
 }
 
 static long wgrad_slabs(long long rows) {
@@ -1664,24 +1613,20 @@ extern "C" int prd_linear_wgrad(float* dw, float* db, const float* dy, const flo
     const int rows_per_wg = (int)((rows + slabs - 1) / slabs);
     const int want_db = db ? 1 : 0;
     const int nw = O * I, n = nw + (want_db ? O : 0);
+    // the three kernel families take the same arguments; PER: 64x64 blocks of dW per workgroup (narrow: rows of dW per lane group)
+#define PRD_WGRAD(...) prd_launch<__VA_ARGS__>(grid, dim3(256), 0, stream, ws, dy, x, (long)rows, O, I, lddy, ldx, rows_per_wg, want_db)
     if (narrow) {
-        dim3 grid((unsigned)slabs, I / 64);
-        if (O <= 4) hipLaunchKernelGGL(linear_wgrad_narrow_kernel<4>, grid, dim3(256), 0, stream, ws, dy, x, (long)rows, O, I, lddy, ldx, rows_per_wg, want_db);
-        else hipLaunchKernelGGL(linear_wgrad_narrow_kernel<16>, grid, dim3(256), 0, stream, ws, dy, x, (long)rows, O, I, lddy, ldx, rows_per_wg, want_db);
+        const dim3 grid((unsigned)slabs, I / 64);
+        PRD_TRY(PRD_FOR_2(O <= 4 ? 4 : 16, PER, 4, 16, PRD_WGRAD(linear_wgrad_narrow_kernel<PER>)));
     } else {
         const int nblk = (O / 64) * (I / 64);
         const int per = (nblk % 4 == 0) ? 4 : ((nblk % 2 == 0) ? 2 : 1);     // 64x64 blocks per workgroup
-        dim3 grid((unsigned)slabs, nblk / per);
-        if (arith == PRD_ARITH_SPLIT16) {
-            if (per == 4) hipLaunchKernelGGL(linear_wgrad_h2_kernel<4>, grid, dim3(256), 0, stream, ws, dy, x, (long)rows, O, I, lddy, ldx, rows_per_wg, want_db);
-            else if (per == 2) hipLaunchKernelGGL(linear_wgrad_h2_kernel<2>, grid, dim3(256), 0, stream, ws, dy, x, (long)rows, O, I, lddy, ldx, rows_per_wg, want_db);
-            else hipLaunchKernelGGL(linear_wgrad_h2_kernel<1>, grid, dim3(256), 0, stream, ws, dy, x, (long)rows, O, I, lddy, ldx, rows_per_wg, want_db);
-        } else if (per == 4) hipLaunchKernelGGL(linear_wgrad_kernel<4>, grid, dim3(256), 0, stream, ws, dy, x, (long)rows, O, I, lddy, ldx, rows_per_wg, want_db);
-        else if (per == 2) hipLaunchKernelGGL(linear_wgrad_kernel<2>, grid, dim3(256), 0, stream, ws, dy, x, (long)rows, O, I, lddy, ldx, rows_per_wg, want_db);
-        else hipLaunchKernelGGL(linear_wgrad_kernel<1>, grid, dim3(256), 0, stream, ws, dy, x, (long)rows, O, I, lddy, ldx, rows_per_wg, want_db);
+        const dim3 grid((unsigned)slabs, nblk / per);
+        if (arith == PRD_ARITH_SPLIT16) PRD_TRY(PRD_FOR_3(per, PER, 4, 2, 1, PRD_WGRAD(linear_wgrad_h2_kernel<PER>)));
+        else PRD_TRY(PRD_FOR_3(per, PER, 4, 2, 1, PRD_WGRAD(linear_wgrad_kernel<PER>)));
     }
-    hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, stream, dw, db, ws, n, nw, (int)slabs);
-    return (int)hipGetLastError();
+#undef PRD_WGRAD
+    return prd_launch<linear_wgrad_reduce_kernel>(dim3((n + 63) / 64), dim3(256), 0, stream, dw, db, ws, n, nw, (int)slabs);
 }
 
 extern "C" int prd_embed_wgrad_multi(float* dtables, const long long* const* idx, const float* const* row_scale, const int* card, int K,
@@ -1705,12 +1650,9 @@ extern "C" int prd_embed_wgrad_multi(float* dtables, const long long* const* idx
     const long slabs = wgrad_slabs(rows);
     const int rows_per_wg = (int)((rows + slabs - 1) / slabs);
     const size_t lds = (size_t)4 * total * 64 * sizeof(float);
-    static std::once_flag once;
-    std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)embed_wgrad_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    hipLaunchKernelGGL(embed_wgrad_multi_kernel, dim3((unsigned)slabs), dim3(256), lds, stream, ws, em, dy, (long)rows, C, lddy, rows_per_wg);
+    PRD_TRY(prd_launch<embed_wgrad_multi_kernel>(dim3((unsigned)slabs), dim3(256), lds, stream, ws, em, dy, (long)rows, C, lddy, rows_per_wg));
     const int n = total * C;
-    hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, stream, dtables, (float*)nullptr, ws, n, n, (int)slabs);
-    return (int)hipGetLastError();
+    return prd_launch<linear_wgrad_reduce_kernel>(dim3((n + 63) / 64), dim3(256), 0, stream, dtables, (float*)nullptr, ws, n, n, (int)slabs);
 }
 
 extern "C" size_t prd_embed_wgrad_workspace(long long rows, int card, int C) {
@@ -1726,10 +1668,7 @@ extern "C" int prd_embed_wgrad(float* dtable, const long long* idx, const float*
     const long slabs = wgrad_slabs(rows);
     const int rows_per_wg = (int)((rows + slabs - 1) / slabs);
     const size_t lds = (size_t)4 * card * 64 * sizeof(float);
-    static std::once_flag once;
-    std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)embed_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    hipLaunchKernelGGL(embed_wgrad_kernel, dim3((unsigned)slabs), dim3(256), lds, stream, ws, idx, dy, row_scale, (long)rows, card, C, lddy, rows_per_wg);
+    PRD_TRY(prd_launch<embed_wgrad_kernel>(dim3((unsigned)slabs), dim3(256), lds, stream, ws, idx, dy, row_scale, (long)rows, card, C, lddy, rows_per_wg));
     const int n = card * C;
-    hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, stream, dtable, (float*)nullptr, ws, n, n, (int)slabs);
-    return (int)hipGetLastError();
+    return prd_launch<linear_wgrad_reduce_kernel>(dim3((n + 63) / 64), dim3(256), 0, stream, dtable, (float*)nullptr, ws, n, n, (int)slabs);
 }

@@ -295,30 +295,8 @@ PRD_DEV void split3_cll(const float (&x)[K / 2], u32x4 (&p)[3][K / 16]) {
             p[2][s][q] = pl;
         }
 }
-// W: global [nout][K] fp32 -> LDS image [3 planes][nout rows of (2*K/16 + 1) x 16 bytes] (the +1 pads the row pitch so that
-// the b128 A-operand reads are bank-conflict free); returns nothing, rows_total = nout is the plane stride in rows
-template <int K>
-PRD_DEV void stage_weight_b3(u32x4* Wb, const float* __restrict__ W, int nout, int ldw, int tid, int nthreads, float scale = 1.0f) {
-    constexpr int S = K / 16, PITCH = 2 * S + 1;
-    for (int idx = tid; idx < nout * S * 2; idx += nthreads) {
-        const int o = idx / (2 * S), rem = idx - o * (2 * S), st = rem >> 1, h = rem & 1;
-        const float4 g0 = *reinterpret_cast<const float4*>(W + (size_t)o * ldw + 16 * st + 4 * h);        // CLL elements 8st .. 8st+3
-        const float4 g1 = *reinterpret_cast<const float4*>(W + (size_t)o * ldw + 16 * st + 8 + 4 * h);    // 8st+4 .. 8st+7
-        const float v[8] = {scale * g0.x, scale * g0.y, scale * g0.z, scale * g0.w, scale * g1.x, scale * g1.y, scale * g1.z, scale * g1.w};
-        u32x4 pk[3];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            unsigned ph, pm, pl;
-            split3(v[2 * q], v[2 * q + 1], ph, pm, pl);
-            pk[0][q] = ph;
-            pk[1][q] = pm;
-            pk[2][q] = pl;
-        }
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) Wb[((size_t)pl * nout + o) * PITCH + 2 * st + h] = pk[pl];
-    }
-}
-// same, for `nrows` rows of W placed at rows row0.. of an image whose planes are `nout` rows apart
+// W: `nrows` rows of global [..][K] fp32 -> rows row0.. of an LDS image [3 planes][nout rows of (2*K/16 + 1) x 16 bytes] (the +1 pads
+// the row pitch so that the b128 A-operand reads are bank-conflict free); nout is the plane stride in rows
 template <int K>
 PRD_DEV void stage_weight_b3_rows(u32x4* Wb, int nout, int row0, const float* __restrict__ W, int nrows, int ldw, int tid, int nthreads,
                                   float scale) {
@@ -341,7 +319,7 @@ PRD_DEV void stage_weight_b3_rows(u32x4* Wb, int nout, int row0, const float* __
         for (int pl = 0; pl < 3; ++pl) Wb[((size_t)pl * nout + row0 + o) * PITCH + 2 * st + h] = pk[pl];
     }
 }
-// acc[nb] += W[row0 + 32*nb .. +31][:] * x for the split row p; Wb / nout as staged by stage_weight_b3
+// acc[nb] += W[row0 + 32*nb .. +31][:] * x for the split row p; Wb / nout as staged by stage_weight_b3_rows
 template <int K, int NB>
 PRD_DEV void rowgemm_b3(const u32x4* Wb, int nout, int row0, const u32x4 (&p)[3][K / 16], f32x16 (&acc)[NB], int r, int hi) {
     constexpr int S = K / 16, PITCH = 2 * S + 1;
@@ -358,28 +336,6 @@ PRD_DEV void rowgemm_b3(const u32x4* Wb, int nout, int row0, const u32x4 (&p)[3]
                 acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w[wp[t]]), __builtin_bit_cast(bf16x8, p[xp[t]][s]),
                                                                    acc[nb], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);          // keeps hipcc from hoisting every LDS read of the unrolled loops (spills)
-        }
-}
-
-// Same products with the operands SWAPPED: D = X * W^T, i.e. lane (r, hi) register q holds output channel row0 + 32 nb + r of
-// pair row drow32(q, hi) -- four CONSECUTIVE rows per register quad, which is what a channel-major store wants
-// (tri_mul_proj's bf16 x 3 operand planes: 8-byte stores of 4 bf16 instead of 2-byte scatters).
-template <int K, int NB>
-PRD_DEV void rowgemm_b3_t(const u32x4* Wb, int nout, int row0, const u32x4 (&p)[3][K / 16], f32x16 (&acc)[NB], int r, int hi) {
-    constexpr int S = K / 16, PITCH = 2 * S + 1;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            u32x4 w[3];
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) w[pl] = Wb[((size_t)pl * nout + row0 + nb * 32 + r) * PITCH + 2 * s + hi];
-            const int wp[6] = {0, 0, 1, 0, 2, 1}, xp[6] = {0, 1, 0, 2, 0, 1};
-#pragma unroll
-            for (int t = 0; t < 6; ++t)
-                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, p[xp[t]][s]), __builtin_bit_cast(bf16x8, w[wp[t]]),
-                                                                   acc[nb], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
         }
 }
 

@@ -6,7 +6,7 @@
 // (ProteinReDiff/modules.py:185-225, 306-311; models/AF2_modules.py:251-293, 613-628).
 #include "prd_common.h"
 #include "../../include/prd_hip.h"
-#include <mutex>
+#include "prd_launch.h"
 
 namespace {
 
@@ -722,20 +722,12 @@ __global__ __launch_bounds__(256 * KG) void gemm_ring_kernel(PrdGemm g) {
 template <int D, int KG>
 static int launch_ring(const PrdGemm& g, dim3 grid, hipStream_t stream) {
     const size_t lds = (size_t)KG * 2 * 4 * 32 * 64 * 2 + 1024;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)gemm_ring_kernel<D, KG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)gemm_ring_kernel<D, KG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    if (g.a_ln) hipLaunchKernelGGL((gemm_ring_kernel<D, KG, true>), grid, dim3(256 * KG), lds, stream, g);
-    else hipLaunchKernelGGL((gemm_ring_kernel<D, KG, false>), grid, dim3(256 * KG), lds, stream, g);
-    return (int)hipGetLastError();
+    return PRD_FOR_BOOL(g.a_ln, LN, prd_launch<gemm_ring_kernel<D, KG, LN>>(grid, dim3(256 * KG), lds, stream, g));
 }
 
 static int launch_ring_bkn(const PrdGemm& g, dim3 grid, hipStream_t stream) {      // B as [K][N]: P V of SPAttention (K = keys)
     const size_t lds = (size_t)2 * 4 * 32 * 64 * 2 + 1024;
-    hipLaunchKernelGGL((gemm_ring_kernel<8, 1, false, true>), grid, dim3(256), lds, stream, g);
-    return (int)hipGetLastError();
+    return prd_launch<gemm_ring_kernel<8, 1, false, true>>(grid, dim3(256), lds, stream, g);
 }
 
 // ---- node-row linears with LARGE weights (the single-track transition 512 -> 2048 -> 512): K split ACROSS workgroups ----------
@@ -1149,16 +1141,13 @@ extern "C" int prd_single_fc1_folded(const float* single, const float* og, const
     if (al & 15) return PRD_ERR_ALIGN;
     const int SK = prd_ceil_div(nslab, spw);
     if ((size_t)SK * M * Hd * sizeof(float) > ws_bytes) return PRD_ERR_WORKSPACE;
-    static std::once_flag once;
-    std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)gemm_slab_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
     const int xmap = slab_xmap(SK, tiles_n);
     const dim3 grid((unsigned)(tiles_m * tiles_n * SK));
     const size_t lds = SL_LDS + (size_t)(SL_BM + SL_BN) * 32 * ex * 2;
-    hipLaunchKernelGGL(gemm_slab_kernel<1>, grid, dim3(SL_NW * 64), lds, stream, single, w1cat, ws, M, Hd, S, S, S + HC, tiles_m, tiles_n, nslab,
-                       spw, xmap, H2_WSCALE, og, HC);
-    hipLaunchKernelGGL(fc1_fold_reduce_kernel<64>, dim3((unsigned)M), dim3(128 * prd_ceil_div(Hd, 512)), 0, stream, ws, SK, M, Hd, S, single, og, woT,
-                       bo, wsum1, w1bo, b1, single_out, h);
-    return (int)hipGetLastError();
+    PRD_TRY(prd_launch<gemm_slab_kernel<1>>(grid, dim3(SL_NW * 64), lds, stream, single, w1cat, ws, M, Hd, S, S, S + HC, tiles_m, tiles_n, nslab,
+                                            spw, xmap, H2_WSCALE, og, HC));
+    return prd_launch<fc1_fold_reduce_kernel<64>>(dim3((unsigned)M), dim3(128 * prd_ceil_div(Hd, 512)), 0, stream, ws, SK, M, Hd, S, single, og, woT,
+                                                  bo, wsum1, w1bo, b1, single_out, h);
 }
 
 extern "C" int prd_gemm_slab_ok(int M, int N, int K, int arith) {
@@ -1184,13 +1173,10 @@ extern "C" int prd_gemm(const PrdGemm* args, hipStream_t stream) {
         if (slab_plan(g.M, g.N, g.K, g.arith, &tiles_m, &tiles_n, &nslab, &spw)) {
             const int SK = prd_ceil_div(nslab, spw);
             if ((size_t)SK * g.M * g.N * sizeof(float) > g.ws_bytes) return PRD_ERR_WORKSPACE;
-            static std::once_flag once;
-            std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)gemm_slab_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
             const int xmap = slab_xmap(SK, tiles_n);
-            hipLaunchKernelGGL(gemm_slab_kernel<0>, dim3((unsigned)(tiles_m * tiles_n * SK)), dim3(SL_NW * 64), SL_LDS, stream, g.A, g.B, g.ws, g.M, g.N,
-                               g.K, g.lda, g.ldb, tiles_m, tiles_n, nslab, spw, xmap, H2_WSCALE, (const float*)nullptr, 0);
-            hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)(g.M * prd_ceil_div(g.N, 512))), dim3(128), 0, stream, g, g.ws, SK);
-            return (int)hipGetLastError();
+            PRD_TRY(prd_launch<gemm_slab_kernel<0>>(dim3((unsigned)(tiles_m * tiles_n * SK)), dim3(SL_NW * 64), SL_LDS, stream, g.A, g.B, g.ws, g.M, g.N,
+                                                    g.K, g.lda, g.ldb, tiles_m, tiles_n, nslab, spw, xmap, H2_WSCALE, (const float*)nullptr, 0));
+            return prd_launch<gemm_slab_reduce_kernel>(dim3((unsigned)(g.M * prd_ceil_div(g.N, 512))), dim3(128), 0, stream, g, g.ws, SK);
         }
     }
     if (g.out_ln) return PRD_ERR_UNSUPPORTED;           // the LayerNorm of the output rows exists on the slab path only (prd_gemm_slab_ok)
@@ -1207,17 +1193,8 @@ extern "C" int prd_gemm(const PrdGemm* args, hipStream_t stream) {
             gx.tile_hint = -8;
             grid.x = 8u * prd_ceil_div(g.M, 64) * prd_ceil_div(prd_ceil_div(g.N, 64), 8);
         }
-        static std::once_flag once1, once4;
-        if (g.K >= 1024) {
-            const size_t lds = (size_t)4 * 2 * 4 * 64 * 64 + 512;
-            std::call_once(once4, [] { (void)hipFuncSetAttribute((const void*)gemm_h2_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-            hipLaunchKernelGGL((gemm_h2_kernel<4>), grid, dim3(1024), lds, stream, gx);
-        } else {
-            const size_t lds = (size_t)2 * 4 * 64 * 64 + 512;
-            std::call_once(once1, [] { (void)hipFuncSetAttribute((const void*)gemm_h2_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-            hipLaunchKernelGGL((gemm_h2_kernel<1>), grid, dim3(256), lds, stream, gx);
-        }
-        return (int)hipGetLastError();
+        if (g.K >= 1024) return prd_launch<gemm_h2_kernel<4>>(grid, dim3(1024), (size_t)4 * 2 * 4 * 64 * 64 + 512, stream, gx);
+        return prd_launch<gemm_h2_kernel<1>>(grid, dim3(256), (size_t)2 * 4 * 64 * 64 + 512, stream, gx);
     }
     // gemm mode 1, latency-bound node-row linears (fewer 64x64 tiles than that): 32x32 tiles with a deep operand ring
     // (batched, e.g. the per-head logits / P V of SPAttention: same kernel, blockIdx.y = batch; without the fused LayerNorm)
@@ -1260,17 +1237,16 @@ extern "C" int prd_gemm(const PrdGemm* args, hipStream_t stream) {
     if (tile == 32) {          // fewer 64x64 tiles than two per CU: skinny kernel, 32x32 tiles + in-workgroup split-K
         dim3 grid(prd_ceil_div(g.M, 32) * prd_ceil_div(g.N, 32), batches);
         // long K and few tiles: 8 K-splits (twice the waves per CU to cover the L2 latency of the operand stream)
-        if (g.a_ln) hipLaunchKernelGGL((gemm_skinny_kernel<4, true>), grid, dim3(256), 0, stream, g);
-        else if (g.K >= 1024 && (long)grid.x * grid.y <= 512) hipLaunchKernelGGL((gemm_skinny_kernel<8, false>), grid, dim3(512), 0, stream, g);
-        else hipLaunchKernelGGL((gemm_skinny_kernel<4, false>), grid, dim3(256), 0, stream, g);
-    } else if (tile == 64) {
-        dim3 grid(prd_ceil_div(g.M, 64) * prd_ceil_div(g.N, 64), batches);
-        hipLaunchKernelGGL((gemm_kernel<32, 32>), grid, dim3(256), 0, stream, g);
-    } else {
-        dim3 grid(prd_ceil_div(g.M, 128) * prd_ceil_div(g.N, 128), batches);
-        hipLaunchKernelGGL((gemm_kernel<64, 64>), grid, dim3(256), 0, stream, g);
+        if (g.a_ln) return prd_launch<gemm_skinny_kernel<4, true>>(grid, dim3(256), 0, stream, g);
+        if (g.K >= 1024 && (long)grid.x * grid.y <= 512) return prd_launch<gemm_skinny_kernel<8, false>>(grid, dim3(512), 0, stream, g);
+        return prd_launch<gemm_skinny_kernel<4, false>>(grid, dim3(256), 0, stream, g);
     }
-    return (int)hipGetLastError();
+    if (tile == 64) {
+        dim3 grid(prd_ceil_div(g.M, 64) * prd_ceil_div(g.N, 64), batches);
+        return prd_launch<gemm_kernel<32, 32>>(grid, dim3(256), 0, stream, g);
+    }
+    dim3 grid(prd_ceil_div(g.M, 128) * prd_ceil_div(g.N, 128), batches);
+    return prd_launch<gemm_kernel<64, 64>>(grid, dim3(256), 0, stream, g);
 }
 
 extern "C" int prd_ln_rows(const float* x, float* y, const float* gamma, const float* beta,
@@ -1279,17 +1255,14 @@ extern "C" int prd_ln_rows(const float* x, float* y, const float* gamma, const f
     const bool al16 = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gamma) |
                         reinterpret_cast<uintptr_t>(beta)) & 15) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0;
     if (C == 64 && al16 && rows >= 4096) {              // the pair-track calls of the training path
-        hipLaunchKernelGGL(ln_rows64_kernel, dim3(prd_ceil_div(rows, 16)), dim3(256), 0, stream, x, y, gamma, beta, rows, ldx, ldy);
-        return (int)hipGetLastError();
+        return prd_launch<ln_rows64_kernel>(dim3(prd_ceil_div(rows, 16)), dim3(256), 0, stream, x, y, gamma, beta, rows, ldx, ldy);
     }
-    hipLaunchKernelGGL(ln_rows_kernel, dim3(prd_ceil_div(rows, 4)), dim3(256), 0, stream, x, y, gamma, beta, rows, C, ldx, ldy);
-    return (int)hipGetLastError();
+    return prd_launch<ln_rows_kernel>(dim3(prd_ceil_div(rows, 4)), dim3(256), 0, stream, x, y, gamma, beta, rows, C, ldx, ldy);
 }
 
 extern "C" int prd_softmax_rows(float* x, int rows, int n, int ld, hipStream_t stream) {
     if (!x || rows <= 0 || n <= 0 || ld < n) return PRD_ERR_ARG;
-    hipLaunchKernelGGL(softmax_rows_kernel, dim3(prd_ceil_div(rows, 4)), dim3(256), 0, stream, x, rows, n, ld);
-    return (int)hipGetLastError();
+    return prd_launch<softmax_rows_kernel>(dim3(prd_ceil_div(rows, 4)), dim3(256), 0, stream, x, rows, n, ld);
 }
 
 extern "C" size_t prd_gemm_slab_workspace(int M, int N, int K) {

@@ -1,0 +1,73 @@
+// Host half of every denoiser kernel launch (libprd_hip.so): the checked launch, the pair_dim dispatch and the launch geometry.
+// Host code only -- nothing here reaches a kernel.  The side libraries (prd_align.hip, prd_tmalign.hip) do not include it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <mutex>
+
+// ---- 1. the launch ---------------------------------------------------------------------------------------------------------------
+// Dynamic LDS up to PRD_LDS_DEFAULT_LIMIT needs no attribute; a launch that asks for more first raises the kernel's limit to the
+// hardware maximum, once per process and kernel (thread-safe: std::call_once; not a stream operation, so it is legal during hipGraph
+// capture).  The result of the raise is kept: if it failed, nothing is launched and every call returns that error.
+constexpr size_t PRD_LDS_DEFAULT_LIMIT = 48 * 1024;
+constexpr int PRD_LDS_MAX = 160 * 1024;
+
+// launches Kernel<<<grid, block, lds, stream>>>(args...); returns 0 or the hipError_t of the raise / the launch
+template <auto Kernel, class... Args>
+static int prd_launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+    if (lds > PRD_LDS_DEFAULT_LIMIT) {
+        static std::once_flag once;
+        static hipError_t raised = hipSuccess;
+        std::call_once(once, [] { raised = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PRD_LDS_MAX); });
+        if (raised != hipSuccess) return (int)raised;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+    return (int)hipGetLastError();
+}
+
+// an entry point with several launches returns the first non-zero result and launches nothing after it
+#define PRD_TRY(launch)                                                                                         \
+    do {                                                                                                        \
+        const int prd_e_ = (launch);                                                                            \
+        if (prd_e_) return prd_e_;                                                                              \
+    } while (0)
+
+// ---- 2. run-time value -> compile-time constant ------------------------------------------------------------------------------------
+// PRD_FOR_P(P, PP, expr) evaluates expr once with `constexpr int PP` bound to 64 or 32 (pair_dim is validated by the caller), so a
+// launch is written once:  return PRD_FOR_P(P, PP, prd_launch<kernel<PP, 8>>(grid, block, lds, stream, ...));
+// A second choice nests:   PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3, B3, prd_launch<kernel<PP, B3>>(...)))
+#define PRD_WITH(T, NAME, VALUE, ...) [&] { constexpr T NAME = VALUE; return __VA_ARGS__; }()
+// v is A or anything else (-> B)
+#define PRD_FOR_2(v, NAME, A, B, ...) ((v) == (A) ? PRD_WITH(int, NAME, A, __VA_ARGS__) : PRD_WITH(int, NAME, B, __VA_ARGS__))
+#define PRD_FOR_P(P, PP, ...) PRD_FOR_2(P, PP, 64, 32, __VA_ARGS__)
+#define PRD_FOR_BOOL(v, NAME, ...) ((v) ? PRD_WITH(bool, NAME, true, __VA_ARGS__) : PRD_WITH(bool, NAME, false, __VA_ARGS__))
+// v is A, B or anything else (-> C)
+#define PRD_FOR_3(v, NAME, A, B, C, ...) \
+    ((v) == (A) ? PRD_WITH(int, NAME, A, __VA_ARGS__) : (v) == (B) ? PRD_WITH(int, NAME, B, __VA_ARGS__) : PRD_WITH(int, NAME, C, __VA_ARGS__))
+
+// ---- 3. launch geometry ------------------------------------------------------------------------------------------------------------
+// persistent workgroups over a task queue: per_wg tasks per workgroup, between 1 and cap workgroups
+static inline int grid_for(long tasks, int per_wg, int cap) {
+    long g = (tasks + per_wg - 1) / per_wg;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
+// persistent workgroups over the rows of one head (grid = result * H; cap = workgroups a head may have): the SMALLEST count that
+// reaches the minimum number of row rounds, so every workgroup walks the same number of rows
+static inline long prd_rows_per_head(long rows_total, long cap) {
+    long per_head = cap < rows_total ? cap : rows_total;
+    if (per_head < 1) per_head = 1;
+    const long rounds = (rows_total + per_head - 1) / per_head;
+    return (rows_total + rounds - 1) / rounds;
+}
+
+// the same, as a multiple of 8 rows in flight per head (never more rounds, never above cap): the kernels then keep the head-workgroups
+// of a row on ONE XCD, whose L2 serves the row to all of them.  (N = 769, H = 4: 60 -> 64 rows in flight.)  xcd8 = false: the A/B
+// switch PRD_TUNE_TA2_NO_XCD8
+static inline long prd_rows_per_head_xcd8(long rows_total, long cap, bool xcd8 = true) {
+    long per_head = prd_rows_per_head(rows_total, cap);
+    if (per_head >= 8 && xcd8) per_head = (per_head + 7) / 8 * 8;
+    if (per_head > cap) per_head = cap;
+    return per_head;
+}

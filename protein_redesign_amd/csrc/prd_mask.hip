@@ -5,6 +5,7 @@
 // atomics, plain vector stores.  A few microseconds of work: nothing here is tuned.
 #include "prd_common.h"
 #include "../../include/prd_hip.h"
+#include "prd_launch.h"
 
 namespace {
 
@@ -288,12 +289,10 @@ extern "C" int prd_mask_lowest_k(float* extra, float* inv, int64_t* tokens, cons
     if ((mode == PRD_MASK_SPATIAL || ligand) && (!atom_pos || !atom_mask || !ca_pos || ld_ca < 3)) return PRD_ERR_ARG;
     if (ligand) {
         if (mode == PRD_MASK_LIGAND_NEAREST && N > MASK_LIGAND_MAX_N) return PRD_ERR_UNSUPPORTED;   // one verdict bit per owned position
-        hipLaunchKernelGGL(mask_ligand_kernel, dim3(b), dim3(MASK_WG), 0, stream, extra, inv, tokens, residue_mask, atom_pos, atom_mask,
-                           ca_pos, ld_ca, p, mode == PRD_MASK_LIGAND_WITHIN ? 1 : 0, N);
-        return (int)hipGetLastError();
+        return prd_launch<mask_ligand_kernel>(dim3(b), dim3(MASK_WG), 0, stream, extra, inv, tokens, residue_mask, atom_pos, atom_mask,
+                                              ca_pos, ld_ca, p, mode == PRD_MASK_LIGAND_WITHIN ? 1 : 0, N);
     }
     if (b > MASK_WG) return PRD_ERR_UNSUPPORTED;        // one thread per sample finds the median of the counts
-    hipLaunchKernelGGL(mask_lowest_k_kernel, dim3(b), dim3(MASK_WG), 0, stream, extra, inv, tokens, residue_mask, key, atom_pos, atom_mask,
-                       ca_pos, ld_ca, p, mode == PRD_MASK_SPATIAL ? 1 : 0, b, N);
-    return (int)hipGetLastError();
+    return prd_launch<mask_lowest_k_kernel>(dim3(b), dim3(MASK_WG), 0, stream, extra, inv, tokens, residue_mask, key, atom_pos, atom_mask,
+                                            ca_pos, ld_ca, p, mode == PRD_MASK_SPATIAL ? 1 : 0, b, N);
 }

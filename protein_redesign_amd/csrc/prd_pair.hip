@@ -6,7 +6,7 @@
 #include "prd_common.h"
 #include <cstdlib>
 #include "../../include/prd_hip.h"
-#include <mutex>
+#include "prd_launch.h"
 
 #ifdef PRD_TIMING     // diagnostic builds only (tools/phase_timing.py): cycles per phase summed over the tasks of a wave
 __device__ unsigned long long prd_dbg_pair[256 * 16 * 8];
@@ -1455,25 +1455,7 @@ __global__ __launch_bounds__(256) void step_boundary_kernel(
     }
 }
 
-int grid_for(long tasks, int per_wg, int cap) {
-    long g = (tasks + per_wg - 1) / per_wg;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 }  // namespace
-
-// raise the dynamic-LDS limit of a kernel to the hardware maximum, once per process and kernel (thread-safe: std::call_once;
-// not a stream operation, so it is legal during hipGraph capture)
-#define PRD_SET_LDS(kernel, bytes)                                                                              \
-    do {                                                                                                        \
-        static std::once_flag prd_lds_once;                                                                     \
-        std::call_once(prd_lds_once, [] {                                                                       \
-            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        });                                                                                                     \
-        (void)(bytes);                                                                                          \
-    } while (0)
 
 #define PRD_CHECK_P(P) if ((P) != 32 && (P) != 64) return PRD_ERR_UNSUPPORTED
 
@@ -1489,32 +1471,28 @@ extern "C" int prd_static_pair(float* out, const float* atom_mask, const float* 
         !chain_index || !tab_b0 || !tab_b1 || !tab_b2 || !tab_bdist || !tab_relpos || b <= 0 || N <= 0) return PRD_ERR_ARG;
     if (P & 3) return PRD_ERR_ALIGN;
     const long total = (long)b * N * N * (P / 4);
-    hipLaunchKernelGGL(static_pair_kernel, dim3(grid_for(total, 256, 4096)), dim3(256), 0, stream, out, atom_mask,
-                       residue_mask, bond_mask, bond_feats, bond_distance, residue_index, chain_index, tab_b0, tab_b1,
-                       tab_b2, tab_bdist, tab_relpos, max_bond_distance, max_relpos, b, N, P);
-    return (int)hipGetLastError();
+    return prd_launch<static_pair_kernel>(dim3(grid_for(total, 256, 4096)), dim3(256), 0, stream, out, atom_mask, residue_mask, bond_mask,
+                                          bond_feats, bond_distance, residue_index, chain_index, tab_b0, tab_b1, tab_b2, tab_bdist, tab_relpos,
+                                          max_bond_distance, max_relpos, b, N, P);
 }
 
 extern "C" int prd_atom_embed(float* out, const int64_t* atom_feats, const float* atom_mask, const float* tables,
                               const int* offsets, int n_feats, int b, int N, int S, hipStream_t stream) {
     if (!out || !atom_feats || !atom_mask || !tables || !offsets || n_feats <= 0 || b <= 0 || N <= 0 || S <= 0) return PRD_ERR_ARG;
-    hipLaunchKernelGGL(atom_embed_kernel, dim3(grid_for((long)b * N * S, 256, 2048)), dim3(256), 0, stream, out,
-                       atom_feats, atom_mask, tables, offsets, n_feats, b * N, S);
-    return (int)hipGetLastError();
+    return prd_launch<atom_embed_kernel>(dim3(grid_for((long)b * N * S, 256, 2048)), dim3(256), 0, stream, out, atom_feats, atom_mask, tables,
+                                         offsets, n_feats, b * N, S);
 }
 
 extern "C" int prd_single_init(float* single, const float* static_single, const float* seq_t, const float* residue_mask,
                                const float* w_rt, int rows, int S, int n_cls, hipStream_t stream) {
     if (!single || !static_single || !seq_t || !residue_mask || !w_rt || rows <= 0 || S <= 0 || n_cls <= 0 || n_cls > 64) return PRD_ERR_ARG;
-    hipLaunchKernelGGL(single_init_kernel, dim3(rows), dim3(128), 0, stream, single, static_single, seq_t, residue_mask, w_rt, S, n_cls);
-    return (int)hipGetLastError();
+    return prd_launch<single_init_kernel>(dim3(rows), dim3(128), 0, stream, single, static_single, seq_t, residue_mask, w_rt, S, n_cls);
 }
 
 extern "C" int prd_time_embed(float* ebeta, const int64_t* t, const float* freqs, const float* w_beta,
                               int num_steps, int b, int P, int time_dim, hipStream_t stream) {
     if (!ebeta || !t || !freqs || !w_beta || num_steps <= 0 || b <= 0 || P <= 0 || time_dim <= 0 || (time_dim & 1)) return PRD_ERR_ARG;
-    hipLaunchKernelGGL(time_embed_kernel, dim3(b), dim3(64), time_dim * sizeof(float), stream, ebeta, t, freqs, w_beta, num_steps, P, time_dim);
-    return (int)hipGetLastError();
+    return prd_launch<time_embed_kernel>(dim3(b), dim3(64), time_dim * sizeof(float), stream, ebeta, t, freqs, w_beta, num_steps, P, time_dim);
 }
 
 extern "C" int prd_pair_init(float* pair, const float* static_pair, const float* z, const float* mask,
@@ -1530,23 +1508,11 @@ extern "C" int prd_pair_init(float* pair, const float* static_pair, const float*
     const int grid = grid_for(ntask, 4, 512);
     if (arith == PRD_ARITH_SPLIT16 && (dist_dim % 128) == 0) {        // fp16 x 2 split operands
         const size_t lds2 = (size_t)4 * P * dist_dim + (size_t)dist_dim * 4;
-        if (P == 64) {
-            PRD_SET_LDS(pair_init_h2_kernel<64>, lds2);
-            hipLaunchKernelGGL(pair_init_h2_kernel<64>, dim3(grid), dim3(WG), lds2, stream, pair, static_pair, z, mask, centers, w_dist, ebeta, b, N, dist_dim);
-        } else {
-            PRD_SET_LDS(pair_init_h2_kernel<32>, lds2);
-            hipLaunchKernelGGL(pair_init_h2_kernel<32>, dim3(grid), dim3(WG), lds2, stream, pair, static_pair, z, mask, centers, w_dist, ebeta, b, N, dist_dim);
-        }
-        return (int)hipGetLastError();
+        return PRD_FOR_P(P, PP, prd_launch<pair_init_h2_kernel<PP>>(dim3(grid), dim3(WG), lds2, stream, pair, static_pair, z, mask, centers, w_dist,
+                                                                    ebeta, b, N, dist_dim));
     }
-    if (P == 64) {
-        PRD_SET_LDS(pair_init_kernel<64>, lds);
-        hipLaunchKernelGGL(pair_init_kernel<64>, dim3(grid), dim3(WG), lds, stream, pair, static_pair, z, mask, centers, w_dist, ebeta, b, N, dist_dim);
-    } else {
-        PRD_SET_LDS(pair_init_kernel<32>, lds);
-        hipLaunchKernelGGL(pair_init_kernel<32>, dim3(grid), dim3(WG), lds, stream, pair, static_pair, z, mask, centers, w_dist, ebeta, b, N, dist_dim);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<pair_init_kernel<PP>>(dim3(grid), dim3(WG), lds, stream, pair, static_pair, z, mask, centers, w_dist, ebeta,
+                                                             b, N, dist_dim));
 }
 
 extern "C" int prd_pair_bias(float* bias_out, const float* pair, const float* gamma, const float* beta,
@@ -1556,9 +1522,8 @@ extern "C" int prd_pair_bias(float* bias_out, const float* pair, const float* ga
     const long ntask = ((long)b * N * N + 31) / 32;
     const int grid = grid_for(ntask, 4, 2048);
     const float* nul = nullptr;
-    if (P == 64) hipLaunchKernelGGL(pair_bias_kernel<64>, dim3(grid), dim3(WG), 0, stream, bias_out, pair, gamma, beta, w, bvec, (float*)nullptr, nul, nul, nul, nul, 0, b, N, H);
-    else hipLaunchKernelGGL(pair_bias_kernel<32>, dim3(grid), dim3(WG), 0, stream, bias_out, pair, gamma, beta, w, bvec, (float*)nullptr, nul, nul, nul, nul, 0, b, N, H);
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<pair_bias_kernel<PP>>(dim3(grid), dim3(WG), 0, stream, bias_out, pair, gamma, beta, w, bvec, (float*)nullptr,
+                                                             nul, nul, nul, nul, 0, b, N, H));
 }
 
 extern "C" int prd_pair_bias2(float* bias_a, const float* pair, const float* gamma_a, const float* beta_a, const float* w_a,
@@ -1569,11 +1534,8 @@ extern "C" int prd_pair_bias2(float* bias_a, const float* pair, const float* gam
     PRD_CHECK_P(P);
     const long ntask = ((long)b * N * N + 31) / 32;
     const int grid = grid_for(ntask, 4, 2048);
-    if (P == 64) hipLaunchKernelGGL(pair_bias_kernel<64>, dim3(grid), dim3(WG), 0, stream, bias_a, pair, gamma_a, beta_a, w_a, bvec_a,
-                                    bias_b, gamma_b, beta_b, w_b, bvec_b, Hb, b, N, Ha);
-    else hipLaunchKernelGGL(pair_bias_kernel<32>, dim3(grid), dim3(WG), 0, stream, bias_a, pair, gamma_a, beta_a, w_a, bvec_a,
-                            bias_b, gamma_b, beta_b, w_b, bvec_b, Hb, b, N, Ha);
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<pair_bias_kernel<PP>>(dim3(grid), dim3(WG), 0, stream, bias_a, pair, gamma_a, beta_a, w_a, bvec_a, bias_b,
+                                                             gamma_b, beta_b, w_b, bvec_b, Hb, b, N, Ha));
 }
 
 extern "C" int prd_pair_head_supported(int P, int dist_dim, int C, int arith) {
@@ -1598,18 +1560,9 @@ extern "C" int prd_pair_head(float* pair, const float* static_pair, const float*
     const size_t lds = (size_t)4 * P * dist_dim + (size_t)4 * P * C + ((size_t)dist_dim + P + 16 * P + 4 * P) * 4;
     const long ntask = (long)b * N * prd_ceil_div(N, 32);
     const int grid = grid_for(ntask, NWH, 256);
-    if (P == 64) {
-        PRD_SET_LDS((pair_head_h2_kernel<64, NWH>), lds);
-        hipLaunchKernelGGL((pair_head_h2_kernel<64, NWH>), dim3(grid), dim3(NWH * 64), lds, stream, pair, static_pair, z, mask, centers, w_dist,
-                           ebeta, dist_dim, ab, w_out, b_out, C, apply_mask, bias_a, gamma_a, beta_a, w_a, bvec_a, Ha, bias_b, gamma_b, beta_b,
-                           w_b, bvec_b, Hb, b, N);
-    } else {
-        PRD_SET_LDS((pair_head_h2_kernel<32, NWH>), lds);
-        hipLaunchKernelGGL((pair_head_h2_kernel<32, NWH>), dim3(grid), dim3(NWH * 64), lds, stream, pair, static_pair, z, mask, centers, w_dist,
-                           ebeta, dist_dim, ab, w_out, b_out, C, apply_mask, bias_a, gamma_a, beta_a, w_a, bvec_a, Ha, bias_b, gamma_b, beta_b,
-                           w_b, bvec_b, Hb, b, N);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<pair_head_h2_kernel<PP, NWH>>(dim3(grid), dim3(NWH * 64), lds, stream, pair, static_pair, z, mask, centers,
+                                                                     w_dist, ebeta, dist_dim, ab, w_out, b_out, C, apply_mask, bias_a, gamma_a,
+                                                                     beta_a, w_a, bvec_a, Ha, bias_b, gamma_b, beta_b, w_b, bvec_b, Hb, b, N));
 }
 
 extern "C" int prd_opm_pair(float* out, const float* pair, const float* ab, const float* mask, const float* w_out,
@@ -1624,23 +1577,10 @@ extern "C" int prd_opm_pair(float* out, const float* pair, const float* ab, cons
     const int grid = grid_for(ntask, 4, 1024);
     if (arith == PRD_ARITH_SPLIT16 && (C % 128) == 0) {               // fp16 x 2 split operands
         const size_t lds2 = (size_t)4 * P * C + (size_t)P * 4;
-        if (P == 64) {
-            PRD_SET_LDS(opm_pair_h2_kernel<64>, lds2);
-            hipLaunchKernelGGL(opm_pair_h2_kernel<64>, dim3(grid), dim3(WG), lds2, stream, out, pair, ab, mask, w_out, b_out, b, N, C, flags);
-        } else {
-            PRD_SET_LDS(opm_pair_h2_kernel<32>, lds2);
-            hipLaunchKernelGGL(opm_pair_h2_kernel<32>, dim3(grid), dim3(WG), lds2, stream, out, pair, ab, mask, w_out, b_out, b, N, C, flags);
-        }
-        return (int)hipGetLastError();
+        return PRD_FOR_P(P, PP, prd_launch<opm_pair_h2_kernel<PP>>(dim3(grid), dim3(WG), lds2, stream, out, pair, ab, mask, w_out, b_out, b, N, C,
+                                                                   flags));
     }
-    if (P == 64) {
-        PRD_SET_LDS(opm_pair_kernel<64>, lds);
-        hipLaunchKernelGGL(opm_pair_kernel<64>, dim3(grid), dim3(WG), lds, stream, out, pair, ab, mask, w_out, b_out, b, N, C, flags);
-    } else {
-        PRD_SET_LDS(opm_pair_kernel<32>, lds);
-        hipLaunchKernelGGL(opm_pair_kernel<32>, dim3(grid), dim3(WG), lds, stream, out, pair, ab, mask, w_out, b_out, b, N, C, flags);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<opm_pair_kernel<PP>>(dim3(grid), dim3(WG), lds, stream, out, pair, ab, mask, w_out, b_out, b, N, C, flags));
 }
 
 namespace {
@@ -1876,15 +1816,8 @@ extern "C" int prd_outer_linear(float* out, const float* pair, const float* x, c
         const int grid = (int)(ntile < 256 ? ntile : 256);
         const size_t ldsp = (size_t)2 * 8 * (P / 32 * 4) * 64 * 16, ldss = (size_t)8 * 32 * ((S / 8) * 4 + 16);
         const size_t ldsk = ldsp > ldss ? ldsp : ldss;             // two partial buffers; the staging tiles alias them
-#define PRD_OLKS(PP, KK)                                                                                               \
-        do {                                                                                                           \
-            PRD_SET_LDS((outer_linear_ks_kernel<PP, KK>), ldsk);                                                       \
-            hipLaunchKernelGGL((outer_linear_ks_kernel<PP, KK>), dim3(grid), dim3(512), ldsk, stream, out, pair, x, u, w, bias, b, N, residual, ldu); \
-        } while (0)
-        if (P == 64) { if (S == 512) PRD_OLKS(64, 4); else if (S == 256) PRD_OLKS(64, 2); else PRD_OLKS(64, 1); }
-        else { if (S == 512) PRD_OLKS(32, 4); else if (S == 256) PRD_OLKS(32, 2); else PRD_OLKS(32, 1); }
-#undef PRD_OLKS
-        return (int)hipGetLastError();
+        return PRD_FOR_P(P, PP, PRD_FOR_3(S, SS, 512, 256, 128,           // a wave's slice of K = S: 4, 2 or 1 x 16 values per lane
+            prd_launch<outer_linear_ks_kernel<PP, SS / 128>>(dim3(grid), dim3(512), ldsk, stream, out, pair, x, u, w, bias, b, N, residual, ldu)));
     }
     if (arith == PRD_ARITH_SPLIT16 && (S % 128) == 0 && (size_t)4 * P * S + 4 * P <= 160 * 1024) {   // fp16 x 2 split operands
         constexpr int NWL = 8;
@@ -1892,14 +1825,8 @@ extern "C" int prd_outer_linear(float* out, const float* pair, const float* x, c
         const long nsym = (long)b * (nvb * (nvb + 1) / 2) * 32;
         const int grid = grid_for(nsym, 4, 256);
         const size_t lds2 = (size_t)4 * P * S + 4 * P;
-        if (P == 64) {
-            PRD_SET_LDS((outer_linear_res_h2_kernel<64, NWL>), lds2);
-            hipLaunchKernelGGL((outer_linear_res_h2_kernel<64, NWL>), dim3(grid), dim3(NWL * 64), lds2, stream, out, pair, x, u, w, bias, b, N, S, residual, ldu);
-        } else {
-            PRD_SET_LDS((outer_linear_res_h2_kernel<32, NWL>), lds2);
-            hipLaunchKernelGGL((outer_linear_res_h2_kernel<32, NWL>), dim3(grid), dim3(NWL * 64), lds2, stream, out, pair, x, u, w, bias, b, N, S, residual, ldu);
-        }
-        return (int)hipGetLastError();
+        return PRD_FOR_P(P, PP, prd_launch<outer_linear_res_h2_kernel<PP, NWL>>(dim3(grid), dim3(NWL * 64), lds2, stream, out, pair, x, u, w, bias,
+                                                                                b, N, S, residual, ldu));
     }
     if (lds <= 150 * 1024 && (S % 64) == 0) {   // W1 resident in LDS: persistent 8-wave workgroups, queue-fed
         constexpr int NWL = 8;
@@ -1908,19 +1835,11 @@ extern "C" int prd_outer_linear(float* out, const float* pair, const float* x, c
         const int grid = grid_for(nsym, 4, 256);
         // fewer tasks than resident waves (symmetric half): the static assignment beats the queue (56 vs 74 us at N = 320)
         int* oq = (nsym > (long)grid * NWL) ? queue : nullptr;
-        if (P == 64) {
-            PRD_SET_LDS((outer_linear_res_kernel<64, NWL>), lds);
-            hipLaunchKernelGGL((outer_linear_res_kernel<64, NWL>), dim3(grid), dim3(NWL * 64), lds, stream, oq, out, pair, x, u, w, bias, b, N, S, residual, ldu);
-        } else {
-            PRD_SET_LDS((outer_linear_res_kernel<32, NWL>), lds);
-            hipLaunchKernelGGL((outer_linear_res_kernel<32, NWL>), dim3(grid), dim3(NWL * 64), lds, stream, oq, out, pair, x, u, w, bias, b, N, S, residual, ldu);
-        }
-        return (int)hipGetLastError();
+        return PRD_FOR_P(P, PP, prd_launch<outer_linear_res_kernel<PP, NWL>>(dim3(grid), dim3(NWL * 64), lds, stream, oq, out, pair, x, u, w, bias,
+                                                                             b, N, S, residual, ldu));
     }
     const int grid = grid_for(ntask, 4, 1024);       // very wide single track: stream W1 through LDS in K chunks
-    if (P == 64) hipLaunchKernelGGL(outer_linear_kernel<64>, dim3(grid), dim3(WG), 0, stream, out, pair, x, u, w, bias, b, N, S, residual, ldu);
-    else hipLaunchKernelGGL(outer_linear_kernel<32>, dim3(grid), dim3(WG), 0, stream, out, pair, x, u, w, bias, b, N, S, residual, ldu);
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<outer_linear_kernel<PP>>(dim3(grid), dim3(WG), 0, stream, out, pair, x, u, w, bias, b, N, S, residual, ldu));
 }
 
 namespace {
@@ -1932,10 +1851,8 @@ int launch_pair_tail_h2(float* out, const float* pair, const float* og, const fl
     const size_t lds = ((size_t)2 * 4 * P * (P / 8) + (size_t)2 * P * (4 * P / 8) + (size_t)2 * P * 8) * 16 + (size_t)(4 * P + 2 * P + 8 * P) * 4;
     if (lds > 160 * 1024) return PRD_ERR_UNSUPPORTED;
     const int grid = grid_for((rows + 31) / 32, 4, 256);
-    PRD_SET_LDS((pair_tail_h2_kernel<P, NWH>), lds);
-    hipLaunchKernelGGL((pair_tail_h2_kernel<P, NWH>), dim3(grid), dim3(NWH * 64), lds, stream, out, pair, og, wo, bo, w1, b1, w2, b2,
-                       bias_w, bias_b, bias_out, H, rows, nn, residual);
-    return (int)hipGetLastError();
+    return prd_launch<pair_tail_h2_kernel<P, NWH>>(dim3(grid), dim3(NWH * 64), lds, stream, out, pair, og, wo, bo, w1, b1, w2, b2, bias_w, bias_b,
+                                                   bias_out, H, rows, nn, residual);
 }
 }  // namespace
 
@@ -1953,14 +1870,8 @@ extern "C" int prd_pair_transition(float* out, const float* pair, const float* w
     const long rows = (long)b * N * N;
     const size_t lds = ((size_t)4 * P * (P + 4) + (size_t)P * (4 * P + 4) + 5 * P) * sizeof(float);
     const int grid = grid_for((rows + 31) / 32, 4, 256);
-    if (P == 64) {
-        PRD_SET_LDS((pair_transition_kernel<64, NWT>), lds);
-        hipLaunchKernelGGL((pair_transition_kernel<64, NWT>), dim3(grid), dim3(NWT * 64), lds, stream, queue, out, pair, w1, b1, w2, b2, rows, residual);
-    } else {
-        PRD_SET_LDS((pair_transition_kernel<32, NWT>), lds);
-        hipLaunchKernelGGL((pair_transition_kernel<32, NWT>), dim3(grid), dim3(NWT * 64), lds, stream, queue, out, pair, w1, b1, w2, b2, rows, residual);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<pair_transition_kernel<PP, NWT>>(dim3(grid), dim3(NWT * 64), lds, stream, queue, out, pair, w1, b1, w2, b2,
+                                                                        rows, residual));
 }
 
 extern "C" int prd_block_tail(float* pair, const float* og, const float* wo, const float* bo, const float* w1, const float* b1,
@@ -1982,14 +1893,8 @@ extern "C" int prd_block_tail(float* pair, const float* og, const float* wo, con
     const int grid = grid_for((rows + 31) / 32, 4, 256);
     // measured at N = 320: static round-robin 87 us, queue 93 us (8-wave workgroups, < 2 tasks per wave); queue beyond that
     int* bq = ((rows + 31) / 32 > (long)2 * grid * NWT) ? queue : nullptr;
-    if (P == 64) {
-        PRD_SET_LDS((block_tail_kernel<64, NWT>), lds);
-        hipLaunchKernelGGL((block_tail_kernel<64, NWT>), dim3(grid), dim3(NWT * 64), lds, stream, bq, pair, og, wo, bo, w1, b1, w2, b2, bias_w, bias_b, bias_out, H, rows, (long)N * N);
-    } else {
-        PRD_SET_LDS((block_tail_kernel<32, NWT>), lds);
-        hipLaunchKernelGGL((block_tail_kernel<32, NWT>), dim3(grid), dim3(NWT * 64), lds, stream, bq, pair, og, wo, bo, w1, b1, w2, b2, bias_w, bias_b, bias_out, H, rows, (long)N * N);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<block_tail_kernel<PP, NWT>>(dim3(grid), dim3(NWT * 64), lds, stream, bq, pair, og, wo, bo, w1, b1, w2, b2,
+                                                                   bias_w, bias_b, bias_out, H, rows, (long)N * N));
 }
 
 extern "C" int prd_coord_head(float* eps_raw, const float* pair, const float* z, const float* mask,
@@ -1999,25 +1904,21 @@ extern "C" int prd_coord_head(float* eps_raw, const float* pair, const float* z,
     PRD_CHECK_P(P);
     const int grid = grid_for((long)b * N, 1, 2048);
     const bool b3 = arith == PRD_ARITH_SPLIT16;
-#define PRD_CH(PP, BB) hipLaunchKernelGGL((coord_head_kernel<PP, BB>), dim3(grid), dim3(WG), 0, stream, eps_raw, pair, z, mask, w1, b1, w2, b, N)
-    if (P == 64) { if (b3) PRD_CH(64, true); else PRD_CH(64, false); }
-    else { if (b3) PRD_CH(32, true); else PRD_CH(32, false); }
-#undef PRD_CH
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3, BB,
+        prd_launch<coord_head_kernel<PP, BB>>(dim3(grid), dim3(WG), 0, stream, eps_raw, pair, z, mask, w1, b1, w2, b, N)));
 }
 
 extern "C" int prd_remove_mean(float* out, const float* x, const float* mask, int b, int N, int D, hipStream_t stream) {
     if (!out || !x || !mask || b <= 0 || N <= 0 || D <= 0 || D > 64) return PRD_ERR_ARG;
-    hipLaunchKernelGGL(remove_mean_kernel, dim3(b), dim3(256), 0, stream, out, x, mask, N, D);
-    return (int)hipGetLastError();
+    return prd_launch<remove_mean_kernel>(dim3(b), dim3(256), 0, stream, out, x, mask, N, D);
 }
 
 extern "C" int prd_reverse_update(float* z, float* seq_t, int64_t* t, const float* noise_pred, const float* seq_pred,
                                   const float* noise, const float* mask, const float* coef,
                                   int b, int N, int n_cls, int num_steps, hipStream_t stream) {
     if (!z || !seq_t || !t || !noise_pred || !seq_pred || !noise || !mask || !coef || b <= 0 || N <= 0 || n_cls <= 0) return PRD_ERR_ARG;
-    hipLaunchKernelGGL(reverse_update_kernel, dim3(b), dim3(256), 0, stream, z, seq_t, t, noise_pred, seq_pred, noise, mask, coef, N, n_cls, num_steps);
-    return (int)hipGetLastError();
+    return prd_launch<reverse_update_kernel>(dim3(b), dim3(256), 0, stream, z, seq_t, t, noise_pred, seq_pred, noise, mask, coef, N, n_cls,
+                                             num_steps);
 }
 
 extern "C" int prd_step_boundary(float* z, float* seq_t, int64_t* t, const float* eps_raw, float* seq_pred,
@@ -2032,8 +1933,7 @@ extern "C" int prd_step_boundary(float* z, float* seq_t, int64_t* t, const float
     if (seq_h && (!w_seq || S_h <= 0)) return PRD_ERR_ARG;
     if (seq_h && ((S_h & 3) || (ldh & 3) || ldh < S_h)) return PRD_ERR_ALIGN;
     const int nblk = prd_ceil_div(N, SB_NODES), neb = prd_ceil_div(P, 4);
-    hipLaunchKernelGGL(step_boundary_kernel<21>, dim3(b * (nblk + neb)), dim3(256), 0, stream, z, seq_t, t, eps_raw, seq_pred, noise, mask, coef,
-                       single_next, static_single, residue_mask, w_rt, ebeta_next, freqs, w_beta, sync, b, N, num_steps, S, P,
-                       time_dim, nblk, neb, seq_h, ldh, w_seq, S_h);
-    return (int)hipGetLastError();
+    return prd_launch<step_boundary_kernel<21>>(dim3(b * (nblk + neb)), dim3(256), 0, stream, z, seq_t, t, eps_raw, seq_pred, noise, mask, coef,
+                                                single_next, static_single, residue_mask, w_rt, ebeta_next, freqs, w_beta, sync, b, N, num_steps, S,
+                                                P, time_dim, nblk, neb, seq_h, ldh, w_seq, S_h);
 }

@@ -24,7 +24,7 @@
 //            workspace and spa_attn_merge_kernel combines the parts (w_p = 2^(max_p - max), o = gate * sum w_p O_p / sum w_p l_p).
 #include "prd_common.h"
 #include "../../include/prd_hip.h"
-#include <mutex>
+#include "prd_launch.h"
 
 namespace {
 
@@ -401,12 +401,10 @@ extern "C" int prd_spa_attn_core(float* o, const float* qkvg, int ldq, const flo
     if (KP > 1 && (!ws || ws_bytes < prd_spa_attn_core_workspace(b, N, H, c))) return PRD_ERR_WORKSPACE;
     const int grid = b * H * nqb * KP;
     const size_t lds = spa_lds_bytes(c);
-    static std::once_flag once;
-    std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)spa_attn_part_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    hipLaunchKernelGGL(spa_attn_part_kernel, dim3(grid), dim3(SPA_NT), lds, stream, o, ws, qkvg, ldq, bias, mask, b, N, H, c, KP, nqb);
+    PRD_TRY(prd_launch<spa_attn_part_kernel>(dim3(grid), dim3(SPA_NT), lds, stream, o, ws, qkvg, ldq, bias, mask, b, N, H, c, KP, nqb));
     if (KP > 1) {
         const long total = (long)b * N * (H * c / 4);
-        hipLaunchKernelGGL(spa_attn_merge_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, o, ws, qkvg, ldq, b, N, H, c, KP);
+        return prd_launch<spa_attn_merge_kernel>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, o, ws, qkvg, ldq, b, N, H, c, KP);
     }
-    return (int)hipGetLastError();
+    return 0;
 }

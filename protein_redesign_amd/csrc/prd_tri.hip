@@ -22,7 +22,7 @@
 #include "../../include/prd_hip.h"
 #include <atomic>
 #include <cstdlib>
-#include <mutex>
+#include "prd_launch.h"
 
 #ifdef PRD_TIMING     // diagnostic builds only (tools/ta_timing.py, tools/phase_timing.py): in-kernel cycle stamps
 __device__ unsigned long long prd_dbg[256 * 16 * 8 * 4];
@@ -1153,7 +1153,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_kernel(
         slot = blockIdx.x / H;
     }
     const float sc = 0.25f * LOG2E;            // 1/sqrt(c) (modules.py:176,216) in the exp2 domain, folded into Wq
-    if (B3) {       // one image of 64 rows; stage_weight_b3 takes (first row pointer, rows staged, plane stride in rows)
+    if (B3) {       // one image of 64 rows; stage_weight_b3_rows takes (first row pointer, rows staged, plane stride in rows)
         u32x4* Wb = reinterpret_cast<u32x4*>(Wl);
         constexpr int PITCH = 2 * (P / 16) + 1;
         stage_weight_b3_rows<P>(Wb, 64, 0, wk + (long)h * C * P, C, P, tid, NT, 1.0f);
@@ -2209,54 +2209,23 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_out_kernel(int* queue, float
     }
 }
 
-int grid_for(long tasks, int per_wg, int cap) {
-    long g = (tasks + per_wg - 1) / per_wg;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 }  // namespace
 
-// raise the dynamic-LDS limit of a kernel to the hardware maximum, once per process and kernel (thread-safe: std::call_once;
-// not a stream operation, so it is legal during hipGraph capture)
-#define PRD_SET_LDS(kernel, bytes)                                                                              \
-    do {                                                                                                        \
-        static std::once_flag prd_lds_once;                                                                     \
-        std::call_once(prd_lds_once, [] {                                                                       \
-            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        });                                                                                                     \
-        (void)(bytes);                                                                                          \
-    } while (0)
-
 // the split contraction by the A/B switches of the caller (waves per workgroup; chunks of operands in flight)
-static void launch_contract_split(int tune, int grid, size_t lds3, hipStream_t stream, float* O, const float* AB, int N, int ldn, int P, int nbatch,
-                                  int tiles, int swap, const unsigned* a_amax = nullptr) {
-    if (a_amax) {       // the scaled first operand of the backward: one form (8 waves)
-        PRD_SET_LDS((tri_mul_contract_split_kernel<8, 2, true>), lds3);
-        hipLaunchKernelGGL((tri_mul_contract_split_kernel<8, 2, true>), dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, a_amax);
-        return;
-    }
+static int launch_contract_split(int tune, int grid, size_t lds3, hipStream_t stream, float* O, const float* AB, int N, int ldn, int P, int nbatch,
+                                 int tiles, int swap, const unsigned* a_amax = nullptr) {
+    if (a_amax)         // the scaled first operand of the backward: one form (8 waves)
+        return prd_launch<tri_mul_contract_split_kernel<8, 2, true>>(dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, a_amax);
     const int nw = PRD_TGET_TMS_NW(tune);
 #ifdef PRD_AB       // (libprd_hip_ab.so) three chunks in flight / 16 waves: measured in rounds 3 and 5, not faster
-    if (nw == 8 && PRD_TGET_TMS_D3(tune)) {
-        PRD_SET_LDS((tri_mul_contract_split_kernel<8, 3>), lds3);
-        hipLaunchKernelGGL((tri_mul_contract_split_kernel<8, 3>), dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
-        return;
-    }
-    if (nw == 16) {
-        PRD_SET_LDS((tri_mul_contract_split_kernel<16>), lds3);
-        hipLaunchKernelGGL((tri_mul_contract_split_kernel<16>), dim3(grid), dim3(1024), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
-        return;
-    }
+    if (nw == 8 && PRD_TGET_TMS_D3(tune))
+        return prd_launch<tri_mul_contract_split_kernel<8, 3>>(dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
+    if (nw == 16)
+        return prd_launch<tri_mul_contract_split_kernel<16>>(dim3(grid), dim3(1024), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
 #endif
-    if (nw == 12) {     // (kept in the shipped library: the second arm of the direct parity test -- same results bit for bit)
-        PRD_SET_LDS((tri_mul_contract_split_kernel<12>), lds3);
-        hipLaunchKernelGGL((tri_mul_contract_split_kernel<12>), dim3(grid), dim3(768), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
-    } else {
-        PRD_SET_LDS((tri_mul_contract_split_kernel<8>), lds3);
-        hipLaunchKernelGGL((tri_mul_contract_split_kernel<8>), dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
-    }
+    if (nw == 12)       // (kept in the shipped library: the second arm of the direct parity test -- same results bit for bit)
+        return prd_launch<tri_mul_contract_split_kernel<12>>(dim3(grid), dim3(768), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
+    return prd_launch<tri_mul_contract_split_kernel<8>>(dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
 }
 
 
@@ -2321,27 +2290,13 @@ extern "C" int prd_tri_attn_core_chunked(float* og, const float* pair, const flo
     const int per = prd_round_up(prd_ceil_div(N, nchunk), 64);         // keys per chunk (the last one may be shorter)
     const size_t lds = ((size_t)64 * (P + 4) + (size_t)per * KP + 16 * (per + 4) + per) * sizeof(float);
     if (lds > 160 * 1024) return PRD_ERR_UNSUPPORTED;
-    const long rows_total = (long)b * N;
-    const long cap = 256 / H;
-    long per_head = cap < rows_total ? cap : rows_total;
-    const long rounds = (rows_total + per_head - 1) / per_head;
-    per_head = (rows_total + rounds - 1) / rounds;
-    const int grid = (int)(per_head * H);
+    const int grid = (int)(prd_rows_per_head((long)b * N, 256 / H) * H);
     for (int ck = 0; ck < nchunk; ++ck) {
         const int key0 = ck * per;
         const int klen = key0 + per <= N ? per : N - key0;
         if (klen <= 0) break;
-        if (P == 64) {
-            PRD_SET_LDS((tri_attn_core_chunk_kernel<64, 8>), lds);
-            hipLaunchKernelGGL((tri_attn_core_chunk_kernel<64, 8>), dim3(grid), dim3(512), lds, stream, og, stats, pair, mask, wq, wk, wv, wg, bg,
-                               b, N, key0, klen, ck == 0 ? 1 : 0, H, ending);
-        } else {
-            PRD_SET_LDS((tri_attn_core_chunk_kernel<32, 8>), lds);
-            hipLaunchKernelGGL((tri_attn_core_chunk_kernel<32, 8>), dim3(grid), dim3(512), lds, stream, og, stats, pair, mask, wq, wk, wv, wg, bg,
-                               b, N, key0, klen, ck == 0 ? 1 : 0, H, ending);
-        }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
+        PRD_TRY(PRD_FOR_P(P, PP, prd_launch<tri_attn_core_chunk_kernel<PP, 8>>(dim3(grid), dim3(512), lds, stream, og, stats, pair, mask, wq, wk, wv, wg,
+                                                                               bg, b, N, key0, klen, ck == 0 ? 1 : 0, H, ending)));
     }
     return 0;
 }
@@ -2376,18 +2331,13 @@ extern "C" int prd_tri_mul(float* out, const float* pair, const float* mask, con
         const size_t lds = (2 * wsz + 4 * P) * sizeof(float);
         const long ntask = ((long)b * N * (ldn / 32) + 7) / 8 * 8 * (2 * P / 32);     // (row block, output block) tasks
         const int grid = grid_for(ntask, 4, 256);
-#define PRD_PROJ_LAUNCH(PP, BB, NWV)                                                                                 \
-        do {                                                                                                         \
-            PRD_SET_LDS((tri_mul_proj_kernel<PP, NWV, BB>), lds);                                                    \
-            hipLaunchKernelGGL((tri_mul_proj_kernel<PP, NWV, BB>), dim3(grid), dim3(NWV * 64), lds, stream, queue, AB, pair, mask, \
-                               w_proj, b_proj, w_gate, b_gate, b, N, ldn, incoming);                                 \
-        } while (0)
-        // (the split operands of the bf16 x 3 form need the registers of a 12-wave workgroup)
-        if (P == 64) { if (b3) { if (PRD_TGET_TMP_NW16(tune)) PRD_PROJ_LAUNCH(64, true, 16); else PRD_PROJ_LAUNCH(64, true, 12); } else PRD_PROJ_LAUNCH(64, false, NWP); }
-        else { if (b3) PRD_PROJ_LAUNCH(32, true, 12); else PRD_PROJ_LAUNCH(32, false, NWP); }
-#undef PRD_PROJ_LAUNCH
-        int e = (int)hipGetLastError();
-        if (e) return e;
+        // (the split operands of the bf16 x 3 form need the registers of a 12-wave workgroup; 16: the A/B switch, pair_dim 64 only)
+        const bool nw16 = b3 && P == 64 && PRD_TGET_TMP_NW16(tune);
+        PRD_TRY(PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3, BB, PRD_FOR_BOOL(nw16, NW16, [&] {
+            constexpr int NWV = !BB ? NWP : (NW16 && PP == 64) ? 16 : 12;
+            return prd_launch<tri_mul_proj_kernel<PP, NWV, BB>>(dim3(grid), dim3(NWV * 64), lds, stream, queue, AB, pair, mask,
+                                                                w_proj, b_proj, w_gate, b_gate, b, N, ldn, incoming);
+        }()))));
     }
     {
         const int tiles = prd_ceil_div(N, 64);
@@ -2396,26 +2346,20 @@ extern "C" int prd_tri_mul(float* out, const float* pair, const float* mask, con
             const int tl = prd_ceil_div(N, TMS_T);
             const int vb3 = b * P * tl * tl;
             const size_t lds3 = (size_t)4 * TMS_OPER;
-        launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 0);
+            PRD_TRY(launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 0));
         }
         else
-            hipLaunchKernelGGL(tri_mul_contract_kernel, dim3(vblocks < 1024 ? vblocks : 1024), dim3(256), 0, stream, O, AB, N, ldn, P, b, tiles);
-        int e = (int)hipGetLastError();
-        if (e) return e;
+            PRD_TRY(prd_launch<tri_mul_contract_kernel>(dim3(vblocks < 1024 ? vblocks : 1024), dim3(256), 0, stream, O, AB, N, ldn, P, b, tiles));
     }
     {
         constexpr int NWO = 8;
         const bool b3o = b3m;
         const long ntask = (long)b * N * prd_ceil_div(N, 32);
         const int grid = grid_for(ntask, 4, 256);
-#define PRD_OUT_LAUNCH(PP, BB)                                                                                         \
-        hipLaunchKernelGGL((tri_mul_out_kernel<PP, NWO, BB>), dim3(grid), dim3(NWO * 64), 0, stream, queue, out, pair, O, w_out, \
-                           b_out, w_ogate, b_ogate, b, N, ldn, residual)
-        if (P == 64) { if (b3o) PRD_OUT_LAUNCH(64, true); else PRD_OUT_LAUNCH(64, false); }
-        else { if (b3o) PRD_OUT_LAUNCH(32, true); else PRD_OUT_LAUNCH(32, false); }
-#undef PRD_OUT_LAUNCH
+        return PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3o, BB,
+            prd_launch<tri_mul_out_kernel<PP, NWO, BB>>(dim3(grid), dim3(NWO * 64), 0, stream, queue, out, pair, O, w_out,
+                                                        b_out, w_ogate, b_ogate, b, N, ldn, residual)));
     }
-    return (int)hipGetLastError();
 }
 
 extern "C" int prd_tri_mul_contract(float* O, const float* AB, int b, int N, int P, int arith, hipStream_t stream) {
@@ -2427,13 +2371,11 @@ extern "C" int prd_tri_mul_contract(float* O, const float* AB, int b, int N, int
         const int tl = prd_ceil_div(N, TMS_T);
         const int vb3 = b * P * tl * tl;
         const size_t lds3 = (size_t)4 * TMS_OPER;
-        launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 0);
-    } else {
-        const int tiles = prd_ceil_div(N, 64);
-        const int vblocks = b * P * tiles * tiles;
-        hipLaunchKernelGGL(tri_mul_contract_kernel, dim3(vblocks < 1024 ? vblocks : 1024), dim3(256), 0, stream, O, AB, N, ldn, P, b, tiles);
+        return launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 0);
     }
-    return (int)hipGetLastError();
+    const int tiles = prd_ceil_div(N, 64);
+    const int vblocks = b * P * tiles * tiles;
+    return prd_launch<tri_mul_contract_kernel>(dim3(vblocks < 1024 ? vblocks : 1024), dim3(256), 0, stream, O, AB, N, ldn, P, b, tiles);
 }
 
 extern "C" int prd_tri_mul_contract_scaled(float* O, const float* AB, const unsigned* a_amax, int b, int N, int P, int arith, hipStream_t stream) {
@@ -2445,8 +2387,7 @@ extern "C" int prd_tri_mul_contract_scaled(float* O, const float* AB, const unsi
     const int ldn = prd_round_up(N, 32);
     const int tl = prd_ceil_div(N, TMS_T);
     const int vb3 = b * P * tl * tl;
-    launch_contract_split(tune, vb3 < 256 ? vb3 : 256, (size_t)4 * TMS_OPER, stream, O, AB, N, ldn, P, b, tl, 0, a_amax);
-    return (int)hipGetLastError();
+    return launch_contract_split(tune, vb3 < 256 ? vb3 : 256, (size_t)4 * TMS_OPER, stream, O, AB, N, ldn, P, b, tl, 0, a_amax);
 }
 
 extern "C" int prd_tri_mul_chain_supported(int N, int P, int arith) {
@@ -2475,53 +2416,31 @@ extern "C" int prd_tri_mul_chain(float* pair, const float* mask, const float* co
     const long rtask = (long)b * N * (ldn / 32);
     const int rgrid = grid_for(rtask, 4, 256);
     const size_t ldsf = ((size_t)2 * P * P + (size_t)2 * 2 * P * P + 6 * P) * sizeof(float);
-    // a failed launch must not let the later stages run over a half-written workspace: checked after every stage
-#define PRD_CHAIN_STAGE_OK() do { const hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
-    // 1. a | b of the outgoing module
-    if (P == 64 && PRD_TGET_TMP_NW16(tune)) {           // (A/B: PRD_TUNE_TMP_NW16)
-        PRD_SET_LDS((tri_mul_proj_kernel<64, 16, true>), ldsp);
-        hipLaunchKernelGGL((tri_mul_proj_kernel<64, 16, true>), dim3(pgrid), dim3(16 * 64), ldsp, stream, (int*)nullptr, AB, pair, mask,
-                           wa[0], wa[1], wa[2], wa[3], b, N, ldn, 0);
-    } else if (P == 64) {
-        PRD_SET_LDS((tri_mul_proj_kernel<64, 12, true>), ldsp);
-        hipLaunchKernelGGL((tri_mul_proj_kernel<64, 12, true>), dim3(pgrid), dim3(12 * 64), ldsp, stream, (int*)nullptr, AB, pair, mask,
-                           wa[0], wa[1], wa[2], wa[3], b, N, ldn, 0);
-    } else {
-        PRD_SET_LDS((tri_mul_proj_kernel<32, 12, true>), ldsp);
-        hipLaunchKernelGGL((tri_mul_proj_kernel<32, 12, true>), dim3(pgrid), dim3(12 * 64), ldsp, stream, (int*)nullptr, AB, pair, mask,
-                           wa[0], wa[1], wa[2], wa[3], b, N, ldn, 0);
-    }
-    PRD_CHAIN_STAGE_OK();
+    // (a failed launch must not let the later stages run over a half-written workspace: every stage is checked)
+    // 1. a | b of the outgoing module: 12 waves; 16: the A/B switch PRD_TUNE_TMP_NW16, pair_dim 64 only
+    const bool nw16 = P == 64 && PRD_TGET_TMP_NW16(tune);
+    PRD_TRY(PRD_FOR_P(P, PP, PRD_FOR_BOOL(nw16, NW16, [&] {
+        constexpr int NWV = (NW16 && PP == 64) ? 16 : 12;
+        return prd_launch<tri_mul_proj_kernel<PP, NWV, true>>(dim3(pgrid), dim3(NWV * 64), ldsp, stream, (int*)nullptr, AB, pair, mask,
+                                                              wa[0], wa[1], wa[2], wa[3], b, N, ldn, 0);
+    }())));
     // 2. its contraction, transposed: O^T[c][j][i]
-        launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 1);
-    PRD_CHAIN_STAGE_OK();
+    PRD_TRY(launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 1));
     // 3. output stage of the outgoing module + a | b of the incoming one.  P = 64: 12 waves (168 VGPRs, three per SIMD) cover the
     // task's latency chain better than 8 (36.6 -> 31.7 us at N = 320; the plain output stage below needs 192 VGPRs and stays at 8:
     // 12 waves spill, 19.9 -> 28.7 us)
-    if (P == 64) {
-        PRD_SET_LDS((tri_mul_out_proj_kernel<64, 12>), ldsf);
-        hipLaunchKernelGGL((tri_mul_out_proj_kernel<64, 12>), dim3(rgrid), dim3(12 * 64), ldsf, stream, pair, O, mask, wa[4], wa[5], wa[6], wa[7],
-                           wb[0], wb[1], wb[2], wb[3], AB, b, N, ldn);
-    } else {
-        PRD_SET_LDS((tri_mul_out_proj_kernel<32, 8>), ldsf);
-        hipLaunchKernelGGL((tri_mul_out_proj_kernel<32, 8>), dim3(rgrid), dim3(8 * 64), ldsf, stream, pair, O, mask, wa[4], wa[5], wa[6], wa[7],
-                           wb[0], wb[1], wb[2], wb[3], AB, b, N, ldn);
-    }
-    PRD_CHAIN_STAGE_OK();
+    PRD_TRY(PRD_FOR_P(P, PP, [&] {
+        constexpr int NWV = PP == 64 ? 12 : 8;
+        return prd_launch<tri_mul_out_proj_kernel<PP, NWV>>(dim3(rgrid), dim3(NWV * 64), ldsf, stream, pair, O, mask, wa[4], wa[5], wa[6], wa[7],
+                                                            wb[0], wb[1], wb[2], wb[3], AB, b, N, ldn);
+    }()));
     // 4. contraction of the incoming module
-        launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 0);
-    PRD_CHAIN_STAGE_OK();
+    PRD_TRY(launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 0));
     // 5. its output stage
-    {
-        const long ntask = (long)b * N * prd_ceil_div(N, 32);
-        const int grid = grid_for(ntask, 4, 256);
-        if (P == 64) hipLaunchKernelGGL((tri_mul_out_kernel<64, 8, true>), dim3(grid), dim3(8 * 64), 0, stream, (int*)nullptr, pair, pair, O,
-                                        wb[4], wb[5], wb[6], wb[7], b, N, ldn, 1);
-        else hipLaunchKernelGGL((tri_mul_out_kernel<32, 8, true>), dim3(grid), dim3(8 * 64), 0, stream, (int*)nullptr, pair, pair, O,
-                                wb[4], wb[5], wb[6], wb[7], b, N, ldn, 1);
-    }
-#undef PRD_CHAIN_STAGE_OK
-    return (int)hipGetLastError();
+    const long ntask = (long)b * N * prd_ceil_div(N, 32);
+    const int grid = grid_for(ntask, 4, 256);
+    return PRD_FOR_P(P, PP, prd_launch<tri_mul_out_kernel<PP, 8, true>>(dim3(grid), dim3(8 * 64), 0, stream, (int*)nullptr, pair, pair, O,
+                                                                        wb[4], wb[5], wb[6], wb[7], b, N, ldn, 1));
 }
 
 extern "C" int prd_tri_attn_core(float* og, const float* pair, const float* mask, const float* wq, const float* wk,
@@ -2544,42 +2463,31 @@ extern "C" int prd_tri_attn_core(float* og, const float* pair, const float* mask
     const int nw = 8;                                   // 2 waves / SIMD: room for the next-row prefetch registers
     // persistent workgroups (weights staged once per workgroup), one per CU: per head the SMALLEST workgroup
     // count that reaches the minimum number of row rounds, so every workgroup walks the same number of rows
-    const long rows_total = (long)b * N;
-    const long cap = 256 / H;
-    long per_head = cap < rows_total ? cap : rows_total;
-    if (per_head < 1) per_head = 1;
-    const long rounds = (rows_total + per_head - 1) / per_head;
-    per_head = (rows_total + rounds - 1) / rounds;
-    const int grid = (int)(per_head * H);
-#define PRD_TA_LAUNCH(KERNEL, NWV, ...)                                                                                \
-    do {                                                                                                               \
-        PRD_SET_LDS((KERNEL<__VA_ARGS__>), lds);                                                                       \
-        hipLaunchKernelGGL((KERNEL<__VA_ARGS__>), dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, wq, wk, wv, wg, bg, b, N, npad, H, ending); \
-    } while (0)
+    const int grid = (int)(prd_rows_per_head((long)b * N, 256 / H) * H);
+    // the first-generation cores share their arguments (the split core has four more: the fused form's, unused here)
+#define PRD_TA_LAUNCH(NWV, KERNEL, ...) \
+    prd_launch<KERNEL>(dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, wq, wk, wv, wg, bg, b, N, npad, H, ending, ##__VA_ARGS__)
+#define PRD_TA_NOT_FUSED nullptr, nullptr, nullptr, nullptr
     (void)nqb; (void)nw;
     // 12 waves (3 per SIMD) + next-row prefetch: the ceil(N/16) query tiles dealt in pairs land 5 per SIMD at N = 320
     // (measured: 12 waves + prefetch 142 us, 16 waves without prefetch 149 us, 8 waves + prefetch 146 us)
     const bool split_long = long_row && b3 &&
         lds == (size_t)64 * P * 4 + (size_t)npad * 68 + (size_t)64 * (npad + 8) + 128 + 8 * 4096;      // tri_attn_lds chose it
 #ifdef PRD_AB
-    if (split_long) { if (P == 64) PRD_TA_LAUNCH(tri_attn_core_split_long_kernel, 8, 64, 8); else PRD_TA_LAUNCH(tri_attn_core_split_long_kernel, 8, 32, 8); }
-    else if (!long_row && b3) {
-        if (P == 64) {
-            if (variant == 1) PRD_TA_LAUNCH(tri_attn_core_split_kernel, 16, 64, 16, 1, false);
-            else if (variant == 2) PRD_TA_LAUNCH(tri_attn_core_split_kernel, 12, 64, 12, 1, false);
-            else if (variant == 3) PRD_TA_LAUNCH(tri_attn_core_split_kernel, 8, 64, 8, 1, true);
-            else PRD_TA_LAUNCH(tri_attn_core_split_kernel, 8, 64, 8, 2, true);
-        } else {
-            PRD_TA_LAUNCH(tri_attn_core_split_kernel, 8, 32, 8, 2, true);
-        }
-    } else
+    if (split_long) return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(8, (tri_attn_core_split_long_kernel<PP, 8>)));
+    if (!long_row && b3) {
+        if (P == 64 && variant == 1) return PRD_TA_LAUNCH(16, (tri_attn_core_split_kernel<64, 16, 1, false>), PRD_TA_NOT_FUSED);
+        if (P == 64 && variant == 2) return PRD_TA_LAUNCH(12, (tri_attn_core_split_kernel<64, 12, 1, false>), PRD_TA_NOT_FUSED);
+        if (P == 64 && variant == 3) return PRD_TA_LAUNCH(8, (tri_attn_core_split_kernel<64, 8, 1, true>), PRD_TA_NOT_FUSED);
+        return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(8, (tri_attn_core_split_kernel<PP, 8, 2, true>), PRD_TA_NOT_FUSED));
+    }
 #else
     (void)split_long; (void)variant;
 #endif
-    if (long_row) { if (P == 64) PRD_TA_LAUNCH(tri_attn_core_long_kernel, 8, 64, 8); else PRD_TA_LAUNCH(tri_attn_core_long_kernel, 8, 32, 8); }
-    else { if (P == 64) PRD_TA_LAUNCH(tri_attn_core_kernel, 12, 64, 12, true, false); else PRD_TA_LAUNCH(tri_attn_core_kernel, 12, 32, 12, true, false); }
+    if (long_row) return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(8, (tri_attn_core_long_kernel<PP, 8>)));
+    return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(12, (tri_attn_core_kernel<PP, 12, true, false>)));
+#undef PRD_TA_NOT_FUSED
 #undef PRD_TA_LAUNCH
-    return (int)hipGetLastError();
 }
 
 extern "C" int prd_single_attn_core(float* o, const float* qkvg, int ldq, const float* bias, const float* mask,
@@ -2587,8 +2495,7 @@ extern "C" int prd_single_attn_core(float* o, const float* qkvg, int ldq, const 
     if (!o || !qkvg || !bias || b <= 0 || N <= 0) return PRD_ERR_ARG;
     if (c != 16 || H * c != 64) return PRD_ERR_UNSUPPORTED;
     if (ldq < 4 * H * c || (ldq & 3)) return PRD_ERR_ALIGN;
-    hipLaunchKernelGGL(single_attn_core_kernel, dim3(b * H * prd_ceil_div(N, 16)), dim3(256), 0, stream, o, qkvg, bias, mask, b, N, H, ldq);
-    return (int)hipGetLastError();
+    return prd_launch<single_attn_core_kernel>(dim3(b * H * prd_ceil_div(N, 16)), dim3(256), 0, stream, o, qkvg, bias, mask, b, N, H, ldq);
 }
 
 // LDS of the fused form: the short-row split kernel's layout + the W_o image and bias of the previous attention
@@ -2615,27 +2522,13 @@ extern "C" int prd_tri_attn_core_fused(float* og, float* pair_out, const float* 
     if (!prd_tri_attn_core_fused_supported(N, P, PRD_ARITH_SPLIT16)) return PRD_ERR_UNSUPPORTED;
     const int npad = prd_round_up(N, 64);
     const size_t lds = tri_attn_fused_lds(N, P);
-    const long rows_total = (long)b * N;
-    const long cap = 256 / H;
-    long per_head = cap < rows_total ? cap : rows_total;
-    if (per_head < 1) per_head = 1;
-    const long rounds = (rows_total + per_head - 1) / per_head;
-    per_head = (rows_total + rounds - 1) / rounds;
-    const int grid = (int)(per_head * H);
+    const int grid = (int)(prd_rows_per_head((long)b * N, 256 / H) * H);
 #ifndef PRD_AB
     (void)grid; (void)lds; (void)npad;
     return PRD_ERR_UNSUPPORTED;
 #else
-    if (P == 64) {
-        PRD_SET_LDS((tri_attn_core_split_kernel<64, 8, 2, true, true>), lds);
-        hipLaunchKernelGGL((tri_attn_core_split_kernel<64, 8, 2, true, true>), dim3(grid), dim3(512), lds, stream, og, pair, mask, wq, wk, wv, wg,
-                           bg, b, N, npad, H, ending, og_in, wo_in, bo_in, pair_out);
-    } else {
-        PRD_SET_LDS((tri_attn_core_split_kernel<32, 8, 2, true, true>), lds);
-        hipLaunchKernelGGL((tri_attn_core_split_kernel<32, 8, 2, true, true>), dim3(grid), dim3(512), lds, stream, og, pair, mask, wq, wk, wv, wg,
-                           bg, b, N, npad, H, ending, og_in, wo_in, bo_in, pair_out);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<tri_attn_core_split_kernel<PP, 8, 2, true, true>>(dim3(grid), dim3(512), lds, stream, og, pair, mask, wq, wk, wv,
+                                                                                         wg, bg, b, N, npad, H, ending, og_in, wo_in, bo_in, pair_out));
 #endif
 }
 
@@ -2648,11 +2541,8 @@ extern "C" int prd_tri_attn_out(float* out, const float* pair, const float* og, 
     const long rows = (long)b * N * N;
     const int grid2 = grid_for((rows + 31) / 32, 4, 256);
     const bool b3 = arith == PRD_ARITH_SPLIT16;
-#define PRD_TAO(PP, BB) hipLaunchKernelGGL((tri_attn_out_kernel<PP, NWA, BB>), dim3(grid2), dim3(NWA * 64), 0, stream, queue, out, pair, og, wo, bo, rows, residual)
-    if (P == 64) { if (b3) PRD_TAO(64, true); else PRD_TAO(64, false); }
-    else { if (b3) PRD_TAO(32, true); else PRD_TAO(32, false); }
-#undef PRD_TAO
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3, BB,
+        prd_launch<tri_attn_out_kernel<PP, NWA, BB>>(dim3(grid2), dim3(NWA * 64), 0, stream, queue, out, pair, og, wo, bo, rows, residual)));
 }
 
 extern "C" int prd_tri_attn(float* out, const float* pair, const float* mask, const float* wq, const float* wk, const float* wv,

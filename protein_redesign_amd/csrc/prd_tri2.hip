@@ -44,7 +44,7 @@
 #include "prd_common.h"
 #include "../../include/prd_hip.h"
 #include <cstdlib>
-#include <mutex>
+#include "prd_launch.h"
 
 #ifdef PRD_TIMING     // diagnostic builds only (tools/ta2_timing.py): cycle stamps [workgroup][12 waves][8 rows][16 stamps]
 __device__ unsigned long long prd_dbg2[256 * 12 * 8 * 16];
@@ -1898,13 +1898,17 @@ size_t v2_lds_bytes(int N, int P) {
 
 }  // namespace
 
-#define PRD2_SET_LDS(kernel)                                                                                    \
-    do {                                                                                                        \
-        static std::once_flag once;                                                                             \
-        std::call_once(once, [] {                                                                               \
-            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        });                                                                                                     \
-    } while (0)
+// A choice that only libprd_hip_ab.so offers (-DPRD_AB: the measured-and-superseded forms): the shipped library
+// carries the default form only, and the switches that select another one are ignored
+#ifdef PRD_AB
+#define PRD2_FOR_AB_BOOL(v, NAME, DEFAULT, ...) PRD_FOR_BOOL(v, NAME, __VA_ARGS__)
+#define PRD2_FOR_AB_0123(v, NAME, ...)                                                                             \
+    ((v) == 0 ? PRD_WITH(int, NAME, 0, __VA_ARGS__) : (v) == 1 ? PRD_WITH(int, NAME, 1, __VA_ARGS__)               \
+                                                    : (v) == 2 ? PRD_WITH(int, NAME, 2, __VA_ARGS__) : PRD_WITH(int, NAME, 3, __VA_ARGS__))
+#else
+#define PRD2_FOR_AB_BOOL(v, NAME, DEFAULT, ...) ((void)(v), PRD_WITH(bool, NAME, DEFAULT, __VA_ARGS__))
+#define PRD2_FOR_AB_0123(v, NAME, ...) ((void)(v), PRD_WITH(int, NAME, 0, __VA_ARGS__))
+#endif
 
 // 1 when the second-generation core serves rows of N positions (split-16 arithmetic only)
 extern "C" int prd_tri_attn_v2_supported(int N, int P, int tune) {
@@ -1936,17 +1940,7 @@ extern "C" int prd_tri_attn_core_v2_lse(float* og, float* lse, const float* pair
     const bool long_rows = N > V2_MAXN;
     bool share = false;
     const size_t lds = long_rows ? v2l_lds_bytes(N, P, &share) : v2_lds_bytes(N, P);
-    const long rows_total = (long)b * N;
-    const long cap = 256 / H;
-    long per_head = cap < rows_total ? cap : rows_total;
-    if (per_head < 1) per_head = 1;
-    const long rounds = (rows_total + per_head - 1) / per_head;
-    per_head = (rows_total + rounds - 1) / rounds;
-    // a multiple of 8 rows in flight per head (never more rounds: per_head <= cap = 64 either way): the kernels then keep the four
-    // head-workgroups of a row on ONE XCD, whose L2 serves three of the four reads of the row.  (N = 769: 60 -> 64 rows in flight.)
-    if (per_head >= 8 && !((tune >> 20) & 1)) per_head = (per_head + 7) / 8 * 8;      // (PRD_TUNE_TA2_NO_XCD8: A/B switch)
-    if (per_head > cap) per_head = cap;
-    const int grid = (int)(per_head * H);
+    const int grid = (int)(prd_rows_per_head_xcd8((long)b * N, 256 / H, !((tune >> 20) & 1)) * H);      // (PRD_TUNE_TA2_NO_XCD8: A/B switch)
     constexpr int NWV = 12;                             // nqb <= 12 query blocks, one wave each
     const int flags_env = PRD_TGET_TA2_FLAGS(tune);     // A/B switch: kernel flags given by the caller (-1: per-kernel default)
     const int use_v3 = !PRD_TGET_TA2_NO_V3(tune);       // A/B switch: 0 = the barrier-per-phase form
@@ -1962,66 +1956,27 @@ extern "C" int prd_tri_attn_core_v2_lse(float* og, float* lse, const float* pair
     const int flags = flags0 | ((long_rows && rem_ && 12 / rem_ >= 2 && !share) ? 16 : 0) | (PRD_TGET_TA2_NO_TAIL_SPLIT(tune) ? 32 : 0)
                       | (tail1 ? 64 : 0) | ((long_rows && (flags0 & 4)) ? 128 : 0);    // (PRD_TA2_FLAGS bit 2: the shared last round in its round-5 form)
     if (long_rows) {
-#define PRD_V2L_LAUNCH(PP, PF, GVF)                                                                                               \
-        do {                                                                                                                      \
-            PRD2_SET_LDS((tri_attn_core_v2l_kernel<PP, NWV, PF, GVF>));                                                           \
-            hipLaunchKernelGGL((tri_attn_core_v2l_kernel<PP, NWV, PF, GVF>), dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, wq, wk, \
-                               wv, wg, bg, b, N, NP, H, ending, flags);                                                           \
-        } while (0)
-        const bool pf = (flags & 8) != 0;               // next-row prefetch of the wave's first block (costs 32 registers)
-        const bool gvl = !PRD_TGET_TA2_NO_GV(tune);     // phase 1 with [K|V] as one row GEMM + transposed V store
-#ifdef PRD_AB       // (libprd_hip_ab.so) the measured-and-superseded forms: next-row prefetch (spills), the round-3 phase 1
-        if (P == 64) {
-            if (gvl) { if (pf) PRD_V2L_LAUNCH(64, true, true); else PRD_V2L_LAUNCH(64, false, true); }
-            else { if (pf) PRD_V2L_LAUNCH(64, true, false); else PRD_V2L_LAUNCH(64, false, false); }
-        } else {
-            if (gvl) { if (pf) PRD_V2L_LAUNCH(32, true, true); else PRD_V2L_LAUNCH(32, false, true); }
-            else { if (pf) PRD_V2L_LAUNCH(32, true, false); else PRD_V2L_LAUNCH(32, false, false); }
-        }
-#else               // the shipped library carries the default form only; the switches that select another one are ignored
-        (void)pf; (void)gvl;
-        if (P == 64) PRD_V2L_LAUNCH(64, false, true); else PRD_V2L_LAUNCH(32, false, true);
-#endif
-#undef PRD_V2L_LAUNCH
-        return (int)hipGetLastError();
+        const bool pf = (flags & 8) != 0;               // next-row prefetch of the wave's first block (costs 32 registers; spills)
+        const bool gvl = !PRD_TGET_TA2_NO_GV(tune);     // phase 1 with [K|V] as one row GEMM + transposed V store (else: the round-3 phase 1)
+        return PRD_FOR_P(P, PP, PRD2_FOR_AB_BOOL(pf, PF, false, PRD2_FOR_AB_BOOL(gvl, GVF, true,
+            prd_launch<tri_attn_core_v2l_kernel<PP, NWV, PF, GVF>>(dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, wq, wk,
+                                                                   wv, wg, bg, b, N, NP, H, ending, flags))));
     }
     if (v3) {
         const size_t lds3 = v3_lds_bytes(N, P);
-#define PRD_V3_LAUNCH(PP, KLF, GVF)                                                                                                 \
-        do {                                                                                                                      \
-            PRD2_SET_LDS((tri_attn_core_v3_kernel<PP, NWV, KLF, GVF>));                                                           \
-            hipLaunchKernelGGL((tri_attn_core_v3_kernel<PP, NWV, KLF, GVF>), dim3(grid), dim3(NWV * 64), lds3, stream, og, pair, mask, wq, wk, wv, wg, \
-                               bg, b, N, NP, H, ending, flags & ~6, lse);                                                         \
-        } while (0)
         const int kl = flags_env >= 0 ? (flags >> 1) & 3 : PRD_V3_DEFAULT_KL;     // key-loop form (bits 1-2 of PRD_TA2_FLAGS; v3 has no stagger)
         // phase 1 with [G|V] as one row GEMM + transposed V store (default); PRD_TUNE_TA2_NO_GV: the G GEMM + swapped V GEMM of round 3.
-        // The A/B key-loop forms 1-3 exist with the round-3 phase 1 only.
+        // The A/B key-loop forms 1-3 exist with the round-3 phase 1 only (measured in round 5, none faster).  The scheduling
+        // switches -- bits 0, 3, 4 -- reach the shipped form too.
         const bool gvf = !PRD_TGET_TA2_NO_GV(tune) && kl == 0;
-#ifdef PRD_AB       // (libprd_hip_ab.so) the key-loop forms 1-3 and the round-3 phase 1: measured in round 5, none faster
-        if (P == 64) {
-            if (gvf) PRD_V3_LAUNCH(64, 0, true);
-            else if (kl == 0) PRD_V3_LAUNCH(64, 0, false); else if (kl == 1) PRD_V3_LAUNCH(64, 1, false); else if (kl == 2) PRD_V3_LAUNCH(64, 2, false); else PRD_V3_LAUNCH(64, 3, false);
-        } else {
-            if (gvf) PRD_V3_LAUNCH(32, 0, true);
-            else if (kl == 0) PRD_V3_LAUNCH(32, 0, false); else if (kl == 1) PRD_V3_LAUNCH(32, 1, false); else if (kl == 2) PRD_V3_LAUNCH(32, 2, false); else PRD_V3_LAUNCH(32, 3, false);
-        }
-#else               // the shipped library carries the default form only (the scheduling switches -- bits 0, 3, 4 -- still reach it)
-        (void)gvf;
-        if (P == 64) PRD_V3_LAUNCH(64, 0, true); else PRD_V3_LAUNCH(32, 0, true);
-#endif
-#undef PRD_V3_LAUNCH
-        return (int)hipGetLastError();
+        return PRD_FOR_P(P, PP, PRD2_FOR_AB_BOOL(gvf, GVF, true, PRD2_FOR_AB_0123(kl, KL, [&] {
+            constexpr int KLF = GVF ? 0 : KL;
+            return prd_launch<tri_attn_core_v3_kernel<PP, NWV, KLF, GVF>>(dim3(grid), dim3(NWV * 64), lds3, stream, og, pair, mask, wq, wk, wv, wg,
+                                                                          bg, b, N, NP, H, ending, flags & ~6, lse);
+        }())));
     }
-    if (P == 64) {
-        PRD2_SET_LDS((tri_attn_core_v2_kernel<64, NWV>));
-        hipLaunchKernelGGL((tri_attn_core_v2_kernel<64, NWV>), dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, wq, wk, wv, wg, bg, b, N,
-                           NP, H, ending, flags, lse);
-    } else {
-        PRD2_SET_LDS((tri_attn_core_v2_kernel<32, NWV>));
-        hipLaunchKernelGGL((tri_attn_core_v2_kernel<32, NWV>), dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, wq, wk, wv, wg, bg, b, N,
-                           NP, H, ending, flags, lse);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<tri_attn_core_v2_kernel<PP, NWV>>(dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, wq, wk, wv, wg, bg,
+                                                                         b, N, NP, H, ending, flags, lse));
 }
 
 extern "C" int prd_tri_attn_core_v2(float* og, const float* pair, const float* mask, const float* wq, const float* wk,
@@ -2060,14 +2015,7 @@ extern "C" int prd_tri_attn_pair(float* og, float* pair, const float* mask, cons
     if (!prd_tri_attn_pair_supported(N, P, arith)) return PRD_ERR_UNSUPPORTED;
     if ((long)b * N * N > 0x7fffffffL / 2) return PRD_ERR_UNSUPPORTED;
     const int NP = prd_round_up(N, 32);
-    const long rows_total = (long)b * N, cap = 256 / H;                 // the grid of prd_tri_attn_core_v2 (heads of a row on one XCD)
-    long per_head = cap < rows_total ? cap : rows_total;
-    if (per_head < 1) per_head = 1;
-    const long rounds = (rows_total + per_head - 1) / per_head;
-    per_head = (rows_total + rounds - 1) / rounds;
-    if (per_head >= 8) per_head = (per_head + 7) / 8 * 8;
-    if (per_head > cap) per_head = cap;
-    const int grid = (int)(per_head * H);
+    const int grid = (int)(prd_rows_per_head_xcd8((long)b * N, 256 / H) * H);   // the grid of prd_tri_attn_core_v2 (heads of a row on one XCD)
     // every workgroup must be resident for the in-kernel barriers: one workgroup of 12 waves + ~150 KB of LDS per CU
     const int cus = prd_cu_count();
     if (cus <= 0 || grid > cus) return PRD_ERR_UNSUPPORTED;
@@ -2078,16 +2026,9 @@ extern "C" int prd_tri_attn_pair(float* og, float* pair, const float* mask, cons
     const int plain = PRD_TGET_TA2_NO_TAIL_SPLIT(tune) ? 1 : 0;               // (A/B: PRD_TA2_TAIL=0 selects the plain counter barrier here)
     if (e != hipSuccess) return (int)e;
     constexpr int NWV = 12;
-    if (P == 64) {
-        PRD2_SET_LDS((tri_attn_pair_kernel<64, NWV>));
-        hipLaunchKernelGGL((tri_attn_pair_kernel<64, NWV>), dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, w_start[0], w_start[1], w_start[2],
-                           w_start[3], w_start[4], w_start[5], w_start[6], w_end[0], w_end[1], w_end[2], w_end[3], w_end[4], b, N, NP, H, bar, plain);
-    } else {
-        PRD2_SET_LDS((tri_attn_pair_kernel<32, NWV>));
-        hipLaunchKernelGGL((tri_attn_pair_kernel<32, NWV>), dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, w_start[0], w_start[1], w_start[2],
-                           w_start[3], w_start[4], w_start[5], w_start[6], w_end[0], w_end[1], w_end[2], w_end[3], w_end[4], b, N, NP, H, bar, plain);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<tri_attn_pair_kernel<PP, NWV>>(dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, w_start[0], w_start[1],
+                                                                      w_start[2], w_start[3], w_start[4], w_start[5], w_start[6], w_end[0], w_end[1],
+                                                                      w_end[2], w_end[3], w_end[4], b, N, NP, H, bar, plain));
 }
 
 // ---- backward core, split-16 arithmetic (tri_attn_bwd_core_v2_kernel) ----
@@ -2111,14 +2052,6 @@ extern "C" int prd_tri_attn_bwd_core_v2(float* dqkvg, const float* dog, const fl
     if (per_head >= 8) per_head = per_head / 8 * 8;     // the heads of a row on one XCD
     const int grid = (int)(per_head * H);
     constexpr int NWV = 12;
-    if (P == 64) {
-        PRD2_SET_LDS((tri_attn_bwd_core_v2_kernel<64, NWV>));
-        hipLaunchKernelGGL((tri_attn_bwd_core_v2_kernel<64, NWV>), dim3(grid), dim3(NWV * 64), lds, stream, dqkvg, dog, og, pair, mask, wq, wk, wv,
-                           wg, bg, b, N, NP, H, ending, lse, x_out);
-    } else {
-        PRD2_SET_LDS((tri_attn_bwd_core_v2_kernel<32, NWV>));
-        hipLaunchKernelGGL((tri_attn_bwd_core_v2_kernel<32, NWV>), dim3(grid), dim3(NWV * 64), lds, stream, dqkvg, dog, og, pair, mask, wq, wk, wv,
-                           wg, bg, b, N, NP, H, ending, lse, x_out);
-    }
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, prd_launch<tri_attn_bwd_core_v2_kernel<PP, NWV>>(dim3(grid), dim3(NWV * 64), lds, stream, dqkvg, dog, og, pair, mask, wq,
+                                                                             wk, wv, wg, bg, b, N, NP, H, ending, lse, x_out));
 }

@@ -26,7 +26,7 @@
 //              share the layout Y^T, so the epilogue is elementwise and stores float4s of 4 channels.
 #include "prd_common.h"
 #include "../../include/prd_hip.h"
-#include <mutex>
+#include "prd_launch.h"
 
 namespace {
 
@@ -273,29 +273,15 @@ __global__ __launch_bounds__(TH_NW * 64) void tri_attn_heads_kernel(
     }
 }
 
-#define PRD_TH_SET_LDS(kernel)                                                                                  \
-    do {                                                                                                        \
-        static std::once_flag prd_lds_once;                                                                     \
-        std::call_once(prd_lds_once, [] {                                                                       \
-            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        });                                                                                                     \
-    } while (0)
-
 template <int P, int CP, bool LSE>
-void th_launch(float* og, float* lse, const float* pair, const float* mask, const float* wq, const float* wk, const float* wv,
+int th_launch(float* og, float* lse, const float* pair, const float* mask, const float* wq, const float* wk, const float* wv,
                const float* wg, const float* bg, int ending, int b, int N, int H, int c, hipStream_t stream) {
     const size_t lds = th_lds_bytes<P, CP>();
     // persistent, one workgroup of 8 waves per CU (the registers allow no second one): per head the smallest workgroup count that
     // reaches the minimum number of row rounds, as prd_tri_attn_core
-    const long rows_total = (long)b * N;
-    const long cap = 256 / H;
-    long per_head = cap < rows_total ? cap : rows_total;
-    if (per_head < 1) per_head = 1;
-    const long rounds = (rows_total + per_head - 1) / per_head;
-    per_head = (rows_total + rounds - 1) / rounds;
-    PRD_TH_SET_LDS((tri_attn_heads_kernel<P, CP, LSE>));
-    hipLaunchKernelGGL((tri_attn_heads_kernel<P, CP, LSE>), dim3((unsigned)(per_head * H)), dim3(TH_NW * 64), lds, stream,
-                       og, lse, pair, mask, wq, wk, wv, wg, bg, b, N, H, c, ending);
+    const long per_head = prd_rows_per_head((long)b * N, 256 / H);
+    return prd_launch<tri_attn_heads_kernel<P, CP, LSE>>(dim3((unsigned)(per_head * H)), dim3(TH_NW * 64), lds, stream,
+                                                         og, lse, pair, mask, wq, wk, wv, wg, bg, b, N, H, c, ending);
 }
 
 }  // namespace
@@ -323,15 +309,8 @@ int th_core(float* og, float* lse, const float* pair, const float* mask, const f
     if (((uintptr_t)og | (uintptr_t)pair) & 15) return PRD_ERR_ALIGN;
     if ((uintptr_t)lse & 7) return PRD_ERR_ALIGN;
     const int cp = c <= 16 ? 16 : c <= 32 ? 32 : 64;
-#define PRD_TH(PP, CC)                                                                                          \
-    do {                                                                                                        \
-        if (lse) th_launch<PP, CC, true>(og, lse, pair, mask, wq, wk, wv, wg, bg, ending, b, N, H, c, stream);  \
-        else th_launch<PP, CC, false>(og, lse, pair, mask, wq, wk, wv, wg, bg, ending, b, N, H, c, stream);     \
-    } while (0)
-    if (P == 64) { if (cp == 16) PRD_TH(64, 16); else if (cp == 32) PRD_TH(64, 32); else PRD_TH(64, 64); }
-    else { if (cp == 16) PRD_TH(32, 16); else if (cp == 32) PRD_TH(32, 32); else PRD_TH(32, 64); }
-#undef PRD_TH
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, PRD_FOR_3(cp, CC, 16, 32, 64, PRD_FOR_BOOL(lse != nullptr, LSE,
+        th_launch<PP, CC, LSE>(og, lse, pair, mask, wq, wk, wv, wg, bg, ending, b, N, H, c, stream))));
 }
 
 }  // namespace

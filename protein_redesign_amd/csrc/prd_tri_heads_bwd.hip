@@ -31,7 +31,7 @@
 // conflict-free at pitch CP + 4), the B operands are the owned registers / the dS, p tiles as they come out of the MFMA.
 #include "prd_common.h"
 #include "../../include/prd_hip.h"
-#include <mutex>
+#include "prd_launch.h"
 
 namespace {
 
@@ -427,33 +427,18 @@ __global__ __launch_bounds__(TB_NW * 64) void tri_attn_heads_bwd_kernel(
 // workgroups of a launch: per head the smallest count that reaches the minimum number of row rounds, one workgroup per CU (as the
 // forward core); the workspace query and the launch must agree on it
 long tb_grid(int b, int N, int H) {
-    const long rows_total = (long)b * N;
-    const long cap = 256 / H;
-    long per_head = cap < rows_total ? cap : rows_total;
-    if (per_head < 1) per_head = 1;
-    const long rounds = (rows_total + per_head - 1) / per_head;
-    per_head = (rows_total + rounds - 1) / rounds;
-    return per_head * H;
+    return prd_rows_per_head((long)b * N, 256 / H) * H;
 }
 
 int tb_cp(int c) { return c <= 16 ? 16 : c <= 32 ? 32 : 64; }
 
-#define PRD_TB_SET_LDS(kernel)                                                                                  \
-    do {                                                                                                        \
-        static std::once_flag prd_lds_once;                                                                     \
-        std::call_once(prd_lds_once, [] {                                                                       \
-            (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        });                                                                                                     \
-    } while (0)
-
 template <int P, int CP>
-void tb_launch(float* dqkvg, const float* dog, const float* og, const float* pair, const float* mask, const float* wq, const float* wk,
+int tb_launch(float* dqkvg, const float* dog, const float* og, const float* pair, const float* mask, const float* wq, const float* wk,
                const float* wv, const float* wg, const float* bg, const float* lse, float* x_out, float* ws, int ending, int b, int N,
                int H, int c, hipStream_t stream) {
     const size_t lds = (size_t)TbLds<P, CP>::FLOATS * sizeof(float);
-    PRD_TB_SET_LDS((tri_attn_heads_bwd_kernel<P, CP>));
-    hipLaunchKernelGGL((tri_attn_heads_bwd_kernel<P, CP>), dim3((unsigned)tb_grid(b, N, H)), dim3(TB_NW * 64), lds, stream,
-                       dqkvg, dog, og, pair, mask, wq, wk, wv, wg, bg, lse, x_out, ws, b, N, H, c, ending);
+    return prd_launch<tri_attn_heads_bwd_kernel<P, CP>>(dim3((unsigned)tb_grid(b, N, H)), dim3(TB_NW * 64), lds, stream,
+                                                        dqkvg, dog, og, pair, mask, wq, wk, wv, wg, bg, lse, x_out, ws, b, N, H, c, ending);
 }
 
 }  // namespace
@@ -482,9 +467,6 @@ extern "C" int prd_tri_attn_bwd_core_heads(float* dqkvg, const float* dog, const
         return PRD_ERR_ALIGN;
     if ((uintptr_t)lse & 7) return PRD_ERR_ALIGN;
     const int cp = tb_cp(c);
-#define PRD_TB(PP, CC) tb_launch<PP, CC>(dqkvg, dog, og, pair, mask, wq, wk, wv, wg, bg, lse, x_out, ws, ending, b, N, H, c, stream)
-    if (P == 64) { if (cp == 16) PRD_TB(64, 16); else if (cp == 32) PRD_TB(64, 32); else PRD_TB(64, 64); }
-    else { if (cp == 16) PRD_TB(32, 16); else if (cp == 32) PRD_TB(32, 32); else PRD_TB(32, 64); }
-#undef PRD_TB
-    return (int)hipGetLastError();
+    return PRD_FOR_P(P, PP, PRD_FOR_3(cp, CC, 16, 32, 64,
+        tb_launch<PP, CC>(dqkvg, dog, og, pair, mask, wq, wk, wv, wg, bg, lse, x_out, ws, ending, b, N, H, c, stream)));
 }
