@@ -434,6 +434,41 @@ def _alignment_reference(data: Mapping[str, Any], align_to) -> Optional[np.ndarr
     return ref
 
 
+def _quality_reference(data: Mapping[str, Any], assess):
+    """What ``generate_samples(assess=...)`` scores against, from host data alone: None for ``"self"``, else (the [na + nr, 3] reference
+    over the rows of a sample, whether its ligand rows hold coordinates); ValueError for a request that cannot be served."""
+    na, nr = int(data["num_atoms"]), int(data["num_residues"])
+    if isinstance(assess, str):
+        if assess == "self":
+            return None
+        if assess != "input":
+            raise ValueError(f"assess must be None, 'self', 'input' or a Protein, got {assess!r}")
+        ram, rap = torch.as_tensor(data["residue_atom_mask"]), torch.as_tensor(data["residue_atom_pos"])
+        what = None
+        if ram.numel() == 0 or not bool((ram[:, 1] > 0.5).any()):
+            what = "no residue has its C-alpha marked in residue_atom_mask"
+        elif not bool((rap[:, 1] != 0).any()):
+            what = "the C-alpha coordinates are all zero (a protein built from its sequence alone?)"
+        if what is not None:
+            raise ValueError("assess='input' scores the samples against the complex's own coordinates: " + what
+                             + "; use assess='self' or pass a reference structure")
+        ref = np.zeros((na + nr, 3), dtype=np.float32)
+        ref[na:] = np.asarray(rap[:, 1], dtype=np.float32)
+        ligand = na >= 1 and "atom_pos" in data and tuple(torch.as_tensor(data["atom_pos"]).shape) == (na, 3)
+        if ligand:
+            ref[:na] = np.asarray(data["atom_pos"], dtype=np.float32)
+        return ref, ligand
+    if not isinstance(assess, Protein):
+        raise ValueError(f"assess must be None, 'self', 'input' or a Protein, got {type(assess).__name__}")
+    ca = np.asarray(assess.atom_pos, dtype=np.float32)[:, 1]
+    if ca.shape != (nr, 3):
+        raise ValueError(f"assess: the reference has shape {ca.shape}, the complex has {nr} residues ([{nr},3] expected; chains of "
+                         "another length need a sequence alignment, which is out of scope)")
+    ref = np.zeros((na + nr, 3), dtype=np.float32)
+    ref[na:] = ca
+    return ref, False
+
+
 def _structural_reference(align_to):
     """The [m,3] C-alpha coordinates that ``generate_samples(align_to=..., correspondence="structure")`` aligns to by structure: the
     residues of a ``Protein`` whose C-alpha is marked in ``atom_mask[:,1]``, or the rows of an ``[m,3]`` array.  From host data alone;
@@ -463,7 +498,7 @@ def _structural_reference(align_to):
 @torch.inference_mode()
 def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_size: int = 1, seed: int = 0,
                      output_dir: Optional[Union[str, Path]] = None, redesign=None, align_to=None, mirror: bool = True,
-                     correspondence: str = "index"):
+                     correspondence: str = "index", assess=None):
     """Draw ``num_samples`` samples of one featurised complex ``data`` (the dict of ligand_to_data ∪ protein_to_data).
 
     Returns (positions [S,N,3] in Angstrom, logits [S,N,21], proteins, ligand_positions).  With ``output_dir`` the CA
@@ -501,7 +536,21 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     before the model is touched, a reference with fewer than 5 C-alphas, all-zero coordinates or more than 2048 residues.  The scores
     are then TM-align's: ``tmscore`` is normalised by the reference and ``rmsd`` runs over the aligned pairs; the dict and
     ``sample_alignment.npz`` gain ``n_aligned`` [S] and ``mapping`` [S,nr] (the residue index into the reference aligned to residue
-    i of the complex, -1 for none)."""
+    i of the complex, -1 for none).
+
+    ``assess`` (default None: nothing below happens, every return value and file is what it was): score every sample WITHOUT a
+    superposition, with ``protein_redesign_amd.quality`` on the device, before the samples are copied to the host.  ``"self"``: the
+    reference-free metrics of ``quality.assess`` -- ``ca_clashes``, ``ligand_clashes``, ``ligand_self_clashes``,
+    ``ligand_bond_outliers``, ``chain_breaks``, ``pocket_size`` (each [S]) and ``pocket`` [S,nr], the residues that line the sample's
+    pocket.  ``"input"``: also the metrics against the complex's own coordinates -- ``lddt_ca`` [S], ``lddt_ca_per_residue`` [S,nr] and,
+    when the input has ligand positions, ``lddt_pli``, ``lddt_ligand`` and ``pocket_recall`` [S]; refused, before anything is uploaded,
+    for an input without coordinates such as ``protein_from_sequence``.  A ``Protein`` of the same length: ``lddt_ca`` and
+    ``lddt_ca_per_residue`` against it.  The samples are scored as ``model.sample`` returned them; every metric is built from distances,
+    which the transform of ``align_to`` leaves as they are (up to its fp32 rounding), so the order of the two does not matter -- and for
+    the same reason a mirror image scores like the original.  The return value gains one more trailing ``dict`` of numpy arrays, after
+    the alignment dict when both are requested.  ``output_dir`` also receives ``sample_quality.npz`` (the dict) and
+    ``sample_quality.txt``: a ``#`` line naming the columns, then one line per sample holding the scalar metrics in the order of
+    ``quality.SCALAR_COLUMNS`` (those present)."""
     import warnings
 
     from .synthetic import NoiseSource, batch_to
@@ -515,6 +564,7 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
             raise ValueError(f"correspondence='structure': the complex has {rows} rows (ligand atoms + residues), an alignment by "
                              f"structure takes at most {MAX_N} (PRD_TMALIGN_MAX_N)")
     align_ref = _alignment_reference(data, align_to) if align_to is not None and struct_ref is None else None      # likewise
+    quality_ref = _quality_reference(data, assess) if assess is not None else None                                 # likewise
     spec = redesign if redesign is not None else getattr(model, "redesign", None)
     if spec is not None and spec.needs_structure:
         check_complex_structure(data)
@@ -523,7 +573,7 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         spec = spec.to(device)                  # a positions mask is uploaded once, not per batch
     positions, logits = [], []
     first_batch = None
-    on_device = []                              # align_to: the samples stay on the device until they are scored
+    on_device = []                              # align_to / assess: the samples stay on the device until they are scored
     for start in range(0, num_samples, batch_size):
         idx = list(range(start, min(start + batch_size, num_samples)))
         batch = collate_fn([data] * len(idx))
@@ -531,7 +581,7 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         pos, lg = model.sample(batch, sources=[NoiseSource(seed, k) for k in idx], redesign=spec)
         if first_batch is None:
             first_batch = batch                 # sample() prepared it in place: it carries the mask that was used
-        if align_to is not None:
+        if align_to is not None or assess is not None:
             on_device.append(pos)
         else:
             positions.append(pos.cpu())
@@ -539,7 +589,17 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     # every sample of the complex shares the mask: read from the first prepared batch, after the loop (no synchronisation inside it)
     used_mask = first_batch["residue_inv_extra_mask"][0].cpu().numpy() if spec is not None and first_batch is not None else None
     na, nr = int(data["num_atoms"]), int(data["num_residues"])
-    alignment = None
+    alignment = quality = None
+    if assess is not None:                      # on the samples as model.sample returned them: distances do not see align_to's transform
+        from . import quality as QL
+        pos = torch.cat(on_device)
+        ref = torch.from_numpy(quality_ref[0]).to(device) if quality_ref is not None else None
+        scores = QL.assess(pos.float()[:, : na + nr], first_batch, ref, num_atoms=na, num_residues=nr,
+                           ref_has_ligand=quality_ref is not None and quality_ref[1])
+        scores["pocket"] = scores["pocket"][:, na:]
+        quality = {k: v.cpu().numpy() for k, v in scores.items()}
+        if align_to is None:
+            positions = [pos.cpu()]
     if align_to is not None:
         from . import align as AL
         pos = torch.cat(on_device).float()
@@ -593,5 +653,13 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
                 for tmscore in alignment["tmscore"]:
                     f.write(str(float(tmscore)) + "\n")
             np.savez(out / "sample_alignment.npz", **alignment)
+        if quality is not None:
+            from .quality import SCALAR_COLUMNS
+            cols = [c for c in SCALAR_COLUMNS if c in quality]
+            np.savez(out / "sample_quality.npz", **quality)
+            with open(out / "sample_quality.txt", "w") as f:
+                f.write("# " + " ".join(cols) + "\n")
+                for k in range(len(positions)):
+                    f.write(" ".join(str(quality[c][k].item()) for c in cols) + "\n")
     result = (positions, logits, proteins, ligands) + ((used_mask,) if spec is not None else ())
-    return result + ((alignment,) if alignment is not None else ())
+    return result + ((alignment,) if alignment is not None else ()) + ((quality,) if quality is not None else ())
