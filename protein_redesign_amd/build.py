@@ -43,6 +43,9 @@ VARIANTS = {
     "shipped": Variant(["-Rpass-analysis=kernel-resource-usage", "-fno-caret-diagnostics"], [], CSRC, LIB, None),
     "ab": Variant(["-DPRD_AB"], [], os.path.join(CSRC, "ab"), os.path.join(HERE, "libprd_hip_ab.so"), "PRD_AB"),
     "timing": Variant(["-DPRD_TIMING"], [], os.path.join(CSRC, "timing"), os.path.join(HERE, "libprd_hip_timing.so"), None),
+    # every launch replaced by a printed line (csrc/prd_launch.h): host code is what it is about, so the device code, which no call of
+    # this library reaches, is compiled without optimisation (a tenth of the time)
+    "trace": Variant(["-DPRD_LAUNCH_TRACE", "-Xarch_device", "-O0"], [], os.path.join(CSRC, "trace"), os.path.join(HERE, "libprd_hip_trace.so"), None),
     "asan": Variant(["-g"] + _ASAN + ["-fno-omit-frame-pointer"], _ASAN, os.path.join(CSRC, "asan"), os.path.join(HERE, "libprd_hip_asan.so"), None),
 }
 
@@ -227,6 +230,19 @@ def build_asan(verbose: bool = True) -> str:
     return exe
 
 
+def build_trace(verbose: bool = True) -> str:
+    """The launch trace (csrc/prd_launch.h under -DPRD_LAUNCH_TRACE): libprd_hip_trace.so, whose launches print a line each instead of
+    reaching HIP, and the driver tests/native/launch_trace.c linked against it, which walks the entry points over a sweep of shapes,
+    arithmetics and switches.  Host code only; tests/test_launch_trace_cpu.py compares the driver's output with the recorded one.
+    Returns the path of the driver binary."""
+    lib = _build(VARIANTS["trace"], SOURCES, verbose=verbose)
+    exe = os.path.join(VARIANTS["trace"].objdir, "launch_trace")
+    driver = os.path.join(os.path.dirname(HERE), "tests", "native", "launch_trace.c")
+    if _stale(exe, [driver, lib, PRD_HIP_H]):
+        _run([_hipcc(), "-x", "c", driver, "-x", "none", "-O1", "-Wno-format-extra-args", "-o", exe, lib, "-Wl,-rpath," + HERE], verbose)
+    return exe
+
+
 def build_ab(verbose: bool = True) -> str:
     """libprd_hip_ab.so: the library with -DPRD_AB, i.e. INCLUDING the superseded kernels the shipped library leaves out (the
     first-generation split-16 attention cores of csrc/prd_tri.hip, in their three wave-count forms, and the fused form built on
@@ -249,6 +265,8 @@ if __name__ == "__main__":
     if "--timing" in sys.argv:
         print(build_timing())
         sys.exit(0)
+    if "--trace" in sys.argv:
+        sys.exit(subprocess.call([build_trace()]))
     for side, s in SIDE_LIBS.items():
         if s.flag in sys.argv:
             print(build_side(side, force="--force" in sys.argv))

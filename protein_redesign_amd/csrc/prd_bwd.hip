@@ -46,6 +46,8 @@ PRD_DEV void ln_cll_bwd(float (&dy)[KH], const float (&y)[KH], float rstd) {
     for (int k = 0; k < KH; ++k) dy[k] = rstd * (dy[k] - m1 - y[k] * m2);
 }
 
+// LDS bytes: W_out, W_ogate and their transposed images, four matrices [P][P + 4] | b_out [P] | b_ogate [P]
+static size_t tri_mul_out_bwd_lds_bytes(int P) { return ((size_t)4 * P * (P + 4) + 2 * P) * sizeof(float); }
 template <int P, int NW>
 __global__ __launch_bounds__(NW * 64) void tri_mul_out_bwd_kernel(
     float* __restrict__ dz_out, float* __restrict__ dgp_out, float* __restrict__ dO, float* __restrict__ dx1,
@@ -153,6 +155,8 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_out_bwd_kernel(
     }
 }
 
+// LDS bytes: W_proj, W_gate [2 P][P + 4] and their transposed images [P][2 P + 4] (split-16: fp16 hi | lo planes of [2 P][P], no padding) | b_proj, b_gate [2 P] each
+static size_t tri_mul_proj_bwd_lds_bytes(int P, bool b3) { return (b3 ? (size_t)8 * P * P + 4 * P : (size_t)2 * 2 * P * (P + 4) + (size_t)2 * P * (2 * P + 4) + 4 * P) * sizeof(float); }
 template <int P, int NW, bool B3>                   // B3: the eight row GEMMs in the fp16 x 2 split form (gemm mode 1), weights x 16
 __global__ __launch_bounds__(NW * 64) void tri_mul_proj_bwd_kernel(
     float* __restrict__ dpair, float* __restrict__ dpp_out, float* __restrict__ dpg_out,
@@ -344,6 +348,8 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_proj_bwd_kernel(
 // projections' input gradient, the LayerNorm backward and the weight gradients are row GEMMs / slab reductions on the caller's side.
 constexpr int TB_PITCH = 20;        // LDS pitch (floats) of the [N][16] arrays
 constexpr float LOG2E = 1.4426950408889634f;
+// LDS bytes: weights [64][P + 4] | Q, K, V and one more [npad][16] array of pitch TB_PITCH | four vectors [npad]
+static size_t tri_attn_bwd_core_lds_bytes(int P, int npad) { return ((size_t)64 * (P + 4) + (size_t)4 * npad * TB_PITCH + 4 * (size_t)npad) * sizeof(float); }
 template <int P>
 __global__ __launch_bounds__(512) void tri_attn_bwd_core_kernel(
     float* __restrict__ dqkvg, const float* __restrict__ dog, const float* __restrict__ pair, const float* __restrict__ mask,
@@ -1009,6 +1015,8 @@ __global__ __launch_bounds__(256) void linear_wgrad_narrow_kernel(float* __restr
 // the input stage, modules.py:35-71): dtable[c][:] = sum of dy over the rows with idx == c.  The BLAS form (one-hot^T dy) is the
 // same long-K, tiny-output GEMM as the linear weight gradients (475 us per table); here a wave keeps a private [card][C] table in
 // LDS (lane = channel, one row at a time: no conflicts, fixed order), the four waves and then the slabs are summed in order.
+// LDS bytes of both embedding weight-gradient kernels: a private table [card][64] for each of the four waves
+static size_t embed_wgrad_lds_bytes(int card) { return (size_t)4 * card * 64 * sizeof(float); }
 __global__ __launch_bounds__(256) void embed_wgrad_kernel(float* __restrict__ part, const long long* __restrict__ idx, const float* __restrict__ dy,
                                                           const float* __restrict__ row_scale, long rows, int card, int C, int lddy, int rows_per_wg) {
     extern __shared__ float etab[];                          // [4 waves][card][64]
@@ -1379,7 +1387,7 @@ extern "C" int prd_tri_mul_out_bwd_amax(float* dz, float* dgp, float* dO, float*
     if (dO_batch_channels < P) return PRD_ERR_ARG;
     constexpr int NWB = 8;
     const int ldn = prd_round_up(N, 32);
-    const size_t lds = ((size_t)4 * P * (P + 4) + 2 * P) * sizeof(float);
+    const size_t lds = tri_mul_out_bwd_lds_bytes(P);
     const int grid = grid_for((long)b * N * prd_ceil_div(N, 32), 4, 256);
     return PRD_FOR_P(P, PP, prd_launch<tri_mul_out_bwd_kernel<PP, NWB>>(dim3(grid), dim3(NWB * 64), lds, stream, dz, dgp, dO, dx1, dy, pair, O,
                                                                         w_out, b_out, w_ogate, b_ogate, w_out_t, w_ogate_t, b, N, ldn, x_out,
@@ -1396,9 +1404,8 @@ extern "C" int prd_tri_mul_proj_bwd(float* dpair, float* dpp, float* dpg, const 
     constexpr int NWB = 8;
     const int ldn = prd_round_up(N, 32);
     const bool b3 = arith == PRD_ARITH_SPLIT16;
-    const size_t lds = b3 ? ((size_t)8 * P * P + 4 * P) * sizeof(float)
-                          : ((size_t)2 * 2 * P * (P + 4) + (size_t)2 * P * (2 * P + 4) + 4 * P) * sizeof(float);
-    if (lds > 160 * 1024) return PRD_ERR_UNSUPPORTED;
+    const size_t lds = tri_mul_proj_bwd_lds_bytes(P, b3);
+    if (lds > PRD_LDS_MAX) return PRD_ERR_UNSUPPORTED;
     const int grid = grid_for((long)b * N * prd_ceil_div(N, 32), 4, 256);
     return PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3, BB,
         prd_launch<tri_mul_proj_bwd_kernel<PP, NWB, BB>>(dim3(grid), dim3(NWB * 64), lds, stream, dpair, dpp, dpg, dAB, dx1, pair,
@@ -1409,10 +1416,10 @@ extern "C" int prd_tri_attn_bwd_core(float* dqkvg, const float* dog, const float
                                      const float* wk, const float* wv, const float* wg, const float* bg, int ending,
                                      int b, int N, int P, int H, int c, hipStream_t stream) {
     if (!dqkvg || !dog || !pair || !mask || !wq || !wk || !wv || !wg || !bg || b <= 0 || N <= 0) return PRD_ERR_ARG;
-    if ((P != 32 && P != 64) || c != 16 || H * c != 64) return PRD_ERR_UNSUPPORTED;
+    if ((P != 32 && P != 64) || !prd_heads_4x16(H, c)) return PRD_ERR_UNSUPPORTED;
     const int npad = prd_round_up(N, 32);
-    const size_t lds = ((size_t)64 * (P + 4) + (size_t)4 * npad * TB_PITCH + 4 * (size_t)npad) * sizeof(float);
-    if (lds > 160 * 1024) return PRD_ERR_UNSUPPORTED;          // rows beyond N = 416: not in this cut
+    const size_t lds = tri_attn_bwd_core_lds_bytes(P, npad);
+    if (lds > PRD_LDS_MAX) return PRD_ERR_UNSUPPORTED;          // rows beyond N = 416: not in this cut
     const long nwork = (long)b * N * H;
     const int grid = (int)(nwork < 256 ? nwork : 256);
     const int nthreads = 512;                                   // 8 waves: two per SIMD cover each other's dependent MFMA chains
@@ -1444,6 +1451,8 @@ PRD_DEV unsigned row_exp_biased(const float (&x)[KH]) {
 PRD_DEV float pow2_from_biased(unsigned eb) { return __uint_as_float(eb << 23); }             // 2^(eb - 127)
 PRD_DEV float inv_pow2_from_biased(unsigned eb) { return __uint_as_float((254u - eb) << 23); } // 2^(127 - eb)
 
+// LDS bytes: the weights as fp16 hi | lo planes, [OUT][K] floats in all | bias [OUT]
+static size_t pair_linear_rows_lds_bytes(int K, int OUT) { return ((size_t)OUT * K + OUT) * sizeof(float); }
 template <int K, int NW>
 __global__ __launch_bounds__(NW * 64) void pair_linear_rows_kernel(
     float* __restrict__ out, float* __restrict__ xn_out, const float* __restrict__ x, const float* __restrict__ w,
@@ -1561,7 +1570,7 @@ extern "C" int prd_pair_linear(float* out, const float* x, const float* w, const
          reinterpret_cast<uintptr_t>(mask_pos)) & 15)
         return PRD_ERR_ALIGN;
     constexpr int NWP = 8;
-    const size_t lds = ((size_t)OUT * K + OUT) * sizeof(float);
+    const size_t lds = pair_linear_rows_lds_bytes(K, OUT);
     const long ntask = (rows + 31) / 32;
     const int grid = grid_for(ntask, NWP, 256);          // one persistent workgroup per CU (the register budget allows two waves per SIMD)
     return PRD_FOR_2(K, KK, 64, 256,
@@ -1600,7 +1609,6 @@ extern "C" size_t prd_linear_wgrad_workspace(long long rows, int O, int I) {
 extern "C" int prd_linear_wgrad(float* dw, float* db, const float* dy, const float* x, long long rows, int O, int I, int lddy, int ldx,
                                 float* ws, size_t ws_bytes, int arith, hipStream_t stream) {
     PRD_SPLIT_ARITH(arith);
-    (void)tune;
     if (!dw || !dy || !x || !ws || rows <= 0 || O <= 0 || I <= 0) return PRD_ERR_ARG;
     const bool narrow = O <= 16;
     if ((!narrow && (O % 64)) || (I % 64) || O > 256 || I > 256) return PRD_ERR_UNSUPPORTED;
@@ -1649,7 +1657,7 @@ extern "C" int prd_embed_wgrad_multi(float* dtables, const long long* const* idx
     if (ws_bytes < prd_embed_wgrad_workspace(rows, total, C)) return PRD_ERR_WORKSPACE;
     const long slabs = wgrad_slabs(rows);
     const int rows_per_wg = (int)((rows + slabs - 1) / slabs);
-    const size_t lds = (size_t)4 * total * 64 * sizeof(float);
+    const size_t lds = embed_wgrad_lds_bytes(total);
     PRD_TRY(prd_launch<embed_wgrad_multi_kernel>(dim3((unsigned)slabs), dim3(256), lds, stream, ws, em, dy, (long)rows, C, lddy, rows_per_wg));
     const int n = total * C;
     return prd_launch<linear_wgrad_reduce_kernel>(dim3((n + 63) / 64), dim3(256), 0, stream, dtables, (float*)nullptr, ws, n, n, (int)slabs);
@@ -1667,7 +1675,7 @@ extern "C" int prd_embed_wgrad(float* dtable, const long long* idx, const float*
     if (ws_bytes < prd_embed_wgrad_workspace(rows, card, C)) return PRD_ERR_WORKSPACE;
     const long slabs = wgrad_slabs(rows);
     const int rows_per_wg = (int)((rows + slabs - 1) / slabs);
-    const size_t lds = (size_t)4 * card * 64 * sizeof(float);
+    const size_t lds = embed_wgrad_lds_bytes(card);
     PRD_TRY(prd_launch<embed_wgrad_kernel>(dim3((unsigned)slabs), dim3(256), lds, stream, ws, idx, dy, row_scale, (long)rows, card, C, lddy, rows_per_wg));
     const int n = card * C;
     return prd_launch<linear_wgrad_reduce_kernel>(dim3((n + 63) / 64), dim3(256), 0, stream, dtable, (float*)nullptr, ws, n, n, (int)slabs);

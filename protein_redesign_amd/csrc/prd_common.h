@@ -662,16 +662,22 @@ struct WaveTasks {
     (void)tune; (void)arith_full;                                                                \
     if ((a) < 0 || ((a) & 0xff) > 1) return -1;                                                  \
     (a) &= 0xff
-#define PRD_TGET_TA_VARIANT(t) ((t) & 15)                   /* first-generation attention core: 0 = default dispatch */
-#define PRD_TGET_TA2_NO_V3(t) (((t) >> 4) & 1)
-#define PRD_TGET_TA2_NO_LONG(t) (((t) >> 5) & 1)
-#define PRD_TGET_TA2_FLAGS(t) ((((t) >> 6) & 1) ? (((t) >> 7) & 31) : -1)
-#define PRD_TGET_TA2_NO_TAIL_SPLIT(t) (((t) >> 19) & 1)
-#define PRD_TGET_TA2_NO_GV(t) (((t) >> 21) & 1)
-#define PRD_TGET_TMP_NW16(t) (((t) >> 22) & 1)
-#define PRD_TGET_TMS_D3(t) ((((t) >> 13) & 3) == 3)             /* 8 waves, three chunks of operands in flight */
-#define PRD_TGET_OL_GEN2(t) (((t) >> 12) & 1)
-#define PRD_TGET_TMS_NW(t) ((((t) >> 13) & 3) == 1 ? 12 : (((t) >> 13) & 3) == 2 ? 16 : 8)
+// the switches of a `tune` word, read through the PRD_TUNE_* macros of include/prd_hip.h (the bit positions live there only)
+#define PRD_TGET_TA_VARIANT(t) ((t) & PRD_TUNE_TA_VARIANT_MASK)    /* first-generation attention core: 0 = default dispatch */
+#define PRD_TGET_TA2_NO_V3(t) (((t) & PRD_TUNE_TA2_NO_V3) != 0)
+#define PRD_TGET_TA2_NO_LONG(t) (((t) & PRD_TUNE_TA2_NO_LONG) != 0)
+#define PRD_TA2_FLAGS_FIELD(f) (PRD_TUNE_TA2_FLAGS(f) & ~PRD_TUNE_TA2_FLAGS_SET)     /* the five flag bits where the word keeps them */
+#define PRD_TGET_TA2_FLAGS(t) (((t) & PRD_TUNE_TA2_FLAGS_SET) ? ((t) & PRD_TA2_FLAGS_FIELD(31)) / PRD_TA2_FLAGS_FIELD(1) : -1)
+#define PRD_TGET_TA2_NO_TAIL_SPLIT(t) (((t) & PRD_TUNE_TA2_NO_TAIL_SPLIT) != 0)
+#define PRD_TGET_TA2_NO_XCD8(t) (((t) & PRD_TUNE_TA2_NO_XCD8) != 0)
+#define PRD_TGET_TA2_NO_GV(t) (((t) & PRD_TUNE_TA2_NO_GV) != 0)
+#define PRD_TGET_TMP_NW16(t) (((t) & PRD_TUNE_TMP_NW16) != 0)
+#define PRD_TGET_TMS(t) ((t) & PRD_TUNE_TMS_DEPTH3)                /* the two-bit field of the split contraction: 0, NW12, NW16 or DEPTH3 */
+#define PRD_TGET_TMS_D3(t) (PRD_TGET_TMS(t) == PRD_TUNE_TMS_DEPTH3)            /* 8 waves, three chunks of operands in flight */
+#define PRD_TGET_OL_GEN2(t) (((t) & PRD_TUNE_OL_GEN2) != 0)
+#define PRD_TGET_TMS_NW(t) (PRD_TGET_TMS(t) == PRD_TUNE_TMS_NW12 ? 12 : PRD_TGET_TMS(t) == PRD_TUNE_TMS_NW16 ? 16 : 8)
 
+// the head layout of the tuned attention kernels: 4 heads x 16 channels (other layouts: csrc/prd_tri_heads.hip)
+static inline bool prd_heads_4x16(int H, int c) { return c == 16 && H * c == 64; }
 static inline int prd_ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int prd_round_up(int a, int b) { return prd_ceil_div(a, b) * b; }

@@ -355,6 +355,8 @@ __global__ __launch_bounds__(NWK * 64) void gemm_skinny_kernel(PrdGemm g) {   //
 // workgroup owns a 64x64 tile (2x2 waves of 32x32), streams K in 32-wide chunks through double-buffered LDS with coalesced
 // 128-byte row segments, and -- for long K -- KG groups of four waves take every KG-th chunk (split-K inside the workgroup,
 // merged in LDS in a fixed order).  Optional fused LayerNorm of the A rows (statistics in a prologue pass).
+// LDS bytes: per wave group two buffers of A hi | A lo | B hi | B lo planes (64 rows x 64 bytes) | LayerNorm mean [64] | rstd [64]
+static size_t gemm_h2_lds_bytes(int KG) { return (size_t)KG * 2 * 4 * 64 * 64 + 512; }
 template <int KG>
 __global__ __launch_bounds__(256 * KG) void gemm_h2_kernel(PrdGemm g) {
     constexpr int PLANE = 64 * 64;                      // bytes of one operand plane of a 64-row, 32-wide chunk
@@ -542,6 +544,8 @@ __global__ __launch_bounds__(256 * KG) void gemm_h2_kernel(PrdGemm g) {
 // rows r and r + 8 on one read slot: 45-50 % of the kernel's LDS cycles were conflicts), and -- for long K -- KG groups take every KG-th chunk with their own LDS stages.  The four
 // waves of a group each take one 16-wide k-step of a chunk; partial tiles are merged in LDS in a fixed order.  LayerNorm
 // statistics come from the ring itself (the whole row is in flight: K <= 64 D KG), so the first load is the only exposed one.
+// LDS bytes: per wave group two stages of A hi | A lo | B hi | B lo planes (32 rows x 64 fp16; the partial tiles alias them) | LayerNorm sums
+static size_t gemm_ring_lds_bytes(int KG) { return (size_t)KG * 2 * 4 * 32 * 64 * 2 + 1024; }
 template <int D, int KG, bool LN, bool BKN = false>      // BKN: B is given as [K][N] (row pitch ldb) -- staged transposed, 2 bytes at a time
 __global__ __launch_bounds__(256 * KG) void gemm_ring_kernel(PrdGemm g) {
     constexpr int KCH = 64, NJ = KCH / 32, PL = 32 * KCH * 2, STAGE = 4 * PL;      // plane = 32 rows x 64 fp16; A hi | A lo | B hi | B lo
@@ -721,13 +725,11 @@ __global__ __launch_bounds__(256 * KG) void gemm_ring_kernel(PrdGemm g) {
 
 template <int D, int KG>
 static int launch_ring(const PrdGemm& g, dim3 grid, hipStream_t stream) {
-    const size_t lds = (size_t)KG * 2 * 4 * 32 * 64 * 2 + 1024;
-    return PRD_FOR_BOOL(g.a_ln, LN, prd_launch<gemm_ring_kernel<D, KG, LN>>(grid, dim3(256 * KG), lds, stream, g));
+    return PRD_FOR_BOOL(g.a_ln, LN, prd_launch<gemm_ring_kernel<D, KG, LN>>(grid, dim3(256 * KG), gemm_ring_lds_bytes(KG), stream, g));
 }
 
 static int launch_ring_bkn(const PrdGemm& g, dim3 grid, hipStream_t stream) {      // B as [K][N]: P V of SPAttention (K = keys)
-    const size_t lds = (size_t)2 * 4 * 32 * 64 * 2 + 1024;
-    return prd_launch<gemm_ring_kernel<8, 1, false, true>>(grid, dim3(256), lds, stream, g);
+    return prd_launch<gemm_ring_kernel<8, 1, false, true>>(grid, dim3(256), gemm_ring_lds_bytes(1), stream, g);
 }
 
 // ---- node-row linears with LARGE weights (the single-track transition 512 -> 2048 -> 512): K split ACROSS workgroups ----------
@@ -748,6 +750,8 @@ constexpr int SL_LDS = (SL_BM + SL_BN) * SL_KS * 4;                  // hi | lo 
 // LDS region of its own: rows of 32 EX bytes per plane, read as one contiguous block per step), so the groups stay balanced and the
 // grid is the same one workgroup per CU.  The single track's attention out-projection rides in its transition's first layer
 // this way (prd_single_fc1_folded).
+// LDS bytes: A hi | A lo [160][256 B], W hi | W lo [64][256 B] (SL_LDS) | with a second A segment its 16 EX columns per slab group, [160 + 64] rows of 32 EX bytes, hi | lo
+static size_t gemm_slab_lds_bytes(int ex) { return SL_LDS + (size_t)(SL_BM + SL_BN) * 32 * ex * 2; }
 template <int EX>
 __global__ __launch_bounds__(SL_NW * 64) void gemm_slab_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                                float* __restrict__ ws, int M, int N, int K, int lda, int ldb,
@@ -1143,7 +1147,7 @@ extern "C" int prd_single_fc1_folded(const float* single, const float* og, const
     if ((size_t)SK * M * Hd * sizeof(float) > ws_bytes) return PRD_ERR_WORKSPACE;
     const int xmap = slab_xmap(SK, tiles_n);
     const dim3 grid((unsigned)(tiles_m * tiles_n * SK));
-    const size_t lds = SL_LDS + (size_t)(SL_BM + SL_BN) * 32 * ex * 2;
+    const size_t lds = gemm_slab_lds_bytes(ex);
     PRD_TRY(prd_launch<gemm_slab_kernel<1>>(grid, dim3(SL_NW * 64), lds, stream, single, w1cat, ws, M, Hd, S, S, S + HC, tiles_m, tiles_n, nslab,
                                             spw, xmap, H2_WSCALE, og, HC));
     return prd_launch<fc1_fold_reduce_kernel<64>>(dim3((unsigned)M), dim3(128 * prd_ceil_div(Hd, 512)), 0, stream, ws, SK, M, Hd, S, single, og, woT,
@@ -1174,7 +1178,7 @@ extern "C" int prd_gemm(const PrdGemm* args, hipStream_t stream) {
             const int SK = prd_ceil_div(nslab, spw);
             if ((size_t)SK * g.M * g.N * sizeof(float) > g.ws_bytes) return PRD_ERR_WORKSPACE;
             const int xmap = slab_xmap(SK, tiles_n);
-            PRD_TRY(prd_launch<gemm_slab_kernel<0>>(dim3((unsigned)(tiles_m * tiles_n * SK)), dim3(SL_NW * 64), SL_LDS, stream, g.A, g.B, g.ws, g.M, g.N,
+            PRD_TRY(prd_launch<gemm_slab_kernel<0>>(dim3((unsigned)(tiles_m * tiles_n * SK)), dim3(SL_NW * 64), gemm_slab_lds_bytes(0), stream, g.A, g.B, g.ws, g.M, g.N,
                                                     g.K, g.lda, g.ldb, tiles_m, tiles_n, nslab, spw, xmap, H2_WSCALE, (const float*)nullptr, 0));
             return prd_launch<gemm_slab_reduce_kernel>(dim3((unsigned)(g.M * prd_ceil_div(g.N, 512))), dim3(128), 0, stream, g, g.ws, SK);
         }
@@ -1193,8 +1197,8 @@ extern "C" int prd_gemm(const PrdGemm* args, hipStream_t stream) {
             gx.tile_hint = -8;
             grid.x = 8u * prd_ceil_div(g.M, 64) * prd_ceil_div(prd_ceil_div(g.N, 64), 8);
         }
-        if (g.K >= 1024) return prd_launch<gemm_h2_kernel<4>>(grid, dim3(1024), (size_t)4 * 2 * 4 * 64 * 64 + 512, stream, gx);
-        return prd_launch<gemm_h2_kernel<1>>(grid, dim3(256), (size_t)2 * 4 * 64 * 64 + 512, stream, gx);
+        if (g.K >= 1024) return prd_launch<gemm_h2_kernel<4>>(grid, dim3(1024), gemm_h2_lds_bytes(4), stream, gx);
+        return prd_launch<gemm_h2_kernel<1>>(grid, dim3(256), gemm_h2_lds_bytes(1), stream, gx);
     }
     // gemm mode 1, latency-bound node-row linears (fewer 64x64 tiles than that): 32x32 tiles with a deep operand ring
     // (batched, e.g. the per-head logits / P V of SPAttention: same kernel, blockIdx.y = batch; without the fused LayerNorm)

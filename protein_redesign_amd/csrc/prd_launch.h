@@ -11,6 +11,58 @@
 constexpr size_t PRD_LDS_DEFAULT_LIMIT = 48 * 1024;
 constexpr int PRD_LDS_MAX = 160 * 1024;
 
+#ifdef PRD_LAUNCH_TRACE
+// The trace build (build.py: variant "trace"; tests/native/launch_trace.c): a launch prints one line -- kernel, grid, block, LDS bytes and
+// every argument (integers and floats by value, pointers by address, structures as their bytes in hex) -- and returns 0.  No HIP function
+// is called, so every host decision above a launch can be compared between two trees on a machine without a GPU.
+#include <cxxabi.h>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <type_traits>
+#include <typeinfo>
+template <class T>
+static void prd_trace_arg(const T& v) {
+    if constexpr (std::is_pointer_v<T> || std::is_null_pointer_v<T>) printf(" %p", (const void*)v);
+    else if constexpr (std::is_floating_point_v<T>) printf(" %.9g", (double)v);
+    else if constexpr (std::is_integral_v<T> || std::is_enum_v<T>) printf(" %lld", (long long)v);
+    else {
+        unsigned char bytes[sizeof(T)];
+        memcpy(bytes, &v, sizeof(T));
+        printf(" {");
+        for (size_t i = 0; i < sizeof(T); ++i) printf("%02x", bytes[i]);
+        printf("}");
+    }
+}
+template <auto Kernel, class... Args>
+static int prd_launch(dim3 grid, dim3 block, size_t lds, hipStream_t, Args... args) {
+    // the kernel with its template arguments: the mangled name of a type local to this instantiation holds the kernel's own
+    // ("...XadL_Z<kernel>EE...E4Here"), whose shortest piece that demangles is "[(anonymous namespace)::]name<arguments>"; a kernel
+    // that is no template and lies in no namespace is "_Z<length><name><parameters>"
+    struct Here {};
+    const char* mangled = strstr(typeid(Here).name(), "XadL_Z");
+    char piece[1024] = "?";
+    char* full = nullptr;
+    int plain = 0, at = 0;
+    if (mangled && sscanf(mangled + 6, "%d%n", &plain, &at) == 1 && mangled[6 + at + plain] != 'I') {
+        snprintf(piece, sizeof piece, "%.*s", plain, mangled + 6 + at);
+    } else if (mangled) {
+        const char* start = mangled + 4;
+        for (const char* e = strchr(start, 'E'); e && !full; e = strchr(e + 1, 'E')) {
+            snprintf(piece, sizeof piece, "%.*s", (int)(e + 1 - start), start);
+            full = abi::__cxa_demangle(piece, nullptr, nullptr, nullptr);
+        }
+    }
+    const char* name = full ? full : piece;
+    if (!strncmp(name, "(anonymous namespace)::", 23)) name += 23;
+    const int len = (int)strlen(name);
+    printf("L %.*s grid %u %u %u block %u %u %u lds %zu args", len, name, grid.x, grid.y, grid.z, block.x, block.y, block.z, lds);
+    (prd_trace_arg(args), ...);
+    printf("\n");
+    free(full);
+    return 0;
+}
+#else
 // launches Kernel<<<grid, block, lds, stream>>>(args...); returns 0 or the hipError_t of the raise / the launch
 template <auto Kernel, class... Args>
 static int prd_launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
@@ -23,6 +75,7 @@ static int prd_launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, Arg
     hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
     return (int)hipGetLastError();
 }
+#endif
 
 // an entry point with several launches returns the first non-zero result and launches nothing after it
 #define PRD_TRY(launch)                                                                                         \

@@ -154,6 +154,8 @@ __global__ void time_embed_kernel(float* __restrict__ eb, const int64_t* __restr
 // pair_init: pair = static + m2 * (W_d rbf(d) + ebeta).  B operand (rbf features) generated in
 // registers, A operand W_d from LDS; never materialises [N,N,dist_dim].
 // ------------------------------------------------------------------------------------------------
+// LDS bytes: W_dist [P][DK + 4] | centers [DK]
+size_t pair_init_lds_bytes(int P, int DK) { return ((size_t)P * (DK + 4) + DK) * sizeof(float); }
 template <int P>
 __global__ __launch_bounds__(WG) void pair_init_kernel(float* __restrict__ pair, const float* __restrict__ stat,
                                                        const float* __restrict__ z, const float* __restrict__ mask,
@@ -212,6 +214,8 @@ __global__ __launch_bounds__(WG) void pair_init_kernel(float* __restrict__ pair,
 
 // pair_init on the fp16 matrix pipe (gemm mode 1; dist_dim a multiple of 128): the radial-basis features are generated per K
 // step in natural order and split into fp16 hi + lo, W_d sits in LDS as hi | lo planes (prd_common.h: h2_nat_step).
+// LDS bytes: W_dist as fp16 hi | lo planes [2][P][DK / 8] of 16 bytes | centers [DK]
+size_t pair_init_h2_lds_bytes(int P, int DK) { return (size_t)4 * P * DK + (size_t)DK * 4; }
 template <int P>
 __global__ __launch_bounds__(WG) void pair_init_h2_kernel(float* __restrict__ pair, const float* __restrict__ stat,
                                                           const float* __restrict__ z, const float* __restrict__ mask,
@@ -265,6 +269,8 @@ __global__ __launch_bounds__(WG) void pair_init_h2_kernel(float* __restrict__ pa
 }
 
 // OPM tail on the fp16 matrix pipe (gemm mode 1; C a multiple of 128): the products a_i * b_j are generated per K step.
+// LDS bytes: W_out as fp16 hi | lo planes [2][P][C / 8] of 16 bytes | bias [P]
+size_t opm_pair_h2_lds_bytes(int P, int C) { return (size_t)4 * P * C + (size_t)P * 4; }
 template <int P>
 __global__ __launch_bounds__(WG) void opm_pair_h2_kernel(float* out, const float* pair, const float* __restrict__ ab,
                                                          const float* __restrict__ mask, const float* __restrict__ wo,
@@ -378,6 +384,8 @@ __global__ __launch_bounds__(WG) void pair_bias_kernel(float* __restrict__ out, 
 // 105 MB at N = 320) and three prologues / tails are paid; here the row stays in registers from the radial-basis GEMM to the
 // bias heads and is written once (1 U + the two [H,N,N] outputs).  The arithmetic of each stage is that of its own kernel
 // (pair_init_h2_kernel, opm_pair_h2_kernel, pair_bias_kernel), in the same order.  A task = (batch row bi = bb N + i, 32 columns j).
+// LDS bytes: W_dist planes [2][P][DK / 8] | W_out planes [2][P][C / 8] | centers [DK] | bias [P] | bias-head rows [2][8 P] | two vectors per head set [2][P] each
+size_t pair_head_lds_bytes(int P, int DK, int C) { return (size_t)4 * P * DK + (size_t)4 * P * C + ((size_t)DK + P + 16 * P + 4 * P) * 4; }
 template <int P, int NW>
 __global__ __launch_bounds__(NW * 64) void pair_head_h2_kernel(
     float* __restrict__ pair, const float* __restrict__ stat, const float* __restrict__ z, const float* __restrict__ mask,
@@ -495,6 +503,8 @@ __global__ __launch_bounds__(NW * 64) void pair_head_h2_kernel(
 // ------------------------------------------------------------------------------------------------
 // OPM tail: pair[i,j,:] += m2 * (W_o (a_i*b_j) + b_o) / (m2 + 1e-3)
 // ------------------------------------------------------------------------------------------------
+// LDS bytes: W_out [P][C + 4] | bias [P]
+size_t opm_pair_lds_bytes(int P, int C) { return ((size_t)P * (C + 4) + P) * sizeof(float); }
 template <int P>
 __global__ __launch_bounds__(WG) void opm_pair_kernel(float* out, const float* pair, const float* __restrict__ ab,
                                                       const float* __restrict__ mask, const float* __restrict__ wo,
@@ -618,6 +628,10 @@ __global__ __launch_bounds__(WG) void outer_linear_kernel(float* out, const floa
 // tasks from the device queue on its own.
 // The product term W1 (x_i * x_j) is SYMMETRIC in (i, j): a task (i, 32-block of j >= block of i) computes it once and
 // writes both out[i,j] = S + u_i - u_j + b and out[j,i] = S + u_j - u_i + b  (55 % of the MFMAs of the full square).
+// LDS bytes: W1 [P][S + 4] | bias [P]
+size_t outer_linear_res_lds_bytes(int P, int S) { return ((size_t)P * (S + 4) + P) * sizeof(float); }
+// W1 stays resident in LDS up to this size only (beyond: outer_linear_kernel streams it in K chunks)
+constexpr size_t OUTER_LINEAR_RES_LDS_MAX = 150 * 1024;
 template <int P, int NW>
 __global__ __launch_bounds__(NW * 64) void outer_linear_res_kernel(int* queue, float* out, const float* pair,
                                                                    const float* __restrict__ x, const float* __restrict__ u,
@@ -712,6 +726,8 @@ __global__ __launch_bounds__(NW * 64) void outer_linear_res_kernel(int* queue, f
 // The same on the fp16 matrix pipe (gemm mode 1): W1 as fp16 hi | lo planes (the size of the fp32 image, so it stays resident),
 // the generated operand x_i * x_j split per K step, three products per step (prd_common.h: rowgemm_h2 scheme).  K runs in
 // natural order: K step s of lane (r, hi) covers k = 16 s + 8 hi .. + 7.  S must be a multiple of 128.
+// LDS bytes: W1 as fp16 hi | lo planes [2][P][S / 8] of 16 bytes | bias [P]
+size_t outer_linear_res_h2_lds_bytes(int P, int S) { return (size_t)4 * P * S + 4 * P; }
 template <int P, int NW>
 __global__ __launch_bounds__(NW * 64) void outer_linear_res_h2_kernel(float* out, const float* pair,
                                                                       const float* __restrict__ x, const float* __restrict__ u,
@@ -791,6 +807,8 @@ __global__ __launch_bounds__(NW * 64) void outer_linear_res_h2_kernel(float* out
 // ------------------------------------------------------------------------------------------------
 // pair transition: pair += W2 relu(W1 LN(pair) + b1) + b2  (hidden 4P kept in registers)
 // ------------------------------------------------------------------------------------------------
+// LDS bytes: W1 [4 P][P + 4] | W2 [P][4 P + 4] | b1 [4 P] | b2 [P]
+size_t pair_transition_lds_bytes(int P) { return ((size_t)4 * P * (P + 4) + (size_t)P * (4 * P + 4) + 5 * P) * sizeof(float); }
 template <int P, int NW>
 __global__ __launch_bounds__(NW * 64) void pair_transition_kernel(int* queue, float* out, const float* pair, const float* __restrict__ w1,
                                                                   const float* __restrict__ b1, const float* __restrict__ w2,
@@ -847,6 +865,8 @@ __global__ __launch_bounds__(NW * 64) void pair_transition_kernel(int* queue, fl
 // All three are row-local, so one pass reads og + pair and writes pair (+ the H-channel bias) instead of three
 // kernels reading / writing the pair tensor three times.
 // ------------------------------------------------------------------------------------------------
+// LDS bytes: W1 [4 P][P + 4] | W2 [P][4 P + 4] | W_o [P][64 + 4] | b1 [4 P] | b2 [P] | b_o [P] | bias head [8][P]
+size_t block_tail_lds_bytes(int P) { return ((size_t)4 * P * (P + 4) + (size_t)P * (4 * P + 4) + (size_t)P * 68 + 6 * P + 8 * P) * sizeof(float); }
 template <int P, int NW>
 __global__ __launch_bounds__(NW * 64) void block_tail_kernel(int* queue, float* pair, const float* __restrict__ og,
                                                              const float* __restrict__ wo, const float* __restrict__ bo,
@@ -1002,6 +1022,8 @@ __global__ __launch_bounds__(NW * 64) void block_tail_kernel(int* queue, float* 
 // prd_pair_transition (og == nullptr: no attention projection, optional residual, out may differ from pair).
 //   raw = pair (+ W_o og + b_o);  out = (residual ? raw : 0) + W_2 relu(W_1 LN(raw) + b_1) + b_2;  bias_out = Linear_h(LN(out))
 // ------------------------------------------------------------------------------------------------
+// LDS bytes: fp16 hi | lo planes of W1 [2][4 P][P / 8], W2 [2][P][4 P / 8] and W_o [2][P][64 / 8], 16 bytes each | b1 [4 P] | b2, b_o [2 P] | bias head [8][P]
+size_t pair_tail_h2_lds_bytes(int P) { return ((size_t)2 * 4 * P * (P / 8) + (size_t)2 * P * (4 * P / 8) + (size_t)2 * P * 8) * 16 + (size_t)(4 * P + 2 * P + 8 * P) * 4; }
 template <int P, int NW>
 __global__ __launch_bounds__(NW * 64) void pair_tail_h2_kernel(float* out, const float* pair, const float* __restrict__ og,
                                                                const float* __restrict__ wo, const float* __restrict__ bo,
@@ -1502,13 +1524,12 @@ extern "C" int prd_pair_init(float* pair, const float* static_pair, const float*
     if (!pair || !static_pair || !z || !mask || !centers || !w_dist || !ebeta || b <= 0 || N <= 0) return PRD_ERR_ARG;
     PRD_CHECK_P(P);
     if (dist_dim <= 0 || (dist_dim & 7)) return PRD_ERR_UNSUPPORTED;
-    const size_t lds = ((size_t)P * (dist_dim + 4) + dist_dim) * sizeof(float);
-    if (lds > 160 * 1024) return PRD_ERR_UNSUPPORTED;
+    const size_t lds = pair_init_lds_bytes(P, dist_dim);
+    if (lds > PRD_LDS_MAX) return PRD_ERR_UNSUPPORTED;
     const long ntask = ((long)b * N * N + 31) / 32;
     const int grid = grid_for(ntask, 4, 512);
     if (arith == PRD_ARITH_SPLIT16 && (dist_dim % 128) == 0) {        // fp16 x 2 split operands
-        const size_t lds2 = (size_t)4 * P * dist_dim + (size_t)dist_dim * 4;
-        return PRD_FOR_P(P, PP, prd_launch<pair_init_h2_kernel<PP>>(dim3(grid), dim3(WG), lds2, stream, pair, static_pair, z, mask, centers, w_dist,
+        return PRD_FOR_P(P, PP, prd_launch<pair_init_h2_kernel<PP>>(dim3(grid), dim3(WG), pair_init_h2_lds_bytes(P, dist_dim), stream, pair, static_pair, z, mask, centers, w_dist,
                                                                     ebeta, b, N, dist_dim));
     }
     return PRD_FOR_P(P, PP, prd_launch<pair_init_kernel<PP>>(dim3(grid), dim3(WG), lds, stream, pair, static_pair, z, mask, centers, w_dist, ebeta,
@@ -1541,8 +1562,7 @@ extern "C" int prd_pair_bias2(float* bias_a, const float* pair, const float* gam
 extern "C" int prd_pair_head_supported(int P, int dist_dim, int C, int arith) {
     if (arith < 0 || (arith & 0xff) != PRD_ARITH_SPLIT16 || (P != 32 && P != 64)) return 0;
     if (dist_dim <= 0 || (dist_dim % 128) || C <= 0 || (C % 128)) return 0;
-    const size_t lds = (size_t)4 * P * dist_dim + (size_t)4 * P * C + ((size_t)dist_dim + P + 16 * P + 4 * P) * 4;
-    return lds <= 160 * 1024 ? 1 : 0;
+    return pair_head_lds_bytes(P, dist_dim, C) <= PRD_LDS_MAX ? 1 : 0;
 }
 
 extern "C" int prd_pair_head(float* pair, const float* static_pair, const float* z, const float* mask, const float* centers,
@@ -1557,7 +1577,7 @@ extern "C" int prd_pair_head(float* pair, const float* static_pair, const float*
     PRD_CHECK_P(P);
     if (!prd_pair_head_supported(P, dist_dim, C, arith)) return PRD_ERR_UNSUPPORTED;
     constexpr int NWH = 8;
-    const size_t lds = (size_t)4 * P * dist_dim + (size_t)4 * P * C + ((size_t)dist_dim + P + 16 * P + 4 * P) * 4;
+    const size_t lds = pair_head_lds_bytes(P, dist_dim, C);
     const long ntask = (long)b * N * prd_ceil_div(N, 32);
     const int grid = grid_for(ntask, NWH, 256);
     return PRD_FOR_P(P, PP, prd_launch<pair_head_h2_kernel<PP, NWH>>(dim3(grid), dim3(NWH * 64), lds, stream, pair, static_pair, z, mask, centers,
@@ -1571,13 +1591,12 @@ extern "C" int prd_opm_pair(float* out, const float* pair, const float* ab, cons
     if (!out || !pair || !ab || !mask || !w_out || !b_out || b <= 0 || N <= 0) return PRD_ERR_ARG;
     PRD_CHECK_P(P);
     if (C <= 0 || (C & 7)) return PRD_ERR_UNSUPPORTED;
-    const size_t lds = ((size_t)P * (C + 4) + P) * sizeof(float);
-    if (lds > 160 * 1024) return PRD_ERR_UNSUPPORTED;
+    const size_t lds = opm_pair_lds_bytes(P, C);
+    if (lds > PRD_LDS_MAX) return PRD_ERR_UNSUPPORTED;
     const long ntask = (long)b * N * prd_ceil_div(N, 32);
     const int grid = grid_for(ntask, 4, 1024);
     if (arith == PRD_ARITH_SPLIT16 && (C % 128) == 0) {               // fp16 x 2 split operands
-        const size_t lds2 = (size_t)4 * P * C + (size_t)P * 4;
-        return PRD_FOR_P(P, PP, prd_launch<opm_pair_h2_kernel<PP>>(dim3(grid), dim3(WG), lds2, stream, out, pair, ab, mask, w_out, b_out, b, N, C,
+        return PRD_FOR_P(P, PP, prd_launch<opm_pair_h2_kernel<PP>>(dim3(grid), dim3(WG), opm_pair_h2_lds_bytes(P, C), stream, out, pair, ab, mask, w_out, b_out, b, N, C,
                                                                    flags));
     }
     return PRD_FOR_P(P, PP, prd_launch<opm_pair_kernel<PP>>(dim3(grid), dim3(WG), lds, stream, out, pair, ab, mask, w_out, b_out, b, N, C, flags));
@@ -1600,6 +1619,11 @@ namespace {
 //     while row i is reduced;
 //   * the eight partial accumulators meet in LDS; wave g then finishes ROWS 4g .. 4g+3 of the tile, 16 lanes per row, so that the
 //     pair rows are read and written as whole 256-byte rows (both the (i, j) rows and the mirrored (j, i) rows).
+// LDS bytes: two partial buffers [2][8 waves][P / 8 groups][64 lanes] of 16 bytes; the staging tiles [8 waves][32 rows][S / 2 + 16 bytes] alias them
+size_t outer_linear_ks_lds_bytes(int P, int S) {
+    const size_t part = (size_t)2 * 8 * (P / 32 * 4) * 64 * 16, stage = (size_t)8 * 32 * ((S / 8) * 4 + 16);
+    return part > stage ? part : stage;
+}
 template <int P, int KS>          // KS = K steps (16 channels each) per wave: S = 128 KS
 __global__ __launch_bounds__(512) void outer_linear_ks_kernel(float* out, const float* pair, const float* __restrict__ x,
                                                               const float* __restrict__ u, const float* __restrict__ w,
@@ -1806,32 +1830,25 @@ extern "C" int prd_outer_linear(float* out, const float* pair, const float* x, c
     if (ldu < P || (ldu & 3)) return PRD_ERR_ALIGN;           // u rows are read in 16-byte pieces
     PRD_CHECK_P(P);
     if (S <= 0 || (S & 7)) return PRD_ERR_UNSUPPORTED;
-    const long ntask = (long)b * N * prd_ceil_div(N, 32);
-    const size_t lds = ((size_t)P * (S + 4) + P) * sizeof(float);
+    const int nvb = prd_ceil_div(N, 32);
+    const long ntask = (long)b * N * nvb, nsym = (long)b * (nvb * (nvb + 1) / 2) * 32;      // nsym: the symmetric half, (i, j-block >= i-block) tasks
+    const size_t lds = outer_linear_res_lds_bytes(P, S);
     const bool ol_v1 = PRD_TGET_OL_GEN2(tune);          // A/B switch: the round-2 kernel
     if (arith == PRD_ARITH_SPLIT16 && !ol_v1 && (S == 128 || S == 256 || S == 512) && (long)b * N * N < (1L << 30)) {
         // K split over the waves of a workgroup, W1 slices in registers (outer_linear_ks_kernel)
-        const int nvb = prd_ceil_div(N, 32);
-        const long ntile = (long)b * (nvb * (nvb + 1) / 2) * 4;       // (block pair, 8 rows i) tasks
+        const long ntile = nsym / 8;                                  // (block pair, 8 rows i) tasks
         const int grid = (int)(ntile < 256 ? ntile : 256);
-        const size_t ldsp = (size_t)2 * 8 * (P / 32 * 4) * 64 * 16, ldss = (size_t)8 * 32 * ((S / 8) * 4 + 16);
-        const size_t ldsk = ldsp > ldss ? ldsp : ldss;             // two partial buffers; the staging tiles alias them
         return PRD_FOR_P(P, PP, PRD_FOR_3(S, SS, 512, 256, 128,           // a wave's slice of K = S: 4, 2 or 1 x 16 values per lane
-            prd_launch<outer_linear_ks_kernel<PP, SS / 128>>(dim3(grid), dim3(512), ldsk, stream, out, pair, x, u, w, bias, b, N, residual, ldu)));
+            prd_launch<outer_linear_ks_kernel<PP, SS / 128>>(dim3(grid), dim3(512), outer_linear_ks_lds_bytes(P, S), stream, out, pair, x, u, w, bias, b, N, residual, ldu)));
     }
-    if (arith == PRD_ARITH_SPLIT16 && (S % 128) == 0 && (size_t)4 * P * S + 4 * P <= 160 * 1024) {   // fp16 x 2 split operands
+    if (arith == PRD_ARITH_SPLIT16 && (S % 128) == 0 && outer_linear_res_h2_lds_bytes(P, S) <= PRD_LDS_MAX) {   // fp16 x 2 split operands
         constexpr int NWL = 8;
-        const int nvb = prd_ceil_div(N, 32);
-        const long nsym = (long)b * (nvb * (nvb + 1) / 2) * 32;
         const int grid = grid_for(nsym, 4, 256);
-        const size_t lds2 = (size_t)4 * P * S + 4 * P;
-        return PRD_FOR_P(P, PP, prd_launch<outer_linear_res_h2_kernel<PP, NWL>>(dim3(grid), dim3(NWL * 64), lds2, stream, out, pair, x, u, w, bias,
+        return PRD_FOR_P(P, PP, prd_launch<outer_linear_res_h2_kernel<PP, NWL>>(dim3(grid), dim3(NWL * 64), outer_linear_res_h2_lds_bytes(P, S), stream, out, pair, x, u, w, bias,
                                                                                 b, N, S, residual, ldu));
     }
-    if (lds <= 150 * 1024 && (S % 64) == 0) {   // W1 resident in LDS: persistent 8-wave workgroups, queue-fed
+    if (lds <= OUTER_LINEAR_RES_LDS_MAX && (S % 64) == 0) {   // W1 resident in LDS: persistent 8-wave workgroups, queue-fed
         constexpr int NWL = 8;
-        const int nvb = prd_ceil_div(N, 32);
-        const long nsym = (long)b * (nvb * (nvb + 1) / 2) * 32;      // symmetric half: (i, j-block >= i-block) tasks
         const int grid = grid_for(nsym, 4, 256);
         // fewer tasks than resident waves (symmetric half): the static assignment beats the queue (56 vs 74 us at N = 320)
         int* oq = (nsym > (long)grid * NWL) ? queue : nullptr;
@@ -1848,8 +1865,8 @@ int launch_pair_tail_h2(float* out, const float* pair, const float* og, const fl
                         const float* b1, const float* w2, const float* b2, const float* bias_w, const float* bias_b,
                         float* bias_out, int H, long rows, long nn, int residual, hipStream_t stream) {
     constexpr int NWH = 12;
-    const size_t lds = ((size_t)2 * 4 * P * (P / 8) + (size_t)2 * P * (4 * P / 8) + (size_t)2 * P * 8) * 16 + (size_t)(4 * P + 2 * P + 8 * P) * 4;
-    if (lds > 160 * 1024) return PRD_ERR_UNSUPPORTED;
+    const size_t lds = pair_tail_h2_lds_bytes(P);
+    if (lds > PRD_LDS_MAX) return PRD_ERR_UNSUPPORTED;
     const int grid = grid_for((rows + 31) / 32, 4, 256);
     return prd_launch<pair_tail_h2_kernel<P, NWH>>(dim3(grid), dim3(NWH * 64), lds, stream, out, pair, og, wo, bo, w1, b1, w2, b2, bias_w, bias_b,
                                                    bias_out, H, rows, nn, residual);
@@ -1861,14 +1878,12 @@ extern "C" int prd_pair_transition(float* out, const float* pair, const float* w
     PRD_SPLIT_ARITH(arith);
     if (!out || !pair || !w1 || !b1 || !w2 || !b2 || b <= 0 || N <= 0) return PRD_ERR_ARG;
     PRD_CHECK_P(P);
-    if (arith == PRD_ARITH_SPLIT16) {             // split 16-bit operands (fp16 x 2), see pair_tail_h2_kernel
-        const long rows_ = (long)b * N * N;
-        return P == 64 ? launch_pair_tail_h2<64>(out, pair, nullptr, nullptr, nullptr, w1, b1, w2, b2, nullptr, nullptr, nullptr, 0, rows_, (long)N * N, residual, stream)
-                       : launch_pair_tail_h2<32>(out, pair, nullptr, nullptr, nullptr, w1, b1, w2, b2, nullptr, nullptr, nullptr, 0, rows_, (long)N * N, residual, stream);
-    }
-    constexpr int NWT = 12;                    // one persistent 12-wave workgroup per CU (weights: 137 KB of LDS at P=64)
     const long rows = (long)b * N * N;
-    const size_t lds = ((size_t)4 * P * (P + 4) + (size_t)P * (4 * P + 4) + 5 * P) * sizeof(float);
+    if (arith == PRD_ARITH_SPLIT16)               // split 16-bit operands (fp16 x 2), see pair_tail_h2_kernel
+        return PRD_FOR_P(P, PP, launch_pair_tail_h2<PP>(out, pair, nullptr, nullptr, nullptr, w1, b1, w2, b2, nullptr, nullptr, nullptr, 0, rows,
+                                                        (long)N * N, residual, stream));
+    constexpr int NWT = 12;                    // one persistent 12-wave workgroup per CU (weights: 137 KB of LDS at P=64)
+    const size_t lds = pair_transition_lds_bytes(P);
     const int grid = grid_for((rows + 31) / 32, 4, 256);
     return PRD_FOR_P(P, PP, prd_launch<pair_transition_kernel<PP, NWT>>(dim3(grid), dim3(NWT * 64), lds, stream, queue, out, pair, w1, b1, w2, b2,
                                                                         rows, residual));
@@ -1881,15 +1896,12 @@ extern "C" int prd_block_tail(float* pair, const float* og, const float* wo, con
     if (!pair || !og || !wo || !bo || !w1 || !b1 || !w2 || !b2 || b <= 0 || N <= 0) return PRD_ERR_ARG;
     if (bias_out && (!bias_w || H <= 0 || H > 8)) return PRD_ERR_ARG;
     PRD_CHECK_P(P);
-    if (arith == PRD_ARITH_SPLIT16) {             // split 16-bit operands (fp16 x 2), see pair_tail_h2_kernel
-        const long rows_ = (long)b * N * N;
-        return P == 64 ? launch_pair_tail_h2<64>(pair, pair, og, wo, bo, w1, b1, w2, b2, bias_w, bias_b, bias_out, H, rows_, (long)N * N, 1, stream)
-                       : launch_pair_tail_h2<32>(pair, pair, og, wo, bo, w1, b1, w2, b2, bias_w, bias_b, bias_out, H, rows_, (long)N * N, 1, stream);
-    }
-    constexpr int NWT = 8;
     const long rows = (long)b * N * N;
-    const size_t lds = ((size_t)4 * P * (P + 4) + (size_t)P * (4 * P + 4) + (size_t)P * 68 + 6 * P + 8 * P) * sizeof(float);
-    if (lds > 160 * 1024) return PRD_ERR_UNSUPPORTED;
+    if (arith == PRD_ARITH_SPLIT16)               // split 16-bit operands (fp16 x 2), see pair_tail_h2_kernel
+        return PRD_FOR_P(P, PP, launch_pair_tail_h2<PP>(pair, pair, og, wo, bo, w1, b1, w2, b2, bias_w, bias_b, bias_out, H, rows, (long)N * N, 1, stream));
+    constexpr int NWT = 8;
+    const size_t lds = block_tail_lds_bytes(P);
+    if (lds > PRD_LDS_MAX) return PRD_ERR_UNSUPPORTED;
     const int grid = grid_for((rows + 31) / 32, 4, 256);
     // measured at N = 320: static round-robin 87 us, queue 93 us (8-wave workgroups, < 2 tasks per wave); queue beyond that
     int* bq = ((rows + 31) / 32 > (long)2 * grid * NWT) ? queue : nullptr;

@@ -380,7 +380,7 @@ int spa_key_parts(int b, int N, int H) {
 extern "C" int prd_spa_attn_core_supported(int N, int c, int arith) {
     if (arith < 0 || (arith & 0xff) != PRD_ARITH_SPLIT16) return 0;
     if (N <= 0 || c < 64 || c > 512 || (c % 64) != 0) return 0;
-    return spa_lds_bytes(c) <= 160 * 1024 ? 1 : 0;
+    return spa_lds_bytes(c) <= PRD_LDS_MAX ? 1 : 0;
 }
 
 // bytes of workspace prd_spa_attn_core needs (0: one key part, no merge launch)

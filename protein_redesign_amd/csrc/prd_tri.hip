@@ -22,6 +22,7 @@
 #include "../../include/prd_hip.h"
 #include <atomic>
 #include <cstdlib>
+#include <cstring>
 #include "prd_launch.h"
 
 #ifdef PRD_TIMING     // diagnostic builds only (tools/ta_timing.py, tools/phase_timing.py): in-kernel cycle stamps
@@ -143,6 +144,8 @@ PRD_DEV void proj_compute(const ProjTask& t, float (&x)[P / 2], float mu, float 
     pt.mark(4);                                     // 4: epilogue + store issue
 }
 
+// LDS bytes: W_proj | W_gate, [2 P][P + 4] floats each (b3, split-16: fp16 hi | lo planes of [2 P][P], no padding) | b_proj, b_gate [2 P] each
+size_t tri_mul_proj_lds_bytes(int P, bool b3) { return (2 * (b3 ? (size_t)2 * P * P : (size_t)2 * P * (P + 4)) + 4 * P) * sizeof(float); }
 template <int P, int NW, bool B3>
 __global__ __launch_bounds__(NW * 64) void tri_mul_proj_kernel(int* queue, float* __restrict__ AB, const float* __restrict__ pair,
                                                           const float* __restrict__ mask,
@@ -206,6 +209,8 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_proj_kernel(int* queue, float
 // those tasks the contraction output must be contiguous in v, which the outgoing contraction provides by swapping its
 // operands (O^T = B A^T).  Per task: Ot[:, u, v-block] and pair[v-block, u] -> gate, projection of LN(O), residual ->
 // pair[v-block, u] (written back) -> LN -> a | b projections and gates of the incoming module, masked -> AB[:, u, v-block].
+// LDS bytes: W_out | W_ogate planes [P][P] each | W_proj | W_gate planes [2 P][P] each | six bias vectors [P]
+size_t tri_mul_out_proj_lds_bytes(int P) { return ((size_t)2 * P * P + (size_t)2 * 2 * P * P + 6 * P) * sizeof(float); }
 template <int P, int NW>
 __global__ __launch_bounds__(NW * 64) void tri_mul_out_proj_kernel(float* pair, const float* __restrict__ Ot, const float* __restrict__ mask,
                                                                    const float* __restrict__ wo, const float* __restrict__ bo,
@@ -442,6 +447,8 @@ constexpr int TMS_T = 160, TMS_PLANE = TMS_T * 64, TMS_OPER = 2 * TMS_PLANE;    
 // PRD_TUNE_TMS_NW in the upper bits of `arith`
 // ASC (the stacked gradient contraction of the backward, prd_tri_mul_contract_scaled): the first operand is a GRADIENT, not O(1);
 // it is split x split_scale(a_amax[complex]) and the result taken back by the inverse power of two (prd_common.h: split_scale)
+// LDS bytes: four operand buffers of TMS_OPER (hi | lo planes of a 160-row tile)
+size_t tri_mul_contract_split_lds_bytes() { return (size_t)4 * TMS_OPER; }
 template <int NWV, int DEPTH = 2, bool ASC = false>  // 8 or 16 waves: 25 sub-tiles dealt round-robin, 4 or 2 accumulators per wave; DEPTH: chunks of operands in flight
 __global__ __launch_bounds__(NWV * 64) void tri_mul_contract_split_kernel(float* __restrict__ O, const float* __restrict__ AB,
                                                                           int N, int ldn, int P, int nbatch, int tiles, int swap,
@@ -1120,6 +1127,8 @@ __global__ __launch_bounds__(256) void single_attn_core_kernel(float* __restrict
 //            operand layouts of the 16x16x4 MFMAs.  The next row's block is already in registers (prefetch).
 //   phase 2: the ceil(N/16) query tiles are dealt round-robin to the waves (SIMD-balanced: waves w and w+4
 //            share a SIMD), two tiles at a time through ta_keyloop.
+// LDS bytes: weights [64][P + 4] | K, V, Q tiles [npad][KP] | gate [16][npad + 4] | override [npad] | bias [32]
+size_t tri_attn_core_lds_bytes(int P, int npad) { return ((size_t)64 * (P + 4) + (size_t)3 * npad * KP + 16 * (npad + 4) + npad + 32) * sizeof(float); }
 template <int P, int NW, bool PREFETCH, bool B3>
 __global__ __launch_bounds__(NW * 64) void tri_attn_core_kernel(
     float* __restrict__ og, const float* __restrict__ pair, const float* __restrict__ mask,
@@ -1316,6 +1325,11 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_kernel(
 // ---- FIRST-GENERATION split-16 attention cores (round 2): compiled only with -DPRD_AB (python -m protein_redesign_amd.build --ab ->
 // libprd_hip_ab.so, for A/B measurements and their own parity tests).  The shipped library serves the split-16 arithmetic with the
 // second generation (csrc/prd_tri2.hip) and, where that does not apply, with the fp32-MFMA kernels of this file. ----
+// LDS bytes of the two first-generation split-16 cores below (outside the #ifdef: the dispatch plan prices them in either build).
+// short rows: weights 64 P x 4 B | K / Q planes 6 x 32 B, gate [KP] floats and override per position | V hi / lo 2 x 16 x (npad + 8) fp16 | bias
+size_t tri_attn_core_split_lds_bytes(int P, int npad) { return (size_t)64 * P * 4 + (size_t)npad * (192 + KP * 4 + 4) + (size_t)64 * (npad + 8) + 128; }
+// long rows: weights | K hi | lo (64 B) and override per position | V hi / lo | bias | 8 waves x 4 KB of scratch
+size_t tri_attn_core_split_long_lds_bytes(int P, int npad) { return (size_t)64 * P * 4 + (size_t)npad * 68 + (size_t)64 * (npad + 8) + 128 + 8 * 4096; }
 #ifdef PRD_AB
 // ---------------------------------------------------------------------------------------------------------------------
 // Triangle attention core on the 16-bit matrix pipes (gemm mode 1), fp32-accurate by operand splitting:
@@ -1931,6 +1945,9 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_long_kernel(
 
 // Long-row variant (K/V of the row fill the LDS, no room for Q / gate tiles): queries are re-projected per
 // 32-query block in phase 2 and reach the MFMA operand layout through wave shuffles instead of LDS.
+// LDS bytes of the fp32 long-row core and of its key-chunked form (nkeys = the keys a launch holds, a multiple of 64):
+// weights [64][P + 4] | K tiles [nkeys][KP] | V [16][nkeys + 4] | override [nkeys]
+size_t tri_attn_core_long_lds_bytes(int P, int nkeys) { return ((size_t)64 * (P + 4) + (size_t)nkeys * KP + 16 * (nkeys + 4) + nkeys) * sizeof(float); }
 template <int P, int NW>
 __global__ __launch_bounds__(NW * 64) void tri_attn_core_long_kernel(
     float* __restrict__ og, const float* __restrict__ pair, const float* __restrict__ mask,
@@ -2211,23 +2228,30 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_out_kernel(int* queue, float
 
 }  // namespace
 
-// the split contraction by the A/B switches of the caller (waves per workgroup; chunks of operands in flight)
-static int launch_contract_split(int tune, int grid, size_t lds3, hipStream_t stream, float* O, const float* AB, int N, int ldn, int P, int nbatch,
-                                 int tiles, int swap, const unsigned* a_amax = nullptr) {
-    if (a_amax)         // the scaled first operand of the backward: one form (8 waves)
-        return prd_launch<tri_mul_contract_split_kernel<8, 2, true>>(dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, a_amax);
+// ---- the stages of the triangle multiplication; each computes its own grid, waves and LDS bytes.  (The projection and output stages
+// stand in front of prd_tri_mul: the kernels keep their order in the code object.)  Contraction: O[b][P][N][ldn] from AB, stored
+// transposed with `swap`; split-16: by the caller's A/B switches (waves, chunks in flight); a_amax: the scaled operand of the backward
+static int launch_tri_mul_contract(int tune, bool b3, hipStream_t stream, float* O, const float* AB, int b, int N, int P, int swap,
+                                   const unsigned* a_amax = nullptr) {
+    const int ldn = prd_round_up(N, 32);
+    if (!b3) {
+        const int tiles = prd_ceil_div(N, 64), vblocks = b * P * tiles * tiles;
+        return prd_launch<tri_mul_contract_kernel>(dim3(vblocks < 1024 ? vblocks : 1024), dim3(256), 0, stream, O, AB, N, ldn, P, b, tiles);
+    }
+    const int tiles = prd_ceil_div(N, TMS_T), vblocks = b * P * tiles * tiles;
+    const dim3 grid(vblocks < 256 ? vblocks : 256);
+    const size_t lds = tri_mul_contract_split_lds_bytes();
+    if (a_amax) return prd_launch<tri_mul_contract_split_kernel<8, 2, true>>(grid, dim3(512), lds, stream, O, AB, N, ldn, P, b, tiles, swap, a_amax);
     const int nw = PRD_TGET_TMS_NW(tune);
 #ifdef PRD_AB       // (libprd_hip_ab.so) three chunks in flight / 16 waves: measured in rounds 3 and 5, not faster
     if (nw == 8 && PRD_TGET_TMS_D3(tune))
-        return prd_launch<tri_mul_contract_split_kernel<8, 3>>(dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
-    if (nw == 16)
-        return prd_launch<tri_mul_contract_split_kernel<16>>(dim3(grid), dim3(1024), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
+        return prd_launch<tri_mul_contract_split_kernel<8, 3>>(grid, dim3(512), lds, stream, O, AB, N, ldn, P, b, tiles, swap, nullptr);
+    if (nw == 16) return prd_launch<tri_mul_contract_split_kernel<16>>(grid, dim3(1024), lds, stream, O, AB, N, ldn, P, b, tiles, swap, nullptr);
 #endif
     if (nw == 12)       // (kept in the shipped library: the second arm of the direct parity test -- same results bit for bit)
-        return prd_launch<tri_mul_contract_split_kernel<12>>(dim3(grid), dim3(768), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
-    return prd_launch<tri_mul_contract_split_kernel<8>>(dim3(grid), dim3(512), lds3, stream, O, AB, N, ldn, P, nbatch, tiles, swap, nullptr);
+        return prd_launch<tri_mul_contract_split_kernel<12>>(grid, dim3(768), lds, stream, O, AB, N, ldn, P, b, tiles, swap, nullptr);
+    return prd_launch<tri_mul_contract_split_kernel<8>>(grid, dim3(512), lds, stream, O, AB, N, ldn, P, b, tiles, swap, nullptr);
 }
-
 
 #ifdef PRD_AB
 constexpr bool PRD_FIRST_GEN = true;
@@ -2235,21 +2259,17 @@ constexpr bool PRD_FIRST_GEN = true;
 constexpr bool PRD_FIRST_GEN = false;       // first-generation split-16 cores compiled out: see the PRD_AB note above them
 #endif
 namespace {
-// LDS bytes of the triangle-attention core for rows of N positions; long_row: the re-projecting variant is needed
-size_t tri_attn_lds(int N, int P, bool b3, bool* long_row) {
+// which first-generation core serves rows of N positions (b3: split-16 operands), and its LDS bytes.  SHORT: K, V, Q and gate of a row
+// resident; LONG_*: Q / gate tiles do not fit next to the row's K / V and are re-projected per query block; TOO_LARGE: not even K / V fit
+enum class TaKind { SHORT, LONG_FP32, LONG_SPLIT, TOO_LARGE };
+struct TaPlan { TaKind kind; size_t lds; };
+TaPlan tri_attn_plan(int N, int P, bool b3) {
     const int npad = prd_round_up(N, 64);
-    const size_t wsz = b3 ? (size_t)3 * 64 * (2 * (P / 16) + 1) * 4 : (size_t)64 * (P + 4);
-    size_t lds = (wsz + (size_t)3 * npad * KP + 16 * (npad + 4) + npad + 32) * sizeof(float);
-    // split-operand kernel (gemm mode 1): K / Q planes 6 x 32 B, V hi / lo 2 x 16 x (npad + 8) fp16, gate, override, bias
-    if (b3) lds = (size_t)64 * P * 4 + (size_t)npad * (192 + KP * 4 + 4) + (size_t)64 * (npad + 8) + 128;
-    *long_row = lds > 160 * 1024;              // Q / gate tiles do not fit next to the row's K / V
-    if (*long_row) {
-        // split-operand long rows: weights + K hi|lo (64 B) + V hi|lo + override per position + bias + 8 waves x 4 KB of scratch
-        const size_t lds_sl = (size_t)64 * P * 4 + (size_t)npad * 68 + (size_t)64 * (npad + 8) + 128 + 8 * 4096;
-        if (b3 && lds_sl <= 160 * 1024) return lds_sl;
-        lds = ((size_t)64 * (P + 4) + (size_t)npad * KP + 16 * (npad + 4) + npad) * sizeof(float);
-    }
-    return lds;
+    const size_t lds_short = b3 ? tri_attn_core_split_lds_bytes(P, npad) : tri_attn_core_lds_bytes(P, npad);
+    if (lds_short <= PRD_LDS_MAX) return {TaKind::SHORT, lds_short};
+    if (b3 && tri_attn_core_split_long_lds_bytes(P, npad) <= PRD_LDS_MAX) return {TaKind::LONG_SPLIT, tri_attn_core_split_long_lds_bytes(P, npad)};
+    const size_t lds_long = tri_attn_core_long_lds_bytes(P, npad);
+    return {lds_long <= PRD_LDS_MAX ? TaKind::LONG_FP32 : TaKind::TOO_LARGE, lds_long};
 }
 }  // namespace
 
@@ -2257,23 +2277,18 @@ extern "C" int prd_tri_attn_variant(int N, int P, int arith) {
     PRD_SPLIT_ARITH(arith);
     if (N <= 0) return PRD_ERR_ARG;
     if (P != 32 && P != 64) return PRD_ERR_UNSUPPORTED;
-    bool long_row;
     const bool split = arith == PRD_ARITH_SPLIT16;
     const bool v2 = split && PRD_TGET_TA_VARIANT(tune) == 0 && prd_tri_attn_v2_supported(N, P, tune);   // what prd_tri_attn_core dispatches to first
     const bool b3 = split && (PRD_FIRST_GEN || v2);   // without the first generation, rows the second one does not serve run the fp32 kernels
-    const size_t lds = tri_attn_lds(N, P, b3, &long_row);
-    if (lds > 160 * 1024)                      // the round-3 core keeps K / V as fp16 planes: rows up to 1024; beyond: key-chunked
-        return v2 ? 2 : 3;
-    if (!long_row) return 0;
-    if (v2) return 2;                          // long rows on the round-3 core (also where the fp32 long-row kernel would fit)
-    const int npad = prd_round_up(N, 64);
-    return (b3 && lds == (size_t)64 * P * 4 + (size_t)npad * 68 + (size_t)64 * (npad + 8) + 128 + 8 * 4096) ? 2 : 1;
+    switch (tri_attn_plan(N, P, b3).kind) {
+    case TaKind::SHORT: return 0;
+    case TaKind::TOO_LARGE: return v2 ? 2 : 3;        // the round-3 core keeps K / V as fp16 planes: rows up to 1024; beyond: key-chunked
+    case TaKind::LONG_SPLIT: return 2;
+    default: return v2 ? 2 : 1;                       // long rows on the round-3 core (also where the fp32 long-row kernel would fit)
+    }
 }
 
-namespace {
-constexpr int TA_CHUNK_MAX = 960;              // keys per chunk: (64 (P+4) + 148 npad + 64) floats... <= 160 KB for P = 64
-int ta_chunks(int N) { return prd_ceil_div(N, TA_CHUNK_MAX); }
-}  // namespace
+constexpr int TA_CHUNK_MAX = 960;              // keys per chunk: tri_attn_core_long_lds_bytes(64, 960) <= 160 KB
 
 extern "C" size_t prd_tri_attn_stats_bytes(int b, int N, int P, int H, int arith) {
     if (b <= 0 || N <= 0 || H <= 0) return 0;
@@ -2284,12 +2299,12 @@ extern "C" int prd_tri_attn_core_chunked(float* og, const float* pair, const flo
                                          const float* wv, const float* wg, const float* bg, int ending,
                                          int b, int N, int P, int H, int c, float* stats, size_t stats_bytes, hipStream_t stream) {
     if (!og || !pair || !mask || !wq || !wk || !wv || !wg || !bg || !stats || b <= 0 || N <= 0) return PRD_ERR_ARG;
-    if ((P != 32 && P != 64) || c != 16 || H * c != 64) return PRD_ERR_UNSUPPORTED;
+    if ((P != 32 && P != 64) || !prd_heads_4x16(H, c)) return PRD_ERR_UNSUPPORTED;
     if (stats_bytes < (size_t)b * N * N * H * 2 * sizeof(float)) return PRD_ERR_WORKSPACE;
-    const int nchunk = ta_chunks(N);
+    const int nchunk = prd_ceil_div(N, TA_CHUNK_MAX);
     const int per = prd_round_up(prd_ceil_div(N, nchunk), 64);         // keys per chunk (the last one may be shorter)
-    const size_t lds = ((size_t)64 * (P + 4) + (size_t)per * KP + 16 * (per + 4) + per) * sizeof(float);
-    if (lds > 160 * 1024) return PRD_ERR_UNSUPPORTED;
+    const size_t lds = tri_attn_core_long_lds_bytes(P, per);
+    if (lds > PRD_LDS_MAX) return PRD_ERR_UNSUPPORTED;
     const int grid = (int)(prd_rows_per_head((long)b * N, 256 / H) * H);
     for (int ck = 0; ck < nchunk; ++ck) {
         const int key0 = ck * per;
@@ -2305,10 +2320,35 @@ extern "C" size_t prd_workspace_bytes(const char* op, int b, int N, int S, int P
     (void)S;
     if (!op || b <= 0 || N <= 0) return 0;
     const size_t ldn = (size_t)prd_round_up(N, 32);
-    if (op[0] == 't' && op[4] == 'm') return (size_t)3 * b * P * N * ldn * sizeof(float);   // "tri_mul": operands a | b + output
-    if (op[0] == 't' && op[4] == 'a')        // "tri_attn": og, and for key-chunked rows the softmax statistics (either arithmetic)
+    if (!strcmp(op, "tri_mul")) return (size_t)3 * b * P * N * ldn * sizeof(float);         // operands a | b + output
+    if (!strcmp(op, "tri_attn"))             // og, and for key-chunked rows the softmax statistics (either arithmetic)
         return (size_t)b * N * N * 64 * sizeof(float) + prd_tri_attn_stats_bytes(b, N, P, 4, PRD_ARITH_FP32);
     return 0;
+}
+
+// projection stage: a | b of the pair rows -> AB [b][2P][N][ldn].  Split-16: 12 waves (the split operands need the registers; 16: the A/B
+// switch PRD_TUNE_TMP_NW16, pair_dim 64 only); fp32: one persistent 16-wave workgroup per CU
+static int launch_tri_mul_proj(int tune, bool b3, hipStream_t stream, int* queue, float* AB, const float* pair, const float* mask, const float* w_proj,
+                               const float* b_proj, const float* w_gate, const float* b_gate, int b, int N, int P, int incoming) {
+    const int ldn = prd_round_up(N, 32);
+    const long ntask = ((long)b * N * (ldn / 32) + 7) / 8 * 8 * (2 * P / 32);     // (row block, output block) tasks
+    const int grid = grid_for(ntask, 4, 256);
+    const bool nw16 = b3 && P == 64 && PRD_TGET_TMP_NW16(tune);
+    return PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3, BB, PRD_FOR_BOOL(nw16, NW16, [&] {
+        constexpr int NWV = !BB ? 16 : (NW16 && PP == 64) ? 16 : 12;
+        return prd_launch<tri_mul_proj_kernel<PP, NWV, BB>>(dim3(grid), dim3(NWV * 64), tri_mul_proj_lds_bytes(P, b3), stream, queue, AB, pair, mask,
+                                                            w_proj, b_proj, w_gate, b_gate, b, N, ldn, incoming);
+    }())));
+}
+
+// output stage: out = (residual ? pair : 0) + gated output projection of LN(O); 8 waves
+static int launch_tri_mul_out(bool b3, hipStream_t stream, int* queue, float* out, const float* pair, const float* O, const float* w_out,
+                              const float* b_out, const float* w_ogate, const float* b_ogate, int b, int N, int P, int residual) {
+    constexpr int NWO = 8;
+    const int grid = grid_for((long)b * N * prd_ceil_div(N, 32), 4, 256);
+    return PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3, BB,
+        prd_launch<tri_mul_out_kernel<PP, NWO, BB>>(dim3(grid), dim3(NWO * 64), 0, stream, queue, out, pair, O, w_out, b_out, w_ogate, b_ogate, b, N,
+                                                    prd_round_up(N, 32), residual)));
 }
 
 extern "C" int prd_tri_mul(float* out, const float* pair, const float* mask, const float* w_proj, const float* b_proj,
@@ -2323,59 +2363,17 @@ extern "C" int prd_tri_mul(float* out, const float* pair, const float* mask, con
     const int ldn = prd_round_up(N, 32);
     float* AB = ws;                                   // [b][2P][N][ldn]
     float* O = ws + (size_t)2 * b * P * N * ldn;      // [b][P][N][ldn]
-    const bool b3m = arith == PRD_ARITH_SPLIT16;
-    {
-        constexpr int NWP = 16;                      // one persistent 16-wave workgroup per CU (4 waves / SIMD)
-        const bool b3 = b3m;                        // bf16 x 3 row GEMM (prd_set_gemm_mode)
-        const size_t wsz = b3 ? (size_t)2 * P * P : (size_t)2 * P * (P + 4);
-        const size_t lds = (2 * wsz + 4 * P) * sizeof(float);
-        const long ntask = ((long)b * N * (ldn / 32) + 7) / 8 * 8 * (2 * P / 32);     // (row block, output block) tasks
-        const int grid = grid_for(ntask, 4, 256);
-        // (the split operands of the bf16 x 3 form need the registers of a 12-wave workgroup; 16: the A/B switch, pair_dim 64 only)
-        const bool nw16 = b3 && P == 64 && PRD_TGET_TMP_NW16(tune);
-        PRD_TRY(PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3, BB, PRD_FOR_BOOL(nw16, NW16, [&] {
-            constexpr int NWV = !BB ? NWP : (NW16 && PP == 64) ? 16 : 12;
-            return prd_launch<tri_mul_proj_kernel<PP, NWV, BB>>(dim3(grid), dim3(NWV * 64), lds, stream, queue, AB, pair, mask,
-                                                                w_proj, b_proj, w_gate, b_gate, b, N, ldn, incoming);
-        }()))));
-    }
-    {
-        const int tiles = prd_ceil_div(N, 64);
-        const int vblocks = b * P * tiles * tiles;
-        if (b3m) {
-            const int tl = prd_ceil_div(N, TMS_T);
-            const int vb3 = b * P * tl * tl;
-            const size_t lds3 = (size_t)4 * TMS_OPER;
-            PRD_TRY(launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 0));
-        }
-        else
-            PRD_TRY(prd_launch<tri_mul_contract_kernel>(dim3(vblocks < 1024 ? vblocks : 1024), dim3(256), 0, stream, O, AB, N, ldn, P, b, tiles));
-    }
-    {
-        constexpr int NWO = 8;
-        const bool b3o = b3m;
-        const long ntask = (long)b * N * prd_ceil_div(N, 32);
-        const int grid = grid_for(ntask, 4, 256);
-        return PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3o, BB,
-            prd_launch<tri_mul_out_kernel<PP, NWO, BB>>(dim3(grid), dim3(NWO * 64), 0, stream, queue, out, pair, O, w_out,
-                                                        b_out, w_ogate, b_ogate, b, N, ldn, residual)));
-    }
+    const bool b3 = arith == PRD_ARITH_SPLIT16;
+    PRD_TRY(launch_tri_mul_proj(tune, b3, stream, queue, AB, pair, mask, w_proj, b_proj, w_gate, b_gate, b, N, P, incoming));
+    PRD_TRY(launch_tri_mul_contract(tune, b3, stream, O, AB, b, N, P, 0));
+    return launch_tri_mul_out(b3, stream, queue, out, pair, O, w_out, b_out, w_ogate, b_ogate, b, N, P, residual);
 }
 
 extern "C" int prd_tri_mul_contract(float* O, const float* AB, int b, int N, int P, int arith, hipStream_t stream) {
     PRD_SPLIT_ARITH(arith);
     if (!O || !AB || b <= 0 || N <= 0) return PRD_ERR_ARG;
     if (P != 32 && P != 64 && P != 128) return PRD_ERR_UNSUPPORTED;     // 2 x 64: the stacked gradient contractions of the backward
-    const int ldn = prd_round_up(N, 32);
-    if (arith == PRD_ARITH_SPLIT16) {
-        const int tl = prd_ceil_div(N, TMS_T);
-        const int vb3 = b * P * tl * tl;
-        const size_t lds3 = (size_t)4 * TMS_OPER;
-        return launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 0);
-    }
-    const int tiles = prd_ceil_div(N, 64);
-    const int vblocks = b * P * tiles * tiles;
-    return prd_launch<tri_mul_contract_kernel>(dim3(vblocks < 1024 ? vblocks : 1024), dim3(256), 0, stream, O, AB, N, ldn, P, b, tiles);
+    return launch_tri_mul_contract(tune, arith == PRD_ARITH_SPLIT16, stream, O, AB, b, N, P, 0);
 }
 
 extern "C" int prd_tri_mul_contract_scaled(float* O, const float* AB, const unsigned* a_amax, int b, int N, int P, int arith, hipStream_t stream) {
@@ -2384,10 +2382,7 @@ extern "C" int prd_tri_mul_contract_scaled(float* O, const float* AB, const unsi
     PRD_SPLIT_ARITH(arith);
     if (!O || !AB || b <= 0 || N <= 0) return PRD_ERR_ARG;
     if (P != 32 && P != 64 && P != 128) return PRD_ERR_UNSUPPORTED;
-    const int ldn = prd_round_up(N, 32);
-    const int tl = prd_ceil_div(N, TMS_T);
-    const int vb3 = b * P * tl * tl;
-    return launch_contract_split(tune, vb3 < 256 ? vb3 : 256, (size_t)4 * TMS_OPER, stream, O, AB, N, ldn, P, b, tl, 0, a_amax);
+    return launch_tri_mul_contract(tune, true, stream, O, AB, b, N, P, 0, a_amax);
 }
 
 extern "C" int prd_tri_mul_chain_supported(int N, int P, int arith) {
@@ -2407,40 +2402,23 @@ extern "C" int prd_tri_mul_chain(float* pair, const float* mask, const float* co
     float* O = ws + (size_t)2 * b * P * N * ldn;      // [b][P][N][ldn]
     const float* const* wa = w_outgoing;              // proj w, b | gate w, b | out w, b | out-gate w, b
     const float* const* wb = w_incoming;
-    const size_t ldsp = ((size_t)2 * 2 * P * P + 4 * P) * sizeof(float);
-    const long ptask = ((long)b * N * (ldn / 32) + 7) / 8 * 8 * (2 * P / 32);
-    const int pgrid = grid_for(ptask, 4, 256);
-    const int tl = prd_ceil_div(N, TMS_T);
-    const int vb3 = b * P * tl * tl;
-    const size_t lds3 = (size_t)4 * TMS_OPER;
-    const long rtask = (long)b * N * (ldn / 32);
-    const int rgrid = grid_for(rtask, 4, 256);
-    const size_t ldsf = ((size_t)2 * P * P + (size_t)2 * 2 * P * P + 6 * P) * sizeof(float);
     // (a failed launch must not let the later stages run over a half-written workspace: every stage is checked)
-    // 1. a | b of the outgoing module: 12 waves; 16: the A/B switch PRD_TUNE_TMP_NW16, pair_dim 64 only
-    const bool nw16 = P == 64 && PRD_TGET_TMP_NW16(tune);
-    PRD_TRY(PRD_FOR_P(P, PP, PRD_FOR_BOOL(nw16, NW16, [&] {
-        constexpr int NWV = (NW16 && PP == 64) ? 16 : 12;
-        return prd_launch<tri_mul_proj_kernel<PP, NWV, true>>(dim3(pgrid), dim3(NWV * 64), ldsp, stream, (int*)nullptr, AB, pair, mask,
-                                                              wa[0], wa[1], wa[2], wa[3], b, N, ldn, 0);
-    }())));
+    // 1. a | b of the outgoing module
+    PRD_TRY(launch_tri_mul_proj(tune, true, stream, nullptr, AB, pair, mask, wa[0], wa[1], wa[2], wa[3], b, N, P, 0));
     // 2. its contraction, transposed: O^T[c][j][i]
-    PRD_TRY(launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 1));
+    PRD_TRY(launch_tri_mul_contract(tune, true, stream, O, AB, b, N, P, 1));
     // 3. output stage of the outgoing module + a | b of the incoming one.  P = 64: 12 waves (168 VGPRs, three per SIMD) cover the
     // task's latency chain better than 8 (36.6 -> 31.7 us at N = 320; the plain output stage below needs 192 VGPRs and stays at 8:
     // 12 waves spill, 19.9 -> 28.7 us)
+    const int rgrid = grid_for((long)b * N * (ldn / 32), 4, 256);
     PRD_TRY(PRD_FOR_P(P, PP, [&] {
         constexpr int NWV = PP == 64 ? 12 : 8;
-        return prd_launch<tri_mul_out_proj_kernel<PP, NWV>>(dim3(rgrid), dim3(NWV * 64), ldsf, stream, pair, O, mask, wa[4], wa[5], wa[6], wa[7],
-                                                            wb[0], wb[1], wb[2], wb[3], AB, b, N, ldn);
+        return prd_launch<tri_mul_out_proj_kernel<PP, NWV>>(dim3(rgrid), dim3(NWV * 64), tri_mul_out_proj_lds_bytes(P), stream, pair, O, mask, wa[4], wa[5],
+                                                            wa[6], wa[7], wb[0], wb[1], wb[2], wb[3], AB, b, N, ldn);
     }()));
-    // 4. contraction of the incoming module
-    PRD_TRY(launch_contract_split(tune, vb3 < 256 ? vb3 : 256, lds3, stream, O, AB, N, ldn, P, b, tl, 0));
-    // 5. its output stage
-    const long ntask = (long)b * N * prd_ceil_div(N, 32);
-    const int grid = grid_for(ntask, 4, 256);
-    return PRD_FOR_P(P, PP, prd_launch<tri_mul_out_kernel<PP, 8, true>>(dim3(grid), dim3(8 * 64), 0, stream, (int*)nullptr, pair, pair, O,
-                                                                        wb[4], wb[5], wb[6], wb[7], b, N, ldn, 1));
+    // 4. contraction of the incoming module, 5. its output stage
+    PRD_TRY(launch_tri_mul_contract(tune, true, stream, O, AB, b, N, P, 0));
+    return launch_tri_mul_out(true, stream, nullptr, pair, pair, O, wb[4], wb[5], wb[6], wb[7], b, N, P, 1);
 }
 
 extern "C" int prd_tri_attn_core(float* og, const float* pair, const float* mask, const float* wq, const float* wk,
@@ -2448,43 +2426,37 @@ extern "C" int prd_tri_attn_core(float* og, const float* pair, const float* mask
                                  int b, int N, int P, int H, int c, int arith, hipStream_t stream) {
     PRD_SPLIT_ARITH(arith);
     if (!og || !pair || !mask || !wq || !wk || !wv || !wg || !bg || b <= 0 || N <= 0) return PRD_ERR_ARG;
-    if ((P != 32 && P != 64) || c != 16 || H * c != 64) return PRD_ERR_UNSUPPORTED;
+    if ((P != 32 && P != 64) || !prd_heads_4x16(H, c)) return PRD_ERR_UNSUPPORTED;
     const int npad = prd_round_up(N, 64);
-    const int nqb = prd_ceil_div(N, 32);
     const bool split = arith == PRD_ARITH_SPLIT16;    // split 16-bit operands
     const int variant = PRD_FIRST_GEN ? PRD_TGET_TA_VARIANT(tune) : 0;    // A/B switch: first-generation kernels (-DPRD_AB builds only)
     // second generation (prd_tri2.hip): short rows, and long rows as far as K / V of a row fit the LDS as fp16 planes
     if (split && variant == 0 && prd_tri_attn_v2_supported(N, P, tune) && (long)b * N * N <= 0x7fffffffL / 2)
         return prd_tri_attn_core_v2(og, pair, mask, wq, wk, wv, wg, bg, ending, b, N, P, H, c, tune, stream);
     const bool b3 = split && PRD_FIRST_GEN;           // otherwise: the fp32-MFMA kernels below (more accurate, slower)
-    bool long_row;
-    const size_t lds = tri_attn_lds(N, P, b3, &long_row);
-    if (lds > 160 * 1024) return PRD_ERR_UNSUPPORTED;
-    const int nw = 8;                                   // 2 waves / SIMD: room for the next-row prefetch registers
+    const TaPlan plan = tri_attn_plan(N, P, b3);
+    if (plan.kind == TaKind::TOO_LARGE) return PRD_ERR_UNSUPPORTED;
     // persistent workgroups (weights staged once per workgroup), one per CU: per head the SMALLEST workgroup
     // count that reaches the minimum number of row rounds, so every workgroup walks the same number of rows
     const int grid = (int)(prd_rows_per_head((long)b * N, 256 / H) * H);
     // the first-generation cores share their arguments (the split core has four more: the fused form's, unused here)
 #define PRD_TA_LAUNCH(NWV, KERNEL, ...) \
-    prd_launch<KERNEL>(dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, wq, wk, wv, wg, bg, b, N, npad, H, ending, ##__VA_ARGS__)
+    prd_launch<KERNEL>(dim3(grid), dim3(NWV * 64), plan.lds, stream, og, pair, mask, wq, wk, wv, wg, bg, b, N, npad, H, ending, ##__VA_ARGS__)
 #define PRD_TA_NOT_FUSED nullptr, nullptr, nullptr, nullptr
-    (void)nqb; (void)nw;
     // 12 waves (3 per SIMD) + next-row prefetch: the ceil(N/16) query tiles dealt in pairs land 5 per SIMD at N = 320
     // (measured: 12 waves + prefetch 142 us, 16 waves without prefetch 149 us, 8 waves + prefetch 146 us)
-    const bool split_long = long_row && b3 &&
-        lds == (size_t)64 * P * 4 + (size_t)npad * 68 + (size_t)64 * (npad + 8) + 128 + 8 * 4096;      // tri_attn_lds chose it
 #ifdef PRD_AB
-    if (split_long) return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(8, (tri_attn_core_split_long_kernel<PP, 8>)));
-    if (!long_row && b3) {
+    if (plan.kind == TaKind::LONG_SPLIT) return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(8, (tri_attn_core_split_long_kernel<PP, 8>)));
+    if (plan.kind == TaKind::SHORT && b3) {
         if (P == 64 && variant == 1) return PRD_TA_LAUNCH(16, (tri_attn_core_split_kernel<64, 16, 1, false>), PRD_TA_NOT_FUSED);
         if (P == 64 && variant == 2) return PRD_TA_LAUNCH(12, (tri_attn_core_split_kernel<64, 12, 1, false>), PRD_TA_NOT_FUSED);
         if (P == 64 && variant == 3) return PRD_TA_LAUNCH(8, (tri_attn_core_split_kernel<64, 8, 1, true>), PRD_TA_NOT_FUSED);
         return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(8, (tri_attn_core_split_kernel<PP, 8, 2, true>), PRD_TA_NOT_FUSED));
     }
 #else
-    (void)split_long; (void)variant;
+    (void)variant;
 #endif
-    if (long_row) return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(8, (tri_attn_core_long_kernel<PP, 8>)));
+    if (plan.kind != TaKind::SHORT) return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(8, (tri_attn_core_long_kernel<PP, 8>)));
     return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(12, (tri_attn_core_kernel<PP, 12, true, false>)));
 #undef PRD_TA_NOT_FUSED
 #undef PRD_TA_LAUNCH
@@ -2493,23 +2465,22 @@ extern "C" int prd_tri_attn_core(float* og, const float* pair, const float* mask
 extern "C" int prd_single_attn_core(float* o, const float* qkvg, int ldq, const float* bias, const float* mask,
                                     int b, int N, int H, int c, hipStream_t stream) {
     if (!o || !qkvg || !bias || b <= 0 || N <= 0) return PRD_ERR_ARG;
-    if (c != 16 || H * c != 64) return PRD_ERR_UNSUPPORTED;
+    if (!prd_heads_4x16(H, c)) return PRD_ERR_UNSUPPORTED;
     if (ldq < 4 * H * c || (ldq & 3)) return PRD_ERR_ALIGN;
     return prd_launch<single_attn_core_kernel>(dim3(b * H * prd_ceil_div(N, 16)), dim3(256), 0, stream, o, qkvg, bias, mask, b, N, H, ldq);
 }
 
 // LDS of the fused form: the short-row split kernel's layout + the W_o image and bias of the previous attention
 static size_t tri_attn_fused_lds(int N, int P) {
-    bool long_row;
-    const size_t lds = tri_attn_lds(N, P, true, &long_row);
-    if (long_row) return (size_t)1 << 30;
-    return lds + (size_t)P * 4 + (size_t)P * 256;
+    const TaPlan plan = tri_attn_plan(N, P, true);
+    if (plan.kind != TaKind::SHORT) return (size_t)1 << 30;
+    return plan.lds + (size_t)P * 4 + (size_t)P * 256;
 }
 
 extern "C" int prd_tri_attn_core_fused_supported(int N, int P, int arith) {
     // (the fused form lives on the first-generation core: -DPRD_AB builds only; measured slower than two launches)
     return (PRD_FIRST_GEN && N > 0 && (P == 32 || P == 64) && arith >= 0 && (arith & 0xff) == PRD_ARITH_SPLIT16 &&
-            tri_attn_fused_lds(N, P) <= 160 * 1024) ? 1 : 0;
+            tri_attn_fused_lds(N, P) <= PRD_LDS_MAX) ? 1 : 0;
 }
 
 extern "C" int prd_tri_attn_core_fused(float* og, float* pair_out, const float* pair, const float* og_in, const float* wo_in,
@@ -2518,17 +2489,14 @@ extern "C" int prd_tri_attn_core_fused(float* og, float* pair_out, const float* 
                                        hipStream_t stream) {
     if (!og || !pair_out || !pair || !og_in || !wo_in || !bo_in || !mask || !wq || !wk || !wv || !wg || !bg || b <= 0 || N <= 0 ||
         pair_out == pair) return PRD_ERR_ARG;
-    if ((P != 32 && P != 64) || c != 16 || H * c != 64) return PRD_ERR_UNSUPPORTED;
+    if ((P != 32 && P != 64) || !prd_heads_4x16(H, c)) return PRD_ERR_UNSUPPORTED;
     if (!prd_tri_attn_core_fused_supported(N, P, PRD_ARITH_SPLIT16)) return PRD_ERR_UNSUPPORTED;
-    const int npad = prd_round_up(N, 64);
-    const size_t lds = tri_attn_fused_lds(N, P);
+#ifdef PRD_AB       // (the shipped library has returned above: no first generation, no fused form)
     const int grid = (int)(prd_rows_per_head((long)b * N, 256 / H) * H);
-#ifndef PRD_AB
-    (void)grid; (void)lds; (void)npad;
-    return PRD_ERR_UNSUPPORTED;
+    return PRD_FOR_P(P, PP, prd_launch<tri_attn_core_split_kernel<PP, 8, 2, true, true>>(dim3(grid), dim3(512), tri_attn_fused_lds(N, P), stream, og, pair, mask,
+        wq, wk, wv, wg, bg, b, N, prd_round_up(N, 64), H, ending, og_in, wo_in, bo_in, pair_out));
 #else
-    return PRD_FOR_P(P, PP, prd_launch<tri_attn_core_split_kernel<PP, 8, 2, true, true>>(dim3(grid), dim3(512), lds, stream, og, pair, mask, wq, wk, wv,
-                                                                                         wg, bg, b, N, npad, H, ending, og_in, wo_in, bo_in, pair_out));
+    return PRD_ERR_UNSUPPORTED;
 #endif
 }
 
@@ -2551,13 +2519,10 @@ extern "C" int prd_tri_attn(float* out, const float* pair, const float* mask, co
     PRD_SPLIT_ARITH(arith);
     if (!ws) return PRD_ERR_ARG;
     if (ws_bytes < prd_workspace_bytes("tri_attn", b, N, 0, P)) return PRD_ERR_WORKSPACE;
-    int e;
-    if (prd_tri_attn_variant(N, P, arith_full) == 3) {
-        const size_t nog = (size_t)b * N * N * 64;
-        e = prd_tri_attn_core_chunked(ws, pair, mask, wq, wk, wv, wg, bg, ending, b, N, P, H, c, ws + nog, ws_bytes - nog * sizeof(float), stream);
-    } else {
-        e = prd_tri_attn_core(ws, pair, mask, wq, wk, wv, wg, bg, ending, b, N, P, H, c, arith_full, stream);
-    }
-    if (e) return e;
+    const size_t nog = (size_t)b * N * N * 64;          // og; behind it the softmax statistics of key-chunked rows
+    if (prd_tri_attn_variant(N, P, arith_full) == 3)
+        PRD_TRY(prd_tri_attn_core_chunked(ws, pair, mask, wq, wk, wv, wg, bg, ending, b, N, P, H, c, ws + nog, ws_bytes - nog * sizeof(float), stream));
+    else
+        PRD_TRY(prd_tri_attn_core(ws, pair, mask, wq, wk, wv, wg, bg, ending, b, N, P, H, c, arith_full, stream));
     return prd_tri_attn_out(out, pair, ws, wo, bo, residual, b, N, P, queue, arith_full, stream);
 }

@@ -1885,7 +1885,7 @@ size_t v2l_lds_bytes(int N, int P, bool* share_out = nullptr) {
     const int NP = prd_round_up(N, 32), nqb = NP / 32, rem = nqb % 12, G = rem ? 12 / rem : 0;
     const size_t base = (size_t)64 * P * 4 + (size_t)NP * (2 * 32 + 64 + 4) + 128 + 64 + (size_t)V2L_TAIL_MAX * 128;
     const size_t extra = G >= 2 ? (size_t)rem * 2048 + 12 * 2560 : 0;
-    const bool share = G >= 2 && base + extra <= 160 * 1024;       // else the last round runs unshared (idle waves, same result)
+    const bool share = G >= 2 && base + extra <= PRD_LDS_MAX;       // else the last round runs unshared (idle waves, same result)
     if (share_out) *share_out = share;
     return base + (share ? extra : 0);
 }
@@ -1910,21 +1910,30 @@ size_t v2_lds_bytes(int N, int P) {
 #define PRD2_FOR_AB_0123(v, NAME, ...) ((void)(v), PRD_WITH(int, NAME, 0, __VA_ARGS__))
 #endif
 
-// 1 when the second-generation core serves rows of N positions (split-16 arithmetic only)
-extern "C" int prd_tri_attn_v2_supported(int N, int P, int tune) {
-    if (N <= 0 || (P != 32 && P != 64)) return 0;
-    if (N <= V2_MAXN) return v2_lds_bytes(N, P) <= 160 * 1024 ? 1 : 0;
-    if (PRD_TGET_TA2_NO_LONG(tune)) return 0;           // A/B switch: long rows stay on the first generation
-    return (prd_round_up(N, 32) <= 1024 && v2l_lds_bytes(N, P) <= 160 * 1024) ? 1 : 0;
+// ---- the dispatch of the second-generation core, decided ONCE for the queries below and the launch (which keeps the kernel flags):
+// the kernel for rows of N positions under the switch word `tune`, its LDS bytes, long rows: is the last round of query blocks shared ----
+enum class Ta2Kernel { NONE = 0, V2 = 1, V3 = 2, V2L = 3 };      // the values prd_tri_attn_v2_form reports
+struct Ta2Plan { Ta2Kernel kernel; size_t lds; bool share; };
+static Ta2Plan tri_attn_v2_plan(int N, int P, int tune) {
+    const Ta2Plan none = {Ta2Kernel::NONE, 0, false};
+    if (N <= 0 || (P != 32 && P != 64)) return none;
+    if (N <= V2_MAXN) {             // short rows: overlapped phases (v3) where its two K / V buffers fit, else one barrier per phase (v2)
+        if (v2_lds_bytes(N, P) > PRD_LDS_MAX) return none;
+        if (!PRD_TGET_TA2_NO_V3(tune) && v3_lds_bytes(N, P) <= PRD_LDS_MAX) return {Ta2Kernel::V3, v3_lds_bytes(N, P), false};
+        return {Ta2Kernel::V2, v2_lds_bytes(N, P), false};
+    }
+    if (PRD_TGET_TA2_NO_LONG(tune)) return none;        // A/B switch: long rows stay on the first generation
+    bool share = false;
+    const size_t lds = v2l_lds_bytes(N, P, &share);
+    if (prd_round_up(N, 32) > 1024 || lds > PRD_LDS_MAX) return none;
+    return {Ta2Kernel::V2L, lds, share};
 }
 
-// which kernel prd_tri_attn_core_v2 launches for rows of N positions: 0 = none (unsupported), 1 = tri_attn_core_v2_kernel,
-// 2 = tri_attn_core_v3_kernel (overlapped phases), 3 = tri_attn_core_v2l_kernel (long rows)
-extern "C" int prd_tri_attn_v2_form(int N, int P, int tune) {
-    if (!prd_tri_attn_v2_supported(N, P, tune)) return 0;
-    if (N > V2_MAXN) return 3;
-    return (!PRD_TGET_TA2_NO_V3(tune) && v3_lds_bytes(N, P) <= 160 * 1024) ? 2 : 1;
-}
+// 1 when the second-generation core serves rows of N positions (split-16 arithmetic only)
+extern "C" int prd_tri_attn_v2_supported(int N, int P, int tune) { return tri_attn_v2_plan(N, P, tune).kernel != Ta2Kernel::NONE ? 1 : 0; }
+
+// which kernel prd_tri_attn_core_v2 launches: 0 none, 1 tri_attn_core_v2_kernel, 2 tri_attn_core_v3_kernel, 3 tri_attn_core_v2l_kernel
+extern "C" int prd_tri_attn_v2_form(int N, int P, int tune) { return (int)tri_attn_v2_plan(N, P, tune).kernel; }
 
 // lse (may be null; short rows only): [b * N rows][H][N][2] = (m, log2 l) of every query: reference and log2 of the sum of
 // 2^(logit - m) in the log2 domain, kept by the training forward for prd_tri_attn_bwd_core_v2
@@ -1932,19 +1941,17 @@ extern "C" int prd_tri_attn_core_v2_lse(float* og, float* lse, const float* pair
                                         const float* wv, const float* wg, const float* bg, int ending,
                                         int b, int N, int P, int H, int c, int tune, hipStream_t stream) {
     if (!og || !pair || !mask || !wq || !wk || !wv || !wg || !bg || b <= 0 || N <= 0 || tune < 0) return PRD_ERR_ARG;
-    if ((P != 32 && P != 64) || c != 16 || H * c != 64) return PRD_ERR_UNSUPPORTED;
-    if (!prd_tri_attn_v2_supported(N, P, tune)) return PRD_ERR_UNSUPPORTED;
-    if (lse && N > V2_MAXN) return PRD_ERR_UNSUPPORTED;
+    if ((P != 32 && P != 64) || !prd_heads_4x16(H, c)) return PRD_ERR_UNSUPPORTED;
+    const Ta2Plan plan = tri_attn_v2_plan(N, P, tune);
+    if (plan.kernel == Ta2Kernel::NONE) return PRD_ERR_UNSUPPORTED;
+    const bool long_rows = plan.kernel == Ta2Kernel::V2L, v3 = plan.kernel == Ta2Kernel::V3;
+    if (lse && long_rows) return PRD_ERR_UNSUPPORTED;
     if ((long)b * N * N > 0x7fffffffL / 2) return PRD_ERR_UNSUPPORTED;      // 32-bit position arithmetic in the kernel
     const int NP = prd_round_up(N, 32);
-    const bool long_rows = N > V2_MAXN;
-    bool share = false;
-    const size_t lds = long_rows ? v2l_lds_bytes(N, P, &share) : v2_lds_bytes(N, P);
-    const int grid = (int)(prd_rows_per_head_xcd8((long)b * N, 256 / H, !((tune >> 20) & 1)) * H);      // (PRD_TUNE_TA2_NO_XCD8: A/B switch)
+    const size_t lds = plan.lds;
+    const int grid = (int)(prd_rows_per_head_xcd8((long)b * N, 256 / H, !PRD_TGET_TA2_NO_XCD8(tune)) * H);        // (A/B switch)
     constexpr int NWV = 12;                             // nqb <= 12 query blocks, one wave each
     const int flags_env = PRD_TGET_TA2_FLAGS(tune);     // A/B switch: kernel flags given by the caller (-1: per-kernel default)
-    const int use_v3 = !PRD_TGET_TA2_NO_V3(tune);       // A/B switch: 0 = the barrier-per-phase form
-    const bool v3 = !long_rows && use_v3 && v3_lds_bytes(N, P) <= 160 * 1024;
     // bit 0 = key-loop priorities by remaining work: needed where the waves of a SIMD must end together (v2, v2l); with
     // overlapped phases (v3) an early finisher starts the next row's projection instead: 67.5 -> 65.9 us without them
     const int flags0 = flags_env >= 0 ? flags_env : (v3 ? 0 : 1);
@@ -1953,7 +1960,7 @@ extern "C" int prd_tri_attn_core_v2_lse(float* og, float* lse, const float* pair
     // A/B: PRD_TA2_FLAGS with bit 1 set keeps it a regular tile)
     const int ntail_ = N - 32 * (nqb_ - 1);
     const bool tail1 = long_rows && nqb_ >= 2 && ntail_ >= 1 && ntail_ <= V2L_TAIL_MAX && !PRD_TGET_TA2_NO_GV(tune) && !(flags0 & 2);
-    const int flags = flags0 | ((long_rows && rem_ && 12 / rem_ >= 2 && !share) ? 16 : 0) | (PRD_TGET_TA2_NO_TAIL_SPLIT(tune) ? 32 : 0)
+    const int flags = flags0 | ((long_rows && rem_ && 12 / rem_ >= 2 && !plan.share) ? 16 : 0) | (PRD_TGET_TA2_NO_TAIL_SPLIT(tune) ? 32 : 0)
                       | (tail1 ? 64 : 0) | ((long_rows && (flags0 & 4)) ? 128 : 0);    // (PRD_TA2_FLAGS bit 2: the shared last round in its round-5 form)
     if (long_rows) {
         const bool pf = (flags & 8) != 0;               // next-row prefetch of the wave's first block (costs 32 registers; spills)
@@ -1963,7 +1970,6 @@ extern "C" int prd_tri_attn_core_v2_lse(float* og, float* lse, const float* pair
                                                                    wv, wg, bg, b, N, NP, H, ending, flags))));
     }
     if (v3) {
-        const size_t lds3 = v3_lds_bytes(N, P);
         const int kl = flags_env >= 0 ? (flags >> 1) & 3 : PRD_V3_DEFAULT_KL;     // key-loop form (bits 1-2 of PRD_TA2_FLAGS; v3 has no stagger)
         // phase 1 with [G|V] as one row GEMM + transposed V store (default); PRD_TUNE_TA2_NO_GV: the G GEMM + swapped V GEMM of round 3.
         // The A/B key-loop forms 1-3 exist with the round-3 phase 1 only (measured in round 5, none faster).  The scheduling
@@ -1971,7 +1977,7 @@ extern "C" int prd_tri_attn_core_v2_lse(float* og, float* lse, const float* pair
         const bool gvf = !PRD_TGET_TA2_NO_GV(tune) && kl == 0;
         return PRD_FOR_P(P, PP, PRD2_FOR_AB_BOOL(gvf, GVF, true, PRD2_FOR_AB_0123(kl, KL, [&] {
             constexpr int KLF = GVF ? 0 : KL;
-            return prd_launch<tri_attn_core_v3_kernel<PP, NWV, KLF, GVF>>(dim3(grid), dim3(NWV * 64), lds3, stream, og, pair, mask, wq, wk, wv, wg,
+            return prd_launch<tri_attn_core_v3_kernel<PP, NWV, KLF, GVF>>(dim3(grid), dim3(NWV * 64), lds, stream, og, pair, mask, wq, wk, wv, wg,
                                                                           bg, b, N, NP, H, ending, flags & ~6, lse);
         }())));
     }
@@ -2000,9 +2006,8 @@ static int prd_cu_count() {
 // dispatch takes for N <= 320-odd), default kernel switches
 extern "C" int prd_tri_attn_pair_supported(int N, int P, int arith) {
     PRD_SPLIT_ARITH(arith);
-    if (N <= 0 || (P != 32 && P != 64) || arith != PRD_ARITH_SPLIT16) return 0;
-    if (N > V2_MAXN || PRD_TGET_TA2_NO_V3(tune) || PRD_TGET_TA2_NO_GV(tune) || PRD_TGET_TA2_FLAGS(tune) >= 0) return 0;
-    return v3_lds_bytes(N, P) <= 160 * 1024 ? 1 : 0;
+    if (arith != PRD_ARITH_SPLIT16 || PRD_TGET_TA2_NO_GV(tune) || PRD_TGET_TA2_FLAGS(tune) >= 0) return 0;
+    return tri_attn_v2_plan(N, P, tune).kernel == Ta2Kernel::V3 ? 1 : 0;
 }
 
 extern "C" int prd_tri_attn_pair(float* og, float* pair, const float* mask, const float* const* w_start, const float* const* w_end,
@@ -2011,7 +2016,7 @@ extern "C" int prd_tri_attn_pair(float* og, float* pair, const float* mask, cons
     const int tune = arith >> 8;                        // (the PRD_TUNE_* word above the arithmetic)
     for (int k = 0; k < 7; ++k) if (!w_start[k]) return PRD_ERR_ARG;
     for (int k = 0; k < 5; ++k) if (!w_end[k]) return PRD_ERR_ARG;
-    if (c != 16 || H * c != 64) return PRD_ERR_UNSUPPORTED;
+    if (!prd_heads_4x16(H, c)) return PRD_ERR_UNSUPPORTED;
     if (!prd_tri_attn_pair_supported(N, P, arith)) return PRD_ERR_UNSUPPORTED;
     if ((long)b * N * N > 0x7fffffffL / 2) return PRD_ERR_UNSUPPORTED;
     const int NP = prd_round_up(N, 32);
@@ -2019,7 +2024,7 @@ extern "C" int prd_tri_attn_pair(float* og, float* pair, const float* mask, cons
     // every workgroup must be resident for the in-kernel barriers: one workgroup of 12 waves + ~150 KB of LDS per CU
     const int cus = prd_cu_count();
     if (cus <= 0 || grid > cus) return PRD_ERR_UNSUPPORTED;
-    const size_t lds3 = v3_lds_bytes(N, P);
+    const size_t lds3 = tri_attn_v2_plan(N, P, tune).lds;
     const size_t ldso = (size_t)P * 64 * 4 + (size_t)P * 4;
     const size_t lds = lds3 > ldso ? lds3 : ldso;
     hipError_t e = hipMemsetAsync(bar, 0, 32 * sizeof(unsigned), stream);     // counters, timeout flag, memberships: zero before EVERY launch
@@ -2035,14 +2040,14 @@ extern "C" int prd_tri_attn_pair(float* og, float* pair, const float* mask, cons
 extern "C" int prd_tri_attn_bwd_core_v2_supported(int N, int P) {
     if (N <= 0 || (P != 32 && P != 64)) return 0;
     const int NP = prd_round_up(N, 32);
-    return (NP / 32 <= 12 && b2_layout(P, NP).total <= 160u * 1024u) ? 1 : 0;
+    return (NP / 32 <= 12 && b2_layout(P, NP).total <= (unsigned)PRD_LDS_MAX) ? 1 : 0;
 }
 
 extern "C" int prd_tri_attn_bwd_core_v2(float* dqkvg, const float* dog, const float* og, const float* pair, const float* mask,
                                         const float* wq, const float* wk, const float* wv, const float* wg, const float* bg,
                                         const float* lse, float* x_out, int ending, int b, int N, int P, int H, int c, hipStream_t stream) {
     if (!dqkvg || !dog || !og || !pair || !mask || !wq || !wk || !wv || !wg || !bg || b <= 0 || N <= 0) return PRD_ERR_ARG;
-    if ((P != 32 && P != 64) || c != 16 || H * c != 64) return PRD_ERR_UNSUPPORTED;
+    if ((P != 32 && P != 64) || !prd_heads_4x16(H, c)) return PRD_ERR_UNSUPPORTED;
     if (!prd_tri_attn_bwd_core_v2_supported(N, P)) return PRD_ERR_UNSUPPORTED;
     if ((long)b * N * N > 0x7fffffffL / 4) return PRD_ERR_UNSUPPORTED;      // 32-bit position arithmetic in the kernel
     const int NP = prd_round_up(N, 32);

@@ -12,7 +12,7 @@ from typing import Mapping, Optional, Tuple
 
 import torch
 
-from ._lib import PrdGemm, arithmetic, check, dptr, lib, stream
+from ._lib import _DEFINES, _TUNE_SHIFT, PrdGemm, arithmetic, check, dptr, lib, stream
 
 F32 = torch.float32
 
@@ -103,10 +103,10 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, *, a_off=0, b_off=0, c_off=0, G1=1,
     g.a_scale = float(a_scale)
     g.mul_pos = int(mul_pos)
     g.a_amax = (a_amax if isinstance(a_amax, int) else dptr(a_amax, torch.int32)) if a_amax is not None else None
-    g.arith = lib().prd_get_gemm_mode() | (lib().prd_get_tune() << 8)
+    g.arith = lib().prd_get_gemm_mode() | (lib().prd_get_tune() << _TUNE_SHIFT)
     import ctypes
     code = lib().prd_gemm(ctypes.byref(g), stream())
-    if unsupported_ok and code == -3:
+    if unsupported_ok and code == _DEFINES["ERR_UNSUPPORTED"]:
         return None
     check(code, "prd_gemm")
     return Cout

@@ -4,6 +4,7 @@
  * Build + run: python -m protein_redesign_amd.build --asan   (tests/test_host_cpu.py::test_c_abi_argument_checks_under_asan) */
 #include <pthread.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/prd_hip.h"
@@ -218,6 +219,14 @@ int main(void) {
     EXPECT((int)(prd_workspace_bytes("tri_mul", 1, 320, 512, 64) != (size_t)3 * 64 * 320 * 320 * 4), 0);
     EXPECT((int)prd_workspace_bytes("nonsense", 1, 320, 512, 64), 0);
     EXPECT((int)prd_workspace_bytes(0, 1, 320, 512, 64), 0);
+    {   /* operator names are compared whole: a shorter string is not read past its terminator (exact-size heap copies, under ASan) */
+        char* one = strdup("t");
+        char* none = strdup("");
+        EXPECT((int)prd_workspace_bytes(one, 1, 320, 512, 64), 0);
+        EXPECT((int)prd_workspace_bytes(none, 1, 320, 512, 64), 0);
+        free(one);
+        free(none);
+    }
     {
         struct thread_arg t0 = {PRD_ARITH_FP32, 3, 0, 1, 0}, t1 = {PRD_ARITH_SPLIT16, 2, 1, 0, 0},
                           t2 = {PRD_ARITH_SPLIT16 | PRD_TUNE(PRD_TUNE_TA2_NO_LONG), 3, 1, 1, 0};

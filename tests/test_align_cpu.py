@@ -127,7 +127,7 @@ def test_build_issues_the_commands_it_issued_before(monkeypatch):
     assert rec.cmds == [shipped[:-3] + [src, "-o", obj],
                         shipped[:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_align.so", obj]]
     assert build.SOURCES == ["prd_gemm.hip", "prd_pair.hip", "prd_tri.hip", "prd_tri2.hip", "prd_bwd.hip", "prd_spa.hip", "prd_tri_heads.hip",
-                             "prd_tri_heads_bwd.hip", "prd_mask.hip"] and sorted(build.VARIANTS) == ["ab", "asan", "shipped", "timing"]
+                             "prd_tri_heads_bwd.hip", "prd_mask.hip"] and sorted(build.VARIANTS) == ["ab", "asan", "shipped", "timing", "trace"]
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")

@@ -202,7 +202,10 @@ def test_variant_table_names_the_documented_outputs():
     pkg = os.path.join(ROOT, "protein_redesign_amd")
     assert {k: (os.path.relpath(v.objdir, pkg), os.path.relpath(v.lib, pkg)) for k, v in build.VARIANTS.items()} == {
         "shipped": ("csrc", "libprd_hip.so"), "ab": ("csrc/ab", "libprd_hip_ab.so"),
-        "timing": ("csrc/timing", "libprd_hip_timing.so"), "asan": ("csrc/asan", "libprd_hip_asan.so")}
+        "timing": ("csrc/timing", "libprd_hip_timing.so"), "trace": ("csrc/trace", "libprd_hip_trace.so"),
+        "asan": ("csrc/asan", "libprd_hip_asan.so")}
+    # the trace variant differs from the shipped compile by its macro and by unoptimised device code, which none of its calls reaches
+    assert build.VARIANTS["trace"].cflags == ["-DPRD_LAUNCH_TRACE", "-Xarch_device", "-O0"] and not build.VARIANTS["trace"].ldflags
     assert build.LIB == build.VARIANTS["shipped"].lib and build.RESOURCE_JSON == os.path.join(pkg, "csrc", "resource_usage.json")
 
 
