@@ -304,3 +304,61 @@ def dptr(t, dtype=torch.float32):
 
 def stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+# ---- the side libraries (align, tmalign, quality): one binding, one statement of their argument checks -------------------------------
+class SideLibrary:
+    """The binding of ``libprd_<name>.so`` beside the package, derived from the name: ``include/prd_<name>.h`` is read and parsed here
+    (``entries``, and ``defines`` without their ``PRD_<NAME>_`` prefix), the library itself is loaded on the first ``lib()``.  ``version``:
+    the ``PRD_<NAME>_VERSION`` the calling module is written against; ``limit``: what ERR_UNSUPPORTED means to a caller, a sentence in
+    which ``{MAX_N}`` and the like stand for the header's defines."""
+
+    def __init__(self, name: str, version: int, limit: str):
+        self.name, self.version, self.prefix = name, version, f"PRD_{name.upper()}_"
+        with open(os.path.join(os.path.dirname(HERE), "include", f"prd_{name}.h")) as f:
+            text = f.read()                     # the header is the only statement of the C ABI and of its constants
+        self.entries = parse_header(text, f"include/prd_{name}.h")
+        self.defines = parse_defines(text, self.prefix)
+        self.limit = limit.format(**self.defines)
+        self._cdll = None
+
+    def lib(self):
+        """The loaded library; raises RuntimeError (never falls back) when it has not been built."""
+        if self._cdll is None:
+            self._cdll = load_library(os.path.join(HERE, f"libprd_{self.name}.so"), self.entries, f"prd_{self.name}_version", self.version,
+                                      f"--{self.name}")
+        return self._cdll
+
+    def check(self, code: int, what: str):
+        check(code, what, self.defines, self.prefix, self.limit)
+
+
+def structures(t, name, *, runs, letter, N=None, bounds=None):
+    """[K,N,3] fp32 device tensor whose last stride is 1 (made so if it is not); returns (tensor, structure stride, row stride).
+    ``letter``: what the messages call the first dimension; ``runs``: the subject and verb of the "GPU only" message; ``N``: the
+    positions expected; ``bounds``: the SideLibrary whose ``MAX_S`` / ``MAX_N`` are refused here already, or None."""
+    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{name} must be a [{letter},N,3] tensor, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    if N is not None and t.shape[1] != N:
+        raise ValueError(f"{name} has {t.shape[1]} positions, expected {N}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: {runs} on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if bounds is not None and (t.shape[1] > bounds.defines["MAX_N"] or t.shape[0] > bounds.defines["MAX_S"]):
+        raise ValueError(f"{name}: {t.shape[0]} structures of {t.shape[1]} positions, at most {bounds.defines['MAX_S']} structures "
+                         f"({bounds.prefix}MAX_S) of {bounds.defines['MAX_N']} positions ({bounds.prefix}MAX_N) are supported")
+    if t.stride(2) != 1 or t.stride(1) < 3 or t.stride(0) < 0:
+        t = t.contiguous()
+    return t, t.stride(0), t.stride(1)
+
+
+def position_mask(mask, name, N, device):
+    """``mask`` as a contiguous [N] fp32 (0 / 1) tensor on ``device``, or ValueError"""
+    if not torch.is_tensor(mask) or mask.shape != (N,):
+        raise ValueError(f"{name} must be a [{N}] tensor, got {tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__}")
+    if mask.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32 (0 / 1), got {mask.dtype}")
+    if mask.device != device:
+        raise ValueError(f"{name} is on {mask.device}, the structures on {device}")
+    return mask.contiguous()

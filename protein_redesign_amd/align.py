@@ -6,39 +6,19 @@ Everything runs on the current stream with no host synchronisation.  HIP only: a
 from __future__ import annotations
 
 import dataclasses
-import os
+import functools
 
 import torch
 
-from ._lib import check, dptr, load_library, parse_defines, parse_header, stream
+from ._lib import SideLibrary, dptr, position_mask, stream, structures
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libprd_align.so")
-HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "prd_align.h")
-
-with open(HEADER_PATH) as _f:
-    _HEADER = _f.read()                         # the header is the only statement of the C ABI and of its constants
-ENTRIES = parse_header(_HEADER, "include/prd_align.h")
-_DEFINES = parse_defines(_HEADER, "PRD_ALIGN_")
-
-ABI_VERSION = 100           # include/prd_align.h PRD_ALIGN_VERSION this binding is written against
+_BINDING = SideLibrary("align", 100, "at most {MAX_N} positions per structure (PRD_ALIGN_MAX_N) and 65535 structures per apply")
+ENTRIES, _DEFINES, ABI_VERSION = _BINDING.entries, _BINDING.defines, _BINDING.version      # 100: include/prd_align.h PRD_ALIGN_VERSION
+lib, _check = _BINDING.lib, _BINDING.check
 MAX_N = _DEFINES["MAX_N"]
 MODES = {"tm": _DEFINES["MODE_TM"], "rmsd": _DEFINES["MODE_RMSD"]}
 PAIRS_CROSS, PAIRS_SELF = _DEFINES["PAIRS_CROSS"], _DEFINES["PAIRS_SELF"]
-
-_lib = None
-
-
-def lib():
-    """The loaded library; raises RuntimeError (never falls back) when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = load_library(LIB_PATH, ENTRIES, "prd_align_version", ABI_VERSION, "--align")
-    return _lib
-
-
-def _check(code: int, what: str):
-    check(code, what, _DEFINES, "PRD_ALIGN_", f"at most {MAX_N} positions per structure (PRD_ALIGN_MAX_N) and 65535 structures per apply")
+_structures = functools.partial(structures, runs="the alignment runs", letter="K")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -49,31 +29,6 @@ class Superposition:
     rotation: torch.Tensor          # [..., 3, 3]; determinant -1 where mirrored
     translation: torch.Tensor       # [..., 3]
     mirrored: torch.Tensor          # [...] int32
-
-
-def _structures(t, name, N=None):
-    """[K,N,3] fp32 device tensor whose last stride is 1 (made so if it is not); returns (tensor, structure stride, row stride)"""
-    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{name} must be a [K,N,3] tensor, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
-    if N is not None and t.shape[1] != N:
-        raise ValueError(f"{name} has {t.shape[1]} positions, expected {N}")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32, got {t.dtype}")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: the alignment runs on the GPU only (got a CPU tensor); there is no CPU fallback")
-    if t.stride(2) != 1 or t.stride(1) < 3 or t.stride(0) < 0:
-        t = t.contiguous()
-    return t, t.stride(0), t.stride(1)
-
-
-def _mask(mask, N, device):
-    if not torch.is_tensor(mask) or mask.shape != (N,):
-        raise ValueError(f"mask must be a [{N}] tensor, got {tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__}")
-    if mask.dtype != torch.float32:
-        raise ValueError(f"mask must be float32 (0 / 1), got {mask.dtype}")
-    if mask.device != device:
-        raise ValueError(f"mask is on {mask.device}, the structures on {device}")
-    return mask.contiguous()
 
 
 def _run(x, y, mask, S, R, N, pairs, mode, mirror):
@@ -110,11 +65,11 @@ def superimpose(x, ref, mask, mirror: bool = True, mode: str = "tm") -> Superpos
     if not torch.is_tensor(ref) or ref.dim() not in (2, 3):
         raise ValueError("ref must be a [N,3] or [R,N,3] tensor")
     single = ref.dim() == 2
-    y = _structures(ref.unsqueeze(0) if single else ref, "ref", N)
+    y = _structures(ref.unsqueeze(0) if single else ref, "ref", N=N)
     if y[0].device != x[0].device:
         raise ValueError(f"ref is on {y[0].device}, x on {x[0].device}")
     R = y[0].shape[0]
-    out = _run(x, y, _mask(mask, N, x[0].device), S, R, N, PAIRS_CROSS, mode, mirror)
+    out = _run(x, y, position_mask(mask, "mask", N, x[0].device), S, R, N, PAIRS_CROSS, mode, mirror)
     if single:
         out = Superposition(out.tm[:, 0], out.rmsd[:, 0], out.rotation[:, 0], out.translation[:, 0], out.mirrored[:, 0])
     return out
@@ -125,7 +80,7 @@ def pairwise(x, mask, mirror: bool = True, mode: str = "tm") -> Superposition:
     the diagonal is tm 1, rmsd 0, identity."""
     x = _structures(x, "x")
     S, N = x[0].shape[:2]
-    return _run(x, None, _mask(mask, N, x[0].device), S, S, N, PAIRS_SELF, mode, mirror)
+    return _run(x, None, position_mask(mask, "mask", N, x[0].device), S, S, N, PAIRS_SELF, mode, mirror)
 
 
 def pairwise_tm(x, mask, mirror: bool = True) -> torch.Tensor:

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import dataclasses
 import os
+import warnings
 from pathlib import Path
 from typing import Any, Dict, Iterable, List, Mapping, Optional, Sequence, Tuple, Union
 
@@ -389,18 +390,22 @@ def update_pos(protein: Protein, num_ligand_atoms: int, pos: np.ndarray) -> Tupl
 # generate.py:138-195 without Lightning / rdkit / TM-align
 # ---------------------------------------------------------------------------------------------------
 
+def _ca_trace_problem(data: Mapping[str, Any]) -> Optional[str]:
+    """What keeps the featurised complex from serving as a C-alpha trace with coordinates, as the clause of a message; None if nothing."""
+    ram, rap = torch.as_tensor(data["residue_atom_mask"]), torch.as_tensor(data["residue_atom_pos"])
+    if ram.numel() == 0 or not bool((ram[:, 1] > 0.5).any()):
+        return "no residue has its C-alpha marked in residue_atom_mask"
+    if not bool((rap[:, 1] != 0).any()):
+        return "the C-alpha coordinates are all zero (a protein built from its sequence alone?)"
+    return None
+
+
 def check_complex_structure(data: Mapping[str, Any]) -> None:
     """ValueError unless the featurised complex carries the coordinates a pocket is measured in: the C-alpha column of
     ``residue_atom_mask`` set, C-alpha coordinates that are not all zero, and at least one ligand atom with a position.  Host data
     only; ``protein_from_sequence`` inputs have none (their coordinates are zero)."""
-    ram = torch.as_tensor(data["residue_atom_mask"])
-    rap = torch.as_tensor(data["residue_atom_pos"])
-    what = None
-    if ram.numel() == 0 or not bool((ram[:, 1] > 0.5).any()):
-        what = "no residue has its C-alpha marked in residue_atom_mask"
-    elif not bool((rap[:, 1] != 0).any()):
-        what = "the C-alpha coordinates are all zero (a protein built from its sequence alone?)"
-    elif int(data.get("num_atoms", 0)) < 1 or "atom_pos" not in data or torch.as_tensor(data["atom_pos"]).shape[0] < 1:
+    what = _ca_trace_problem(data)
+    if what is None and (int(data.get("num_atoms", 0)) < 1 or "atom_pos" not in data or torch.as_tensor(data["atom_pos"]).shape[0] < 1):
         what = "there is no ligand atom with a position"
     if what is not None:
         raise ValueError("Redesign.within / Redesign.nearest measure a pocket and need the complex's coordinates: " + what
@@ -416,16 +421,11 @@ def _alignment_reference(data: Mapping[str, Any], align_to) -> Optional[np.ndarr
             return None
         if align_to != "input":
             raise ValueError(f"align_to must be 'input', 'first', a Protein or an [{nr},3] array, got {align_to!r}")
-        ram, rap = torch.as_tensor(data["residue_atom_mask"]), torch.as_tensor(data["residue_atom_pos"])
-        what = None
-        if ram.numel() == 0 or not bool((ram[:, 1] > 0.5).any()):
-            what = "no residue has its C-alpha marked in residue_atom_mask"
-        elif not bool((rap[:, 1] != 0).any()):
-            what = "the C-alpha coordinates are all zero (a protein built from its sequence alone?)"
+        what = _ca_trace_problem(data)
         if what is not None:
             raise ValueError("align_to='input' superimposes the samples on the complex's own C-alpha coordinates: " + what
                              + "; use align_to='first' or pass a reference structure")
-        return np.asarray(rap[:, 1], dtype=np.float32)
+        return np.asarray(torch.as_tensor(data["residue_atom_pos"])[:, 1], dtype=np.float32)
     ref = align_to.atom_pos[:, 1] if isinstance(align_to, Protein) else align_to
     ref = np.asarray(ref, dtype=np.float32)
     if ref.shape != (nr, 3):
@@ -443,17 +443,12 @@ def _quality_reference(data: Mapping[str, Any], assess):
             return None
         if assess != "input":
             raise ValueError(f"assess must be None, 'self', 'input' or a Protein, got {assess!r}")
-        ram, rap = torch.as_tensor(data["residue_atom_mask"]), torch.as_tensor(data["residue_atom_pos"])
-        what = None
-        if ram.numel() == 0 or not bool((ram[:, 1] > 0.5).any()):
-            what = "no residue has its C-alpha marked in residue_atom_mask"
-        elif not bool((rap[:, 1] != 0).any()):
-            what = "the C-alpha coordinates are all zero (a protein built from its sequence alone?)"
+        what = _ca_trace_problem(data)
         if what is not None:
             raise ValueError("assess='input' scores the samples against the complex's own coordinates: " + what
                              + "; use assess='self' or pass a reference structure")
         ref = np.zeros((na + nr, 3), dtype=np.float32)
-        ref[na:] = np.asarray(rap[:, 1], dtype=np.float32)
+        ref[na:] = np.asarray(torch.as_tensor(data["residue_atom_pos"])[:, 1], dtype=np.float32)
         ligand = na >= 1 and "atom_pos" in data and tuple(torch.as_tensor(data["atom_pos"]).shape) == (na, 3)
         if ligand:
             ref[:na] = np.asarray(data["atom_pos"], dtype=np.float32)
@@ -493,6 +488,126 @@ def _structural_reference(align_to):
     if not bool((ref[ca] != 0).any()):
         raise ValueError("align_to: the C-alpha coordinates of the reference are all zero (a protein built from its sequence alone?)")
     return ref, ca
+
+
+def _references(model, data, redesign, align_to, correspondence, assess):
+    """Stage (a) of generate_samples: every refusal that host data alone decides, in the order callers rely on, before ``model.device``
+    is read.  Returns (structural reference or None, index-wise alignment reference or None, quality reference or None, redesign spec)."""
+    if correspondence not in ("index", "structure"):
+        raise ValueError(f"correspondence must be 'index' or 'structure', got {correspondence!r}")
+    struct_ref = _structural_reference(align_to) if correspondence == "structure" else None
+    if struct_ref is not None:
+        from .tmalign import MAX_N
+        rows = int(data["num_atoms"]) + int(data["num_residues"])
+        if rows > MAX_N:                        # the sample side of the alignment: refused now, not after the samples are drawn
+            raise ValueError(f"correspondence='structure': the complex has {rows} rows (ligand atoms + residues), an alignment by "
+                             f"structure takes at most {MAX_N} (PRD_TMALIGN_MAX_N)")
+    align_ref = _alignment_reference(data, align_to) if align_to is not None and struct_ref is None else None
+    quality_ref = _quality_reference(data, assess) if assess is not None else None
+    spec = redesign if redesign is not None else getattr(model, "redesign", None)
+    if spec is not None and spec.needs_structure:
+        check_complex_structure(data)
+    return struct_ref, align_ref, quality_ref, spec
+
+
+def _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device):
+    """Stage (b): the sampling loop, with no synchronisation beyond its copies to the host.  Returns (positions per batch -- left on the
+    device if ``keep_on_device``, for the stages that score them there --, logits per batch on the host, the first prepared batch)."""
+    from .synthetic import NoiseSource, batch_to
+    positions, logits, first_batch = [], [], None
+    for start in range(0, num_samples, batch_size):
+        idx = list(range(start, min(start + batch_size, num_samples)))
+        batch = collate_fn([data] * len(idx))
+        batch = batch_to({k: v for k, v in batch.items() if torch.is_tensor(v)}, device)
+        pos, lg = model.sample(batch, sources=[NoiseSource(seed, k) for k in idx], redesign=spec)
+        if first_batch is None:
+            first_batch = batch                 # sample() prepared it in place: it carries the mask that was used
+        positions.append(pos if keep_on_device else pos.cpu())
+        logits.append(lg.cpu())
+    return positions, logits, first_batch
+
+
+def _assess(pos, first_batch, quality_ref, na, nr):
+    """Stage (c): the quality scores of the samples as model.sample returned them (distances do not see align_to's transform), as numpy"""
+    from . import quality as QL
+    ref = torch.from_numpy(quality_ref[0]).to(pos.device) if quality_ref is not None else None
+    scores = QL.assess(pos.float()[:, : na + nr], first_batch, ref, num_atoms=na, num_residues=nr,
+                       ref_has_ligand=quality_ref is not None and quality_ref[1])
+    scores["pocket"] = scores["pocket"][:, na:]
+    return {k: v.cpu().numpy() for k, v in scores.items()}
+
+
+def _superpose(pos, data, struct_ref, align_ref, mirror, na, nr):
+    """Stage (d): fit every sample to the reference (by structure, index-wise, or to the first sample), score the samples among themselves
+    and move whole rows into the reference's frame.  Returns (moved positions, the alignment dict), both still on the device."""
+    from . import align as AL
+    pos, device = pos.float(), pos.device
+    n = pos.shape[1]
+    ca_mask = torch.zeros(n)
+    ca_mask[na: na + nr] = (torch.as_tensor(data["residue_atom_mask"])[:, 1] > 0.5).float()
+    ca_mask = ca_mask.to(device)
+    if struct_ref is not None:
+        from . import tmalign as TM
+        fit = TM.align(pos, torch.from_numpy(struct_ref[0]).to(device), ca_mask, torch.from_numpy(struct_ref[1].astype(np.float32)).to(device),
+                       mirror=mirror)
+    else:
+        if align_ref is None:
+            warnings.warn("Using the first sample as a reference. The resulting structures may be mirror images.", UserWarning)
+            ref = pos[0].clone()
+        else:
+            ref = torch.zeros(n, 3)
+            ref[na: na + nr] = torch.from_numpy(align_ref)
+            ref = ref.to(device)
+        fit = AL.superimpose(pos, ref, ca_mask, mirror=mirror)
+    div = AL.diversity(pos, ca_mask, mirror=mirror)
+    moved = AL.apply(pos, fit.rotation, fit.translation)
+    alignment = {"tmscore": fit.tm, "rmsd": fit.rmsd, "mirrored": fit.mirrored, "rotation": fit.rotation, "translation": fit.translation,
+                 "diversity": div}
+    if struct_ref is not None:
+        alignment["n_aligned"] = fit.n_aligned
+        alignment["mapping"] = fit.mapping[:, na: na + nr]          # rows of the reference ARE its residue indices
+    return moved, alignment
+
+
+def _decode(data, positions, logits, na, nr):
+    """Stage (e): (proteins, ligand positions) of the samples, every protein with its decoded sequence; warns of undetermined residues"""
+    template = Protein(np.asarray(data["residue_chain_index"]), np.asarray(data["residue_index"]),
+                       np.asarray(data["residue_type"]), np.asarray(data["residue_atom_pos"], dtype=np.float32),
+                       np.asarray(data["residue_atom_mask"], dtype=np.float32))
+    proteins, ligands = [], []
+    for pos, lg in zip(positions, logits):
+        prot, lig = update_pos(template, na, pos)
+        seq = predict_seq(lg[na: na + nr])
+        prot = dataclasses.replace(prot, aatype=np.array([RESIDUE_TYPES.index(s) if s != "X" else -1 for s in seq], dtype=np.int64))
+        proteins.append(prot)
+        ligands.append(lig)
+    undetermined = [k for k, p in enumerate(proteins) if (p.aatype < 0).any()]
+    if undetermined:
+        warnings.warn(f"samples {undetermined} decode to 'X' at some residues; those are written as UNK", UserWarning)
+    return proteins, ligands
+
+
+def _write(output_dir, proteins, ligands, used_mask, alignment, quality):
+    """Stage (f): the files of ``output_dir``"""
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    proteins_to_pdb_file(proteins, out / "sample_protein.pdb")
+    np.save(out / "sample_ligand_pos.npy", np.stack(ligands))
+    if used_mask is not None:
+        np.save(out / "sample_redesign_mask.npy", used_mask)
+    if alignment is not None:
+        with open(out / "sample_tmscores.txt", "w") as f:
+            for tmscore in alignment["tmscore"]:
+                f.write(str(float(tmscore)) + "\n")
+        np.savez(out / "sample_alignment.npz", **alignment)
+    if quality is not None:
+        from .quality import SCALAR_COLUMNS
+        cols = [c for c in SCALAR_COLUMNS if c in quality]
+        np.savez(out / "sample_quality.npz", **quality)
+        with open(out / "sample_quality.txt", "w") as f:
+            f.write("# " + " ".join(cols) + "\n")
+            for k in range(len(proteins)):
+                f.write(" ".join(str(quality[c][k].item()) for c in cols) + "\n")
 
 
 @torch.inference_mode()
@@ -551,115 +666,23 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     the alignment dict when both are requested.  ``output_dir`` also receives ``sample_quality.npz`` (the dict) and
     ``sample_quality.txt``: a ``#`` line naming the columns, then one line per sample holding the scalar metrics in the order of
     ``quality.SCALAR_COLUMNS`` (those present)."""
-    import warnings
-
-    from .synthetic import NoiseSource, batch_to
-    if correspondence not in ("index", "structure"):
-        raise ValueError(f"correspondence must be 'index' or 'structure', got {correspondence!r}")
-    struct_ref = _structural_reference(align_to) if correspondence == "structure" else None  # refuses on the host data alone
-    if struct_ref is not None:
-        from .tmalign import MAX_N
-        rows = int(data["num_atoms"]) + int(data["num_residues"])
-        if rows > MAX_N:                        # the sample side of the alignment: refused now, not after the samples are drawn
-            raise ValueError(f"correspondence='structure': the complex has {rows} rows (ligand atoms + residues), an alignment by "
-                             f"structure takes at most {MAX_N} (PRD_TMALIGN_MAX_N)")
-    align_ref = _alignment_reference(data, align_to) if align_to is not None and struct_ref is None else None      # likewise
-    quality_ref = _quality_reference(data, assess) if assess is not None else None                                 # likewise
-    spec = redesign if redesign is not None else getattr(model, "redesign", None)
-    if spec is not None and spec.needs_structure:
-        check_complex_structure(data)
+    struct_ref, align_ref, quality_ref, spec = _references(model, data, redesign, align_to, correspondence, assess)
     device = model.device
     if spec is not None:
         spec = spec.to(device)                  # a positions mask is uploaded once, not per batch
-    positions, logits = [], []
-    first_batch = None
-    on_device = []                              # align_to / assess: the samples stay on the device until they are scored
-    for start in range(0, num_samples, batch_size):
-        idx = list(range(start, min(start + batch_size, num_samples)))
-        batch = collate_fn([data] * len(idx))
-        batch = batch_to({k: v for k, v in batch.items() if torch.is_tensor(v)}, device)
-        pos, lg = model.sample(batch, sources=[NoiseSource(seed, k) for k in idx], redesign=spec)
-        if first_batch is None:
-            first_batch = batch                 # sample() prepared it in place: it carries the mask that was used
-        if align_to is not None or assess is not None:
-            on_device.append(pos)
-        else:
-            positions.append(pos.cpu())
-        logits.append(lg.cpu())
+    na, nr = int(data["num_atoms"]), int(data["num_residues"])
+    scored = align_to is not None or assess is not None         # then the samples stay on the device until they are scored
+    drawn, logits, first_batch = _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device=scored)
     # every sample of the complex shares the mask: read from the first prepared batch, after the loop (no synchronisation inside it)
     used_mask = first_batch["residue_inv_extra_mask"][0].cpu().numpy() if spec is not None and first_batch is not None else None
-    na, nr = int(data["num_atoms"]), int(data["num_residues"])
-    alignment = quality = None
-    if assess is not None:                      # on the samples as model.sample returned them: distances do not see align_to's transform
-        from . import quality as QL
-        pos = torch.cat(on_device)
-        ref = torch.from_numpy(quality_ref[0]).to(device) if quality_ref is not None else None
-        scores = QL.assess(pos.float()[:, : na + nr], first_batch, ref, num_atoms=na, num_residues=nr,
-                           ref_has_ligand=quality_ref is not None and quality_ref[1])
-        scores["pocket"] = scores["pocket"][:, na:]
-        quality = {k: v.cpu().numpy() for k, v in scores.items()}
-        if align_to is None:
-            positions = [pos.cpu()]
-    if align_to is not None:
-        from . import align as AL
-        pos = torch.cat(on_device).float()
-        n = pos.shape[1]
-        ca_mask = torch.zeros(n)
-        ca_mask[na: na + nr] = (torch.as_tensor(data["residue_atom_mask"])[:, 1] > 0.5).float()
-        ca_mask = ca_mask.to(device)
-        if struct_ref is not None:
-            from . import tmalign as TM
-            fit = TM.align(pos, torch.from_numpy(struct_ref[0]).to(device), ca_mask, torch.from_numpy(struct_ref[1].astype(np.float32)).to(device),
-                           mirror=mirror)
-        else:
-            if align_ref is None:
-                warnings.warn("Using the first sample as a reference. The resulting structures may be mirror images.", UserWarning)
-                ref = pos[0].clone()
-            else:
-                ref = torch.zeros(n, 3)
-                ref[na: na + nr] = torch.from_numpy(align_ref)
-                ref = ref.to(device)
-            fit = AL.superimpose(pos, ref, ca_mask, mirror=mirror)
-        div = AL.diversity(pos, ca_mask, mirror=mirror)
-        positions = [AL.apply(pos, fit.rotation, fit.translation).cpu()]
-        alignment = {"tmscore": fit.tm.cpu().numpy(), "rmsd": fit.rmsd.cpu().numpy(), "mirrored": fit.mirrored.cpu().numpy(),
-                     "rotation": fit.rotation.cpu().numpy(), "translation": fit.translation.cpu().numpy(), "diversity": float(div.cpu())}
-        if struct_ref is not None:
-            alignment["n_aligned"] = fit.n_aligned.cpu().numpy()
-            alignment["mapping"] = fit.mapping[:, na: na + nr].cpu().numpy()         # rows of the reference ARE its residue indices
-    positions, logits = torch.cat(positions).numpy(), torch.cat(logits).numpy()
-    template = Protein(np.asarray(data["residue_chain_index"]), np.asarray(data["residue_index"]),
-                       np.asarray(data["residue_type"]), np.asarray(data["residue_atom_pos"], dtype=np.float32),
-                       np.asarray(data["residue_atom_mask"], dtype=np.float32))
-    proteins, ligands = [], []
-    for pos, lg in zip(positions, logits):
-        prot, lig = update_pos(template, na, pos)
-        seq = predict_seq(lg[na: na + nr])
-        prot = dataclasses.replace(prot, aatype=np.array([RESIDUE_TYPES.index(s) if s != "X" else -1 for s in seq], dtype=np.int64))
-        proteins.append(prot)
-        ligands.append(lig)
-    undetermined = [k for k, p in enumerate(proteins) if (p.aatype < 0).any()]
-    if undetermined:
-        warnings.warn(f"samples {undetermined} decode to 'X' at some residues; those are written as UNK", UserWarning)
+    pos = torch.cat(drawn)
+    quality = _assess(pos, first_batch, quality_ref, na, nr) if assess is not None else None
+    pos, alignment = _superpose(pos, data, struct_ref, align_ref, mirror, na, nr) if align_to is not None else (pos, None)
+    positions, logits = pos.cpu().numpy(), torch.cat(logits).numpy()       # the one copy of scored samples; unscored ones are on the host
+    if alignment is not None:
+        alignment = {k: float(v.cpu()) if k == "diversity" else v.cpu().numpy() for k, v in alignment.items()}
+    proteins, ligands = _decode(data, positions, logits, na, nr)
     if output_dir is not None:
-        out = Path(output_dir)
-        out.mkdir(parents=True, exist_ok=True)
-        proteins_to_pdb_file(proteins, out / "sample_protein.pdb")
-        np.save(out / "sample_ligand_pos.npy", np.stack(ligands))
-        if used_mask is not None:
-            np.save(out / "sample_redesign_mask.npy", used_mask)
-        if alignment is not None:
-            with open(out / "sample_tmscores.txt", "w") as f:
-                for tmscore in alignment["tmscore"]:
-                    f.write(str(float(tmscore)) + "\n")
-            np.savez(out / "sample_alignment.npz", **alignment)
-        if quality is not None:
-            from .quality import SCALAR_COLUMNS
-            cols = [c for c in SCALAR_COLUMNS if c in quality]
-            np.savez(out / "sample_quality.npz", **quality)
-            with open(out / "sample_quality.txt", "w") as f:
-                f.write("# " + " ".join(cols) + "\n")
-                for k in range(len(positions)):
-                    f.write(" ".join(str(quality[c][k].item()) for c in cols) + "\n")
+        _write(output_dir, proteins, ligands, used_mask, alignment, quality)
     result = (positions, logits, proteins, ligands) + ((used_mask,) if spec is not None else ())
     return result + ((alignment,) if alignment is not None else ()) + ((quality,) if quality is not None else ())

@@ -11,25 +11,18 @@ Everything runs on the current stream with no host synchronisation.  HIP only: a
 from __future__ import annotations
 
 import dataclasses
+import functools
 import math
-import os
 
 import torch
 
-from ._lib import check, dptr, load_library, parse_defines, parse_header, stream
+from ._lib import SideLibrary, dptr, position_mask as _mask, stream, structures
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libprd_quality.so")
-HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "prd_quality.h")
-
-with open(HEADER_PATH) as _f:
-    _HEADER = _f.read()                         # the header is the only statement of the C ABI and of its constants
-ENTRIES = parse_header(_HEADER, "include/prd_quality.h")
-_DEFINES = parse_defines(_HEADER, "PRD_QUALITY_")
-
-ABI_VERSION = 100           # include/prd_quality.h PRD_QUALITY_VERSION this binding is written against
-MAX_N = _DEFINES["MAX_N"]
-MAX_S = _DEFINES["MAX_S"]
+_BINDING = SideLibrary("quality", 100, "at most {MAX_N} positions per structure (PRD_QUALITY_MAX_N) and {MAX_S} structures per call")
+ENTRIES, _DEFINES, ABI_VERSION = _BINDING.entries, _BINDING.defines, _BINDING.version      # 100: include/prd_quality.h PRD_QUALITY_VERSION
+lib, _check = _BINDING.lib, _BINDING.check
+MAX_N, MAX_S = _DEFINES["MAX_N"], _DEFINES["MAX_S"]
+_structures = functools.partial(structures, runs="the quality scores run", letter="S", bounds=_BINDING)
 THRESHOLDS = (0.5, 1.0, 2.0, 4.0)       # Angstrom; fixed in the kernel, stated here for readers and for the tests
 
 # the documented defaults of ``assess`` (Angstrom); each is a keyword of it
@@ -38,20 +31,6 @@ BOND_RANGE, CA_STEP, CA_STEP_TOLERANCE, POCKET = (0.9, 2.1), 3.8, 0.5, 8.0
 LDDT_RADIUS, LDDT_PLI_RADIUS = 15.0, 10.0
 SCALAR_COLUMNS = ("ca_clashes", "ligand_clashes", "ligand_self_clashes", "ligand_bond_outliers", "chain_breaks", "pocket_size",
                   "lddt_ca", "lddt_pli", "lddt_ligand", "pocket_recall")      # the column order of sample_quality.txt (those present)
-
-_lib = None
-
-
-def lib():
-    """The loaded library; raises RuntimeError (never falls back) when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = load_library(LIB_PATH, ENTRIES, "prd_quality_version", ABI_VERSION, "--quality")
-    return _lib
-
-
-def _check(code: int, what: str):
-    check(code, what, _DEFINES, "PRD_QUALITY_", f"at most {MAX_N} positions per structure (PRD_QUALITY_MAX_N) and {MAX_S} structures per call")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -68,32 +47,6 @@ class LDDT:
 class Contacts:
     count: torch.Tensor             # [S] int32
     nearest: torch.Tensor           # [S,N] float32 Angstrom, +inf where a row has no partner or is outside A
-
-
-def _structures(t, name):
-    """[S,N,3] fp32 device tensor whose last stride is 1 (made so if it is not); returns (tensor, structure stride, row stride)"""
-    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{name} must be a [S,N,3] tensor, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32, got {t.dtype}")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: the quality scores run on the GPU only (got a CPU tensor); there is no CPU fallback")
-    if t.shape[1] > MAX_N or t.shape[0] > MAX_S:
-        raise ValueError(f"{name}: {t.shape[0]} structures of {t.shape[1]} positions, at most {MAX_S} structures (PRD_QUALITY_MAX_S) of "
-                         f"{MAX_N} positions (PRD_QUALITY_MAX_N) are supported")
-    if t.stride(2) != 1 or t.stride(1) < 3 or t.stride(0) < 0:
-        t = t.contiguous()
-    return t, t.stride(0), t.stride(1)
-
-
-def _mask(mask, name, N, device):
-    if not torch.is_tensor(mask) or mask.shape != (N,):
-        raise ValueError(f"{name} must be a [{N}] tensor, got {tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__}")
-    if mask.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32 (0 / 1), got {mask.dtype}")
-    if mask.device != device:
-        raise ValueError(f"{name} is on {mask.device}, the structures on {device}")
-    return mask.contiguous()
 
 
 def _bound(value, name):

@@ -7,38 +7,17 @@ Everything runs on the current stream with no host synchronisation.  HIP only: a
 from __future__ import annotations
 
 import dataclasses
-import os
+import functools
 
 import torch
 
-from ._lib import check, dptr, load_library, parse_defines, parse_header, stream
-from .align import _mask, _structures
+from ._lib import SideLibrary, dptr, position_mask, stream, structures
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libprd_tmalign.so")
-HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "prd_tmalign.h")
-
-with open(HEADER_PATH) as _f:
-    _HEADER = _f.read()                         # the header is the only statement of the C ABI and of its constants
-ENTRIES = parse_header(_HEADER, "include/prd_tmalign.h")
-_DEFINES = parse_defines(_HEADER, "PRD_TMALIGN_")
-
-ABI_VERSION = 100           # include/prd_tmalign.h PRD_TMALIGN_VERSION this binding is written against
+_BINDING = SideLibrary("tmalign", 100, "at most {MAX_N} positions per structure (PRD_TMALIGN_MAX_N)")
+ENTRIES, _DEFINES, ABI_VERSION = _BINDING.entries, _BINDING.defines, _BINDING.version      # 100: include/prd_tmalign.h PRD_TMALIGN_VERSION
+lib, _check = _BINDING.lib, _BINDING.check
 MAX_N = _DEFINES["MAX_N"]
-
-_lib = None
-
-
-def lib():
-    """The loaded library; raises RuntimeError (never falls back) when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = load_library(LIB_PATH, ENTRIES, "prd_tmalign_version", ABI_VERSION, "--tmalign")
-    return _lib
-
-
-def _check(code: int, what: str):
-    check(code, what, _DEFINES, "PRD_TMALIGN_", f"at most {MAX_N} positions per structure (PRD_TMALIGN_MAX_N)")
+_structures = functools.partial(structures, runs="the alignment runs", letter="K")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -68,7 +47,7 @@ def align(x, ref, mask, ref_mask, mirror: bool = True) -> StructuralAlignment:
         raise ValueError(f"ref is on {y[0].device}, x on {x[0].device}")
     R, Ny = y[0].shape[:2]
     dev = x[0].device
-    mx, my = _mask(mask, Nx, dev), _mask(ref_mask, Ny, dev)
+    mx, my = position_mask(mask, "mask", Nx, dev), position_mask(ref_mask, "mask", Ny, dev)
     if max(Nx, Ny) > MAX_N:
         raise ValueError(f"align: {max(Nx, Ny)} positions per structure, at most {MAX_N} (PRD_TMALIGN_MAX_N) are supported")
     L = lib()

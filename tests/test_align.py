@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import align_ref as AR
+from no_host_sync import run_without_host_sync
 from protein_redesign_amd import align
 from protein_redesign_amd import pipeline as PL
 
@@ -245,20 +246,6 @@ def test_limits():
         align.superimpose(x, x[0], torch.ones(12, device=DEV), mode="gdt")
 
 
-def _sync_debug_mode_is_honoured():
-    """Does this torch build raise on a synchronising call under set_sync_debug_mode("error")?"""
-    x = torch.ones(1, device=DEV)
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
-        x.item()
-    except RuntimeError:
-        return True
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    return False
-
-
 def test_no_host_synchronisation():
     """Mechanism as in tests/test_redesign_region.py: ``set_sync_debug_mode("error")`` where this torch build honours it (probed with an
     ``.item()``), otherwise a single-stream capture, where a synchronisation fails the capture.  Which one ran is printed."""
@@ -271,21 +258,7 @@ def test_no_host_synchronisation():
     def work():
         return align.superimpose(x, ref, m), align.pairwise_tm(x, m), align.apply(x, torch.eye(3, device=DEV).expand(5, 3, 3), torch.zeros(5, 3, device=DEV))
     warm = work()                                       # library, allocator
-    torch.cuda.synchronize()
-    if _sync_debug_mode_is_honoured():
-        print("\nmechanism: torch.cuda.set_sync_debug_mode('error')")
-        torch.cuda.set_sync_debug_mode("error")
-        try:
-            got = work()
-        finally:
-            torch.cuda.set_sync_debug_mode("default")
-    else:
-        print("\nmechanism: stream capture (set_sync_debug_mode is not honoured by this build)")
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            got = work()
-        graph.replay()
-    torch.cuda.synchronize()
+    got = run_without_host_sync(work)
     assert torch.equal(got[0].tm, warm[0].tm) and torch.equal(got[1], warm[1]) and torch.equal(got[0].rotation, warm[0].rotation)
     assert torch.equal(got[2], x)                       # identity transform: t + x @ 1 with t = 0 is x bit for bit
 

@@ -12,6 +12,7 @@ from conftest import ROOT
 from protein_redesign_amd import _lib, build
 from protein_redesign_amd import pipeline as PL
 from protein_redesign_amd.synthetic import synthetic_sample
+from sample_stubs import _NoDevice, _Stub, header_entries
 from test_binding_cpu import Recorder, exported
 
 LENGTHS = [3, 4, 5, 21, 22, 63, 64, 65, 130, 257, 1025]
@@ -85,13 +86,8 @@ def test_seed_filter_leaves_the_default_search_alone_and_decisive_seeds_exist():
 
 # ---- header, build, export list ---------------------------------------------------------------------------------------------------
 
-def header_entries():
-    with open(os.path.join(ROOT, "include", "prd_align.h")) as f:
-        return _lib.parse_header(f.read())
-
-
 def test_header_parses_with_the_derived_binding():
-    e = header_entries()
+    e = header_entries("align")
     assert sorted(e) == ["prd_align_apply", "prd_align_superimpose", "prd_align_version", "prd_align_workspace_bytes"]
     assert all(x.inject is None for x in e.values())            # no parameter is an injected word
     assert e["prd_align_workspace_bytes"].restype is _lib.cz and len(e["prd_align_superimpose"].argtypes) == 21
@@ -104,7 +100,7 @@ def test_header_parses_with_the_derived_binding():
 def test_build_align_compiles_exports_the_header_and_is_incremental(monkeypatch):
     lib = build.build_align(verbose=False)
     assert lib == build.LIB_ALIGN == os.path.join(ROOT, "protein_redesign_amd", "libprd_align.so") and os.path.exists(lib)
-    assert exported(lib) == set(header_entries())
+    assert exported(lib) == set(header_entries("align"))
     rec = Recorder(execute=True)
     rec.install(monkeypatch)
     assert build.build_align(verbose=False) == lib
@@ -176,20 +172,6 @@ def test_host_argument_checks_of_the_python_side():
 
 
 # ---- pipeline.generate_samples(align_to=...) ---------------------------------------------------------------------------------------
-
-class _NoDevice:
-    def __getattr__(self, name):
-        raise AssertionError(f"the model was touched ({name}) before the input was checked")
-
-
-class _Stub:
-    """a model whose samples are a function of the keyed noise source alone"""
-    device = torch.device("cpu")
-
-    def sample(self, batch, sources, redesign=None):
-        n = batch["atom_mask"].shape[1]
-        return (torch.stack([torch.randn(n, 3, generator=s.g) for s in sources]), torch.stack([torch.randn(n, 21, generator=s.g) for s in sources]))
-
 
 def test_align_to_input_is_refused_without_coordinates_before_the_model_is_touched():
     lig = {k: v for k, v in synthetic_sample(5, 9, esm_dim=16, seed=8).items() if k.startswith(("atom_", "bond_")) or k == "num_atoms"}

@@ -12,6 +12,7 @@ from conftest import ROOT
 from protein_redesign_amd import _lib, build
 from protein_redesign_amd import pipeline as PL
 from protein_redesign_amd.synthetic import synthetic_sample
+from sample_stubs import _NoDevice, _Stub, header_entries
 from test_binding_cpu import Recorder, exported
 
 HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
@@ -93,14 +94,9 @@ def test_the_inputs_keep_the_ambiguous_pairs_far_below_the_cap():
 
 # ---- header, build, export list ---------------------------------------------------------------------------------------------------
 
-def header_entries():
-    with open(os.path.join(ROOT, "include", "prd_quality.h")) as f:
-        return _lib.parse_header(f.read())
-
-
 def test_header_parses_with_the_derived_binding():
     from protein_redesign_amd import align, quality, tmalign
-    e = header_entries()
+    e = header_entries("quality")
     assert sorted(e) == ["prd_quality_contacts", "prd_quality_lddt", "prd_quality_version"]
     assert all(x.inject is None and x.restype is _lib.ci for x in e.values())
     assert len(e["prd_quality_lddt"].argtypes) == 13 and len(e["prd_quality_contacts"].argtypes) == 12
@@ -135,7 +131,7 @@ def test_side_libs_has_the_entry_and_the_other_builds_issue_what_they_issued(mon
 def test_forced_cross_compile_exports_the_header_and_a_second_build_is_incremental(monkeypatch):
     lib = build.build_quality(force=True, verbose=False)
     assert lib == build.LIB_QUALITY and os.path.exists(lib)
-    assert exported(lib) == set(header_entries())
+    assert exported(lib) == set(header_entries("quality"))
     rec = Recorder(execute=True)
     rec.install(monkeypatch)
     assert build.build_quality(verbose=False) == lib
@@ -198,20 +194,6 @@ def test_host_argument_checks_of_the_python_side():
 
 
 # ---- pipeline.generate_samples(assess=...) -----------------------------------------------------------------------------------------
-
-class _NoDevice:
-    def __getattr__(self, name):
-        raise AssertionError(f"the model was touched ({name}) before the input was checked")
-
-
-class _Stub:
-    """a model whose samples are a function of the keyed noise source alone"""
-    device = torch.device("cpu")
-
-    def sample(self, batch, sources, redesign=None):
-        n = batch["atom_mask"].shape[1]
-        return (torch.stack([torch.randn(n, 3, generator=s.g) for s in sources]), torch.stack([torch.randn(n, 21, generator=s.g) for s in sources]))
-
 
 def test_assess_input_is_refused_without_coordinates_before_the_model_is_touched():
     lig = {k: v for k, v in synthetic_sample(5, 9, esm_dim=16, seed=8).items() if k.startswith(("atom_", "bond_")) or k == "num_atoms"}

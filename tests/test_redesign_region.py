@@ -19,6 +19,7 @@ import torch
 
 import prd_oracle as O
 from conftest import rel_l2
+from no_host_sync import run_without_host_sync
 from protein_redesign_amd import _lib, masking, ops
 from protein_redesign_amd.constants import make_args
 from protein_redesign_amd.diffusion_model import ProteinReDiffModel
@@ -135,20 +136,6 @@ def test_entry_refuses_before_any_launch():
 # ---------------------------------------------------------------------------------------------------
 # 2. prepare_batch
 # ---------------------------------------------------------------------------------------------------
-def _sync_debug_mode_is_honoured():
-    """Does this torch build raise on a synchronising call under set_sync_debug_mode("error")?"""
-    x = torch.ones(1, device=DEV)
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
-        x.item()
-    except RuntimeError:
-        return True
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    return False
-
-
 def restated_spec_masks(batch, kind, value):
     """(extra, inv) of a spec on a CPU batch through the restatement; the pocket kinds assert the fixture's boundary gap."""
     rm = batch["residue_mask"]
@@ -193,21 +180,7 @@ def test_prepare_batch_with_a_spec_equals_the_restatement_and_does_not_synchroni
     model.prepare_batch(batch_to(clone_batch(batch), DEV), redesign=spec)      # warm: library, allocators
     d = batch_to(clone_batch(batch), DEV)
     counter = model._sample_counter
-    torch.cuda.synchronize()
-    if _sync_debug_mode_is_honoured():
-        print("\nmechanism: torch.cuda.set_sync_debug_mode('error')")
-        torch.cuda.set_sync_debug_mode("error")
-        try:
-            got = model.prepare_batch(d, redesign=spec)
-        finally:
-            torch.cuda.set_sync_debug_mode("default")
-    else:
-        print("\nmechanism: stream capture (set_sync_debug_mode is not honoured by this build)")
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            got = model.prepare_batch(d, redesign=spec)
-        graph.replay()
-    torch.cuda.synchronize()
+    got = run_without_host_sync(lambda: model.prepare_batch(d, redesign=spec))
     assert model._sample_counter == counter == 0        # the noise sources are not consulted for the mask
     for k in ("residue_extra_mask", "residue_inv_extra_mask", "residue_type_masked", "residue_one_hot", "residue_esm", "x",
               "residue_and_atom_mask"):

@@ -23,6 +23,7 @@ from protein_redesign_amd.constants import make_args
 from protein_redesign_amd.diffusion_model import ProteinReDiffModel
 from protein_redesign_amd.masking import Redesign
 from protein_redesign_amd.synthetic import synthetic_batch, synthetic_sample
+from sample_stubs import _NoDevice
 
 GAP = 1e-3          # Angstrom, in float64, at every decision boundary: coordinates within +-50 make fp32 distances good to ~1e-5
 MID_RADIUS = 14.0   # Angstrom: a radius that cuts through the residues of every fixture below
@@ -257,13 +258,6 @@ def test_model_refuses_a_spec_under_training_mode_and_reaches_the_operator_other
     assert float(pb["residue_one_hot"][:, [4, 5]].abs().sum()) == 0 and float(pb["residue_esm"][:, [4, 5]].abs().sum()) == 0
     with pytest.raises(ValueError, match="shape"):
         m.prepare_batch(synthetic_batch([(3, 9)], esm_dim=16, seed=5), redesign=Redesign.positions(torch.ones(5)))
-
-
-class _NoDevice:
-    """A model stand-in whose every attribute access fails: generate_samples must refuse before it touches the model."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"the model was touched ({name}) before the input was checked")
 
 
 def test_pipeline_refuses_a_pocket_without_coordinates():

@@ -15,7 +15,7 @@ from conftest import ROOT
 from protein_redesign_amd import _lib, build
 from protein_redesign_amd import pipeline as PL
 from protein_redesign_amd.synthetic import synthetic_sample
-from test_align_cpu import _NoDevice, _Stub
+from sample_stubs import _NoDevice, _Stub, header_entries
 from test_binding_cpu import Recorder, exported
 
 HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
@@ -80,13 +80,8 @@ def test_yardstick_short_chains_and_equal_length_identity():
 
 # ---- header, build, export list ---------------------------------------------------------------------------------------------------
 
-def header_entries():
-    with open(os.path.join(ROOT, "include", "prd_tmalign.h")) as f:
-        return _lib.parse_header(f.read())
-
-
 def test_header_parses_with_the_derived_binding():
-    e = header_entries()
+    e = header_entries("tmalign")
     assert sorted(e) == ["prd_tmalign_align", "prd_tmalign_version", "prd_tmalign_workspace_bytes"]
     assert all(x.inject is None for x in e.values())
     assert e["prd_tmalign_workspace_bytes"].restype is _lib.cz and len(e["prd_tmalign_workspace_bytes"].argtypes) == 5
@@ -99,7 +94,7 @@ def test_header_parses_with_the_derived_binding():
 def test_build_tmalign_compiles_exports_the_header_and_is_incremental(monkeypatch):
     lib = build.build_tmalign(verbose=False)
     assert lib == build.LIB_TMALIGN == os.path.join(ROOT, "protein_redesign_amd", "libprd_tmalign.so") and os.path.exists(lib)
-    assert exported(lib) == set(header_entries())
+    assert exported(lib) == set(header_entries("tmalign"))
     rec = Recorder(execute=True)
     rec.install(monkeypatch)
     assert build.build_tmalign(verbose=False) == lib

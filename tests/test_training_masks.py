@@ -14,6 +14,7 @@ import torch
 
 import prd_oracle as O
 from conftest import rel_l2
+from no_host_sync import run_without_host_sync
 from protein_redesign_amd import masking, ops
 from protein_redesign_amd.constants import make_args
 from protein_redesign_amd.diffusion_model import ProteinReDiffModel
@@ -275,20 +276,6 @@ def test_sample_under_training_mode_matches_the_oracle(name, monkeypatch):
 # ---------------------------------------------------------------------------------------------------
 # 4. no host synchronisation
 # ---------------------------------------------------------------------------------------------------
-def _sync_debug_mode_is_honoured():
-    """Does this torch build raise on a synchronising call under set_sync_debug_mode("error")?"""
-    x = torch.ones(1, device=DEV)
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
-        x.item()
-    except RuntimeError:
-        return True
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
-    return False
-
-
 @pytest.mark.parametrize("rt", [0.1, 0.4, 0.9])
 def test_training_mode_prepare_batch_does_not_synchronise(rt):
     """Mechanism: ``torch.cuda.set_sync_debug_mode("error")`` where this torch build honours it on ROCm (probed with an
@@ -304,21 +291,7 @@ def test_training_mode_prepare_batch_does_not_synchronise(rt):
     want = {k: v.clone() for k, v in want.items() if torch.is_tensor(v)}
     d = batch_to(clone_batch(batch), DEV)
     draws = masking.MaskDraws(recorded=rec)
-    torch.cuda.synchronize()
-    if _sync_debug_mode_is_honoured():
-        print("\nmechanism: torch.cuda.set_sync_debug_mode('error')")
-        torch.cuda.set_sync_debug_mode("error")
-        try:
-            got = model.prepare_batch(d, mask_draws=draws)
-        finally:
-            torch.cuda.set_sync_debug_mode("default")
-    else:
-        print("\nmechanism: stream capture (set_sync_debug_mode is not honoured by this build)")
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            got = model.prepare_batch(d, mask_draws=draws)
-        graph.replay()
-    torch.cuda.synchronize()
+    got = run_without_host_sync(lambda: model.prepare_batch(d, mask_draws=draws))
     for k in ("residue_extra_mask", "residue_inv_extra_mask", "residue_type_masked", "residue_one_hot", "x", "residue_esm_tokens"):
         assert torch.equal(got[k], want[k]), k
     assert int(got["residue_inv_extra_mask"].sum()) == (0 if rt >= 0.5 else int(want["residue_inv_extra_mask"].sum()))
