@@ -6,15 +6,22 @@ and enqueues HIP kernels on the current torch stream.  Weight tensors are passed
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes
 import math
 import os
-from typing import Mapping, Optional, Tuple
+from typing import Mapping, NamedTuple, Optional, Tuple
 
 import torch
 
 from ._lib import _DEFINES, _TUNE_SHIFT, PrdGemm, arithmetic, check, dptr, lib, stream
 
 F32 = torch.float32
+
+
+def _device_index(device) -> int:
+    idx = torch.device(device).index
+    return idx if idx is not None else torch.cuda.current_device()
 
 
 _QUEUES = {}
@@ -24,10 +31,9 @@ def task_queue(device) -> int:
     """Device pointer of the per-device task-queue counters (zero-initialised int32s, see prd_hip.h), or 0 = static
     wave-major task order.  The static order measured faster for every row kernel at the bench shape,
     so the queue is opt-in: PRD_TASK_QUEUE=1."""
-    import os
     if not os.environ.get("PRD_TASK_QUEUE"):
         return 0
-    key = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
+    key = _device_index(device)
     q = _QUEUES.get(key)
     if q is None:
         q = _QUEUES[key] = torch.zeros(256, dtype=torch.int32, device=f"cuda:{key}")
@@ -42,13 +48,11 @@ class SideStream:
     of small kernels they take off the critical path), so it is OFF unless ``PRD_SIDE_STREAM=1``."""
 
     def __init__(self, device):
-        import os
         self.enabled = os.environ.get("PRD_SIDE_STREAM", "0") == "1"
         self.stream = torch.cuda.Stream(device=device) if self.enabled else None
 
     def fork(self):
         """Context manager: launches inside run on the side stream, ordered after everything enqueued so far on the current one."""
-        import contextlib
         if not self.enabled:
             return contextlib.nullcontext()
         self.stream.wait_stream(torch.cuda.current_stream())
@@ -104,7 +108,6 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, *, a_off=0, b_off=0, c_off=0, G1=1,
     g.mul_pos = int(mul_pos)
     g.a_amax = (a_amax if isinstance(a_amax, int) else dptr(a_amax, torch.int32)) if a_amax is not None else None
     g.arith = lib().prd_get_gemm_mode() | (lib().prd_get_tune() << _TUNE_SHIFT)
-    import ctypes
     code = lib().prd_gemm(ctypes.byref(g), stream())
     if unsupported_ok and code == _DEFINES["ERR_UNSUPPORTED"]:
         return None
@@ -121,7 +124,7 @@ def gemm_workspace(device, nbytes: int) -> torch.Tensor:
     capturing graph's own memory pool (the allocator reuses it between the GEMMs of the captured step, which are ordered on the
     capture stream, and the graph keeps the addresses alive exactly as long as it exists; a cached buffer would outlive the graph
     it was carved from)."""
-    dev = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
+    dev = _device_index(device)
     n = max(1, (nbytes + 3) // 4)
     if torch.cuda.is_current_stream_capturing():
         return torch.empty(n, device=f"cuda:{dev}", dtype=F32)
@@ -347,7 +350,6 @@ def tri_mul_chain_supported(N: int, P: int) -> bool:
 def tri_mul_chain_(pair, mask, wts_outgoing, wts_incoming, ws=None) -> torch.Tensor:
     """pair += TriMul_outgoing(pair); pair += TriMul_incoming(pair), in place (modules.py:336-337), with the output stage of the
     first and the projection stage of the second fused into one row pass (prd_tri_mul_chain; gemm mode 1)."""
-    import ctypes
     b, N, _, P = pair.shape
     nbytes = workspace_bytes("tri_mul", b, N, 0, P)
     if ws is None:
@@ -372,7 +374,7 @@ def tri_attn_pair_supported(N: int, P: int) -> bool:
 
 def tri_attn_pair_bar(device) -> torch.Tensor:
     """The 32 uint32 (counters, memberships, [1] = timeout flag) of prd_tri_attn_pair on ``device``: zeroed by every call, stream-ordered."""
-    key = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
+    key = _device_index(device)
     bar = _PAIR_BARS.get(key)
     if bar is None:
         bar = _PAIR_BARS[key] = torch.zeros(32, dtype=torch.int32, device=f"cuda:{key}")
@@ -383,7 +385,6 @@ def tri_attn_pair_(pair, mask, wts_start, wts_end, H: int, c: int, og=None) -> t
     """pair += TriangleAttention_starting(pair) in place, then og [b,N,N,64] = the gated head outputs of the ENDING attention on the
     updated pair (its output projection rides in block_tail_): modules.py:338-339 as ONE persistent launch (prd_tri_attn_pair).
     wts_start = (q.w, k.w, v.w, gate.w, gate.b, out.w, out.b), wts_end = (q.w, k.w, v.w, gate.w, gate.b)."""
-    import ctypes
     b, N, _, P = pair.shape
     if og is None:
         og = torch.empty(b, N, N, 64, device=pair.device, dtype=F32)
@@ -448,59 +449,59 @@ def tri_mul_backward(dy, pair, mask, wts, *, incoming: bool, ws=None):
 
 
 TRI_ATTN_BWD_V2 = os.environ.get("PRD_TRI_ATTN_BWD_V2", "1") != "0"      # 0: the fp32-MFMA backward core in split-16 mode too (A/B measurements)
-TRI_ATTN_BWD_TUNED_MAX_N = 416      # longest row of the two 4 x 16 backward cores (their LDS layout; training.TRI_ATTN_BWD_MAX_N)
+# longest row of the two 4 x 16 backward cores: q, k, v, do of a row (padded to 32) and the head's weights in LDS, 156 KB (BASELINE draws N <= 384)
+TRI_ATTN_BWD_TUNED_MAX_N = 416
+# core: the backward core, "v2" (prd_tri_attn_bwd_core_v2) | "tuned" (prd_tri_attn_bwd_core) | "heads" (prd_tri_attn_bwd_core_heads);
+# keeps_lse: the forward core leaves the softmax statistics of its queries for it; forward: "core" (tri_attn_core) | "core_heads"
+TriAttnBwdPlan = NamedTuple("TriAttnBwdPlan", [("core", str), ("keeps_lse", bool), ("forward", str)])
+
+
+def tri_attn_bwd_plan(N: int, P: int, H: int, c: int) -> TriAttnBwdPlan:
+    """What the triangle-attention backward of this shape runs (long 4 x 16 rows: the general core finds the statistics).  ``core`` and
+    ``keeps_lse`` read the arithmetic in force: they hold for the backward where that is the backward's arithmetic (training._pin_arithmetic)."""
+    if not default_head_layout(H, c):
+        return TriAttnBwdPlan("heads", True, "core_heads")
+    if N > TRI_ATTN_BWD_TUNED_MAX_N:
+        return TriAttnBwdPlan("heads", False, "core")
+    v2 = lib().prd_get_gemm_mode() == 1 and TRI_ATTN_BWD_V2 and lib().prd_tri_attn_bwd_core_v2_supported(N, P) == 1
+    return TriAttnBwdPlan("v2" if v2 else "tuned", tri_attn_lse_supported(N, P), "core")
+
+
+def tri_attn_core_for_bwd(pair, mask, wts, H: int, c: int, *, ending: bool, plan: TriAttnBwdPlan, keep_lse: bool = True):
+    """(og, lse) of the plan's forward core: the gated head outputs and, where the plan keeps them and ``keep_lse``, the statistics (else None)."""
+    b, N = pair.shape[:2]
+    lse = torch.empty(b * N, H, N, 2, device=pair.device, dtype=F32) if keep_lse and plan.keeps_lse else None
+    return (tri_attn_core if plan.forward == "core" else tri_attn_core_heads)(pair, mask, wts, H, c, ending=ending, lse=lse), lse
 
 
 def tri_attn_backward(dy, pair, mask, wts, H: int, c: int, *, ending: bool, og=None, lse=None, residual: bool = False):
     """Gradients of the TriangleAttention update (ops.tri_attn with residual=False; ``residual``: of pair + update, i.e. dy is added
-    to the pair gradient) with respect to ``pair`` and its seven weight
-    tensors on the hand-written backward (csrc/prd_bwd.hip): out-projection backward (row GEMM) -> attention core backward per
-    (row, head) -> projections backward (row GEMM) -> LayerNorm backward.  Weight gradients: slab reductions over all N^2 rows
-    (linear_wgrad).  The core: 4 x 16 at N <= TRI_ATTN_BWD_TUNED_MAX_N on the two tuned cores (prd_tri_attn_bwd_core, _v2), every
-    other layout and every longer row on the general core (prd_tri_attn_bwd_core_heads: no row limit)."""
-    wq, wk, wv, wg, bg, wo, bo = wts
+    to the pair gradient) with respect to ``pair`` and its seven weight tensors on the hand-written backward (csrc/prd_bwd.hip):
+    out-projection backward (row GEMM) -> attention core backward per (row, head), the core of tri_attn_bwd_plan -> projections backward
+    (row GEMM) -> LayerNorm backward.  Weight gradients: slab reductions over all N^2 rows (linear_wgrad)."""
     b, N, _, P = pair.shape
     HC = H * c
-    dev = pair.device
-    dy = dy.contiguous()
-    tuned = default_head_layout(H, c) and N <= TRI_ATTN_BWD_TUNED_MAX_N
-    if og is None and tuned:                                                                    # forward recompute: gated head outputs
-        lse = torch.empty(b * N, H, N, 2, device=dev, dtype=F32) if tri_attn_lse_supported(N, P) else None
-        og = tri_attn_core(pair, mask, (wq, wk, wv, wg, bg), H, c, ending=ending, lse=lse)
-    elif og is None and default_head_layout(H, c):      # long 4 x 16 rows: the tuned long-row / chunked forward keeps no statistics
-        lse = None
-        og = tri_attn_core(pair, mask, (wq, wk, wv, wg, bg), H, c, ending=ending)
-    elif og is None:
-        lse = torch.empty(b * N, H, N, 2, device=dev, dtype=F32)
-        og = tri_attn_core_heads(pair, mask, (wq, wk, wv, wg, bg), H, c, ending=ending, lse=lse)
-    dog = pair_linear(dy.view(-1, P), wo.t())                                                     # d og = dy W_o
-    if dog is None:                 # general core: fp32 MFMA (a split-16 GEMM loses training-scale gradients to the fp16 subnormal range)
-        with arithmetic(None if tuned else 0):
-            dog = linear(dy, wo.t().contiguous())
-    dqkvg = torch.empty(b, N, N, 4, HC, device=dev, dtype=F32)
-    x = None
-    if not tuned:
-        x = torch.empty_like(pair)                                                                # LN(pair), left by the core
-        tri_attn_bwd_core_heads(dog, og, pair, mask, (wq, wk, wv, wg, bg), H, c, ending=ending, lse=lse, x_out=x, dqkvg=dqkvg)
-    elif lib().prd_get_gemm_mode() == 1 and TRI_ATTN_BWD_V2 and lib().prd_tri_attn_bwd_core_v2_supported(N, P) == 1:
-        x = torch.empty_like(pair)                                                                # LN(pair), left by the core
-        check(lib().prd_tri_attn_bwd_core_v2(dptr(dqkvg), dptr(dog), dptr(og), dptr(pair), dptr(mask), dptr(wq), dptr(wk), dptr(wv), dptr(wg),
-                                             dptr(bg), dptr(lse) if lse is not None else None, dptr(x), int(ending), b, N, P, H, c, stream()),
-              "prd_tri_attn_bwd_core_v2")
+    dy2 = dy.contiguous().view(-1, P)
+    plan = tri_attn_bwd_plan(N, P, H, c)
+    if og is None:                                                                                # forward recompute: gated head outputs
+        og, lse = tri_attn_core_for_bwd(pair, mask, wts[:5], H, c, ending=ending, plan=plan)
+    arith = 0 if plan.core == "heads" else None     # general core: fp32 MFMA (a split-16 GEMM loses training-scale gradients to the fp16 subnormals)
+    dog = rows_linear(dy2, wts[5], transposed=True, fallback_arith=arith)                         # d og = dy W_o
+    dqkvg = torch.empty(b, N, N, 4, HC, device=pair.device, dtype=F32)
+    x = torch.empty_like(pair) if plan.core != "tuned" else None                                  # LN(pair), left by the core
+    if plan.core == "heads":
+        tri_attn_bwd_core_heads(dog, og, pair, mask, wts[:5], H, c, ending=ending, lse=lse, x_out=x, dqkvg=dqkvg)
+    elif plan.core == "v2":
+        check(lib().prd_tri_attn_bwd_core_v2(dptr(dqkvg), dptr(dog), dptr(og), dptr(pair), dptr(mask), *map(dptr, wts[:5]), dptr(lse), dptr(x),
+                                             int(ending), b, N, P, H, c, stream()), "prd_tri_attn_bwd_core_v2")
     else:
-        check(lib().prd_tri_attn_bwd_core(dptr(dqkvg), dptr(dog), dptr(pair), dptr(mask), dptr(wq), dptr(wk), dptr(wv), dptr(wg), dptr(bg),
-                                          int(ending), b, N, P, H, c, stream()), "prd_tri_attn_bwd_core")
-    wcat = torch.cat([wq, wk, wv, wg], dim=0)                                                     # [4 HC, P]
-    dxn = pair_linear(dqkvg.view(-1, 4 * HC), wcat.t())                                          # gradient of LN(pair)
-    if dxn is None:
-        with arithmetic(None if tuned else 0):
-            dxn = linear(dqkvg.view(b, N, N, 4 * HC), wcat.t().contiguous())
-    dpair = torch.empty_like(pair)
-    check(lib().prd_ln_rows_bwd(dptr(dpair), dptr(dxn), dptr(pair), dptr(dy) if residual else None, b * N * N, P, stream()), "prd_ln_rows_bwd")
+        check(lib().prd_tri_attn_bwd_core(dptr(dqkvg), dptr(dog), dptr(pair), dptr(mask), *map(dptr, wts[:5]), int(ending), b, N, P, H, c, stream()),
+              "prd_tri_attn_bwd_core")
+    d2 = dqkvg.view(-1, 4 * HC)                                                                   # (W_q | W_k | W_v | W_g stacked: [4 HC, P])
+    dxn = rows_linear(d2, torch.cat(wts[:4], dim=0), transposed=True, fallback_arith=arith)       # gradient of LN(pair)
+    dpair = ln_rows_bwd(dxn, pair.view(-1, P), res=dy2 if residual else None).view_as(pair)
     x = (x if x is not None else layer_norm(pair.contiguous())).view(-1, P)
-    d2 = dqkvg.view(-1, 4, HC)
-    dy2 = dy.view(-1, P)
-    dw4, db4 = linear_wgrad(dqkvg.view(-1, 4 * HC), x, bias=True)                                # d W_q | W_k | W_v | W_g stacked [4 HC, P]
+    dw4, db4 = linear_wgrad(d2, x, bias=True)                                                     # d W_q | W_k | W_v | W_g stacked [4 HC, P]
     grads = (dw4[:HC], dw4[HC:2 * HC], dw4[2 * HC:3 * HC], dw4[3 * HC:], db4[3 * HC:], *linear_wgrad(dy2, og.view(-1, HC), bias=True))
     return dpair, grads
 
@@ -561,6 +562,24 @@ def ln_rows_bwd(dy2: torch.Tensor, x2: torch.Tensor, res: Optional[torch.Tensor]
     dx = torch.empty_like(x2)
     check(lib().prd_ln_rows_bwd(dptr(dx), dptr(dy2), dptr(x2), dptr(res), rows, Cn, stream()), "prd_ln_rows_bwd")
     return dx
+
+
+def rows_linear(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, transposed: bool = False, ln_in: bool = False,
+                xn_out: Optional[torch.Tensor] = None, act: int = 0, relu_mask: Optional[torch.Tensor] = None, fallback_arith=None) -> torch.Tensor:
+    """act(LN?(x2) w^T + bias) as [rows, OUT]: ``pair_linear`` where the row kernel serves the call, else the same through ``linear``, that
+    fallback alone inside ``arithmetic(fallback_arith)`` (None: a context that does nothing on entry and exit).  ``transposed``: multiply
+    by w as [K, OUT] (w.t(); a contiguous copy of it for the GEMM)."""
+    y = pair_linear(x2, w.t() if transposed else w, bias, ln_in=ln_in, xn_out=xn_out, act=act, relu_mask=relu_mask)
+    if y is None:
+        with arithmetic(fallback_arith):
+            y = linear(x2, w.t().contiguous() if transposed else w, bias, act=act, ln_a=ln_in, ln_a_out=xn_out, relu_mask=relu_mask)
+    return y
+
+
+def ln_relu_rows(x2: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor):
+    """(h, xn) = (relu(W1 LN(x2) + b1), LN(x2)): the forward recompute of a LayerNorm-linear-ReLU, the normalised rows on the side."""
+    xn = torch.empty_like(x2)
+    return rows_linear(x2, w1, b1, ln_in=True, xn_out=xn, act=1), xn
 
 
 def pair_bias_bwd(dbias: torch.Tensor, wf: torch.Tensor, pair: torch.Tensor):
@@ -626,7 +645,6 @@ def embed_wgrad_multi(idxs, dy2: torch.Tensor, cards, scales=None):
     """The gradients of several small tables looked up at the same rows, in one pass over dy2 [rows, C] (prd_embed_wgrad_multi):
     ``idxs`` int64 [rows] each, ``cards`` their table sizes, ``scales`` optional per-set row factors [rows] (entries may be None).
     Returns the list of [card_k, C] gradients."""
-    import ctypes
     K = len(idxs)
     rows, Cn = dy2.shape
     total = int(sum(cards))

@@ -11,6 +11,7 @@ fp32 throughout (the reference trains under fp16 autocast, train.py:37; parity i
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 
@@ -42,6 +43,7 @@ INPUT_STAGE_BWD = os.environ.get("PRD_INPUT_STAGE_BWD", "1") != "0"     # 0: the
 FUSED_RESIDUAL = os.environ.get("PRD_TRAIN_FUSED_RESIDUAL", "1") != "0"
 # 0: the attention-bias backward as permute copy + K = H GEMM + LayerNorm-backward pass + LayerNorm pass (A/B; round 4)
 PAIR_BIAS_BWD = os.environ.get("PRD_PAIR_BIAS_BWD", "1") != "0"
+TRI_ATTN_BWD_MAX_N = ops.TRI_ATTN_BWD_TUNED_MAX_N        # alias: the row limit of the tuned 4 x 16 backward cores
 
 
 def _forward_arith() -> Optional[int]:
@@ -57,7 +59,6 @@ def _pin_arithmetic(cls):
     call, and autograd runs a backward long after the ``with _lib.arithmetic(...)`` of ``training_step`` has exited: without the pin a
     model held to "fp32" (``model.arithmetic``, or sample()'s fallback) ran its recompute and its hand-written backward kernels in
     split-16 -- the operand overflow the pin is there to avoid came back in the gradients."""
-    import functools
     f, b = cls.__dict__["forward"].__func__, cls.__dict__["backward"].__func__
 
     @functools.wraps(f)
@@ -215,17 +216,11 @@ class HeadsFn(torch.autograd.Function):
                 r = zij * torch.rsqrt(torch.sum(torch.square(zij), -1, keepdim=True) + 1e-4)
                 dw = (mask.unsqueeze(-1) * mask.unsqueeze(-2)) * (r * de.unsqueeze(2)).sum(-1)         # [b, N, N]
                 psym = ops.sym_rows(pair.detach().contiguous(), 0.5).view(-1, P)
-                xn = torch.empty_like(psym)
-                h = ops.pair_linear(psym, wr1, br1, ln_in=True, xn_out=xn, act=1)
-                if h is None:
-                    h = ops.linear(psym, wr1, br1, act=1, ln_a=True, ln_a_out=xn)
+                h, xn = ops.ln_relu_rows(psym, wr1, br1)
                 dw2 = dw.reshape(-1, 1)
                 gw[2] = (dw2 * h).sum(0, keepdim=True)                                                  # d wr2 [1, HID]
                 g = torch.where(h > 0, dw2 * wr2, torch.zeros((), device=h.device))                     # [rows, HID]
-                dxn = ops.pair_linear(g, wr1.t())
-                if dxn is None:
-                    dxn = ops.linear(g, wr1.t().contiguous())
-                dps = ops.ln_rows_bwd(dxn, psym)
+                dps = ops.ln_rows_bwd(ops.rows_linear(g, wr1, transposed=True), psym)
                 gp = ops.sym_rows(dps.view(b, N, N, P), 0.5)
                 gw[0], gw[1] = ops.linear_wgrad(g, xn, bias=True)
         return (None, None, None, gs, gp, *gw)
@@ -248,25 +243,15 @@ class PairTransitionFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w1, b1, w2, b2 = ctx.saved_tensors
-        P, HID = x.shape[-1], w1.shape[0]
         with torch.no_grad():
-            x2 = x.detach().contiguous().view(-1, P)
-            dy2 = dy.contiguous().view(-1, P)
-            xn = torch.empty_like(x2)
-            res = dy2 if ctx.residual else None                                # (+ dy: the residual path)
-            h = ops.pair_linear(x2, w1, b1, ln_in=True, xn_out=xn, act=1)      # [rows, HID]; LN(x) rows on the side
-            if h is None:
-                h = ops.linear(x2, w1, b1, act=1, ln_a=True, ln_a_out=xn)
-            g = ops.pair_linear(dy2, w2.t(), relu_mask=h)                      # (dy W2) * [h > 0]
-            if g is None:
-                g = ops.linear(dy2, w2.t().contiguous(), relu_mask=h)
-            dxn = ops.pair_linear(g, w1.t())                                   # [rows, P]
-            if dxn is None:
-                dxn = ops.linear(g, w1.t().contiguous())
-            dx = ops.ln_rows_bwd(dxn, x2, res=res)
+            x2 = x.detach().contiguous().view(-1, x.shape[-1])
+            dy2 = dy.contiguous().view_as(x2)
+            h, xn = ops.ln_relu_rows(x2, w1, b1)                               # [rows, HID]; LN(x) rows on the side
+            g = ops.rows_linear(dy2, w2, transposed=True, relu_mask=h)         # (dy W2) * [h > 0]
+            dxn = ops.rows_linear(g, w1, transposed=True)                      # [rows, P]
+            dx = ops.ln_rows_bwd(dxn, x2, res=dy2 if ctx.residual else None).view_as(x)     # (+ dy: the residual path)
             dw2, db2 = ops.linear_wgrad(dy2, h, bias=True)
             dw1, db1 = ops.linear_wgrad(g, xn, bias=True)
-            dx = dx.view_as(x)
         return dx, dw1, db1, dw2, db2, None
 
 
@@ -400,8 +385,7 @@ class TriMulFn(torch.autograd.Function):
 class TriAttnFn(torch.autograd.Function):
     """TriangleAttention update with a hand-written backward (ops.tri_attn_backward: out-projection backward, flash-style attention
     core backward per (row, head), projection + LayerNorm backward on HIP kernels; weight-gradient reductions through BLAS).
-    4 heads x 16 channels run the tuned forward cores, and the tuned backward cores up to TRI_ATTN_BWD_MAX_N positions; every other
-    layout, and longer 4 x 16 rows, take the general backward core (prd_tri_attn_bwd_core_heads), which has no row limit."""
+    Which forward and backward core a layout and row length run is ops.tri_attn_bwd_plan's to say."""
 
     @staticmethod
     def forward(ctx, pair, mask, ending: bool, H: int, c: int, residual: bool, *wts):
@@ -409,20 +393,12 @@ class TriAttnFn(torch.autograd.Function):
         ctx.residual = residual
         with torch.no_grad():
             p, w = pair.detach().contiguous(), [x.detach() for x in wts]
-            # without per-block checkpointing the gated head outputs (64 floats per pair position) and the softmax statistics of
-            # the queries (2 floats per query and head) are kept for the backward instead of being recomputed by a second core launch
+            # without per-block checkpointing the gated head outputs and the queries' softmax statistics are kept, not recomputed by a second launch
             ctx.keep_og = not USE_CHECKPOINT
-            b, N, _, P = p.shape
-            if ops.default_head_layout(H, c):
-                # (the long-row / chunked forward cores beyond TRI_ATTN_BWD_MAX_N keep no statistics: the general backward core finds them)
-                lse = (torch.empty(b * N, H, N, 2, device=p.device, dtype=torch.float32)
-                       if ctx.keep_og and p.is_cuda and N <= TRI_ATTN_BWD_MAX_N and ops.tri_attn_lse_supported(N, P) else None)
-                og = ops.tri_attn_core(p, mask, w[:5], H, c, ending=ending, lse=lse)
-                out = ops.tri_attn_out(p, og, w[5], w[6], residual=residual)
-            else:
-                lse = torch.empty(b * N, H, N, 2, device=p.device, dtype=torch.float32) if ctx.keep_og else None
-                og = ops.tri_attn_core_heads(p, mask, w[:5], H, c, ending=ending, lse=lse)
-                out = ops.linear(og, w[5], w[6], resid=p if residual else None)
+            plan = ops.tri_attn_bwd_plan(p.shape[1], p.shape[-1], H, c)
+            og, lse = ops.tri_attn_core_for_bwd(p, mask, w[:5], H, c, ending=ending, plan=plan, keep_lse=ctx.keep_og)
+            out = (ops.tri_attn_out(p, og, w[5], w[6], residual=residual) if plan.forward == "core" else
+                   ops.linear(og, w[5], w[6], resid=p if residual else None))
         ctx.has_lse = lse is not None
         ctx.save_for_backward(pair, mask, *wts, *([og] if ctx.keep_og else []), *([lse] if ctx.has_lse else []))
         return out
@@ -438,11 +414,6 @@ class TriAttnFn(torch.autograd.Function):
             dpair, grads = ops.tri_attn_backward(dy, pair.detach().contiguous(), mask, [w.detach() for w in wts], H, c, ending=ending, og=og, lse=lse,
                                                  residual=ctx.residual)
         return (dpair, None, None, None, None, None, *grads)
-
-
-TRI_ATTN_BWD_MAX_N = 416        # prd_tri_attn_bwd_core keeps q, k, v, do of a row (padded to 32) and the head's weights in LDS (the gate is
-                                # parked in its own output slot): 156 KB at N = 416 (pitch 20 floats); BASELINE configs[3] draws N <= 384.
-                                # Longer rows (and other layouts) take the general backward core (ops.TRI_ATTN_BWD_TUNED_MAX_N)
 
 
 def tri_attn_update(ta, pair: torch.Tensor, mask: torch.Tensor, residual: bool = False) -> torch.Tensor:
@@ -461,6 +432,10 @@ def _lin(m) -> Tuple[torch.Tensor, ...]:
     return (m.weight, m.bias) if m.bias is not None else (m.weight,)
 
 
+def _big(pair: torch.Tensor) -> bool:       # on the device, with the rows of the library backwards' slab reductions (read at call time)
+    return pair.is_cuda and pair.numel() // pair.shape[-1] >= ops.WGRAD_MIN_ROWS and LIBRARY_BWD
+
+
 # ---------------------------------------------------------------------------------------------------
 # one FoldingBlock (modules.py:328-343), every update out of place
 # ---------------------------------------------------------------------------------------------------
@@ -469,11 +444,15 @@ def folding_block(blk, single: torch.Tensor, pair: torch.Tensor, mask: torch.Ten
     sa, H, c = blk.single_attn, blk.single_attn.num_heads, blk.single_attn.head_dim
     wb, bb = blk.attn_bias[1].weight, blk.attn_bias[1].bias
 
-    big = pair.is_cuda and pair.numel() // pair.shape[-1] >= ops.WGRAD_MIN_ROWS and LIBRARY_BWD
-    if big:
-        bias = PairBiasFn.apply(pair, wb, bb)
-    else:
-        bias = HipOp.apply(lambda p, w, b: ops.pair_bias(p.contiguous(), w, b), R.pair_bias, pair, wb, bb)
+    big = _big(pair)
+    fuse = big and FUSED_RESIDUAL
+
+    def update(pair_, node, small=None):
+        """pair + update in its three residual forms: ``node(residual=True)`` adds inside the operator's kernel; else pair + ``node()``; an
+        operator whose hand-written backward wants a big pair tensor gives ``small``, its HipOp form, for the others."""
+        return node(residual=True) if fuse else pair_ + (node() if big or small is None else small())
+
+    bias = PairBiasFn.apply(pair, wb, bb) if big else HipOp.apply(lambda p, w, b: ops.pair_bias(p.contiguous(), w, b), R.pair_bias, pair, wb, bb)
 
     def sa_ref(x, bias_, *w):
         return R.gated_attention(x, mask, *w, H, c, bias=bias_)
@@ -502,35 +481,43 @@ def folding_block(blk, single: torch.Tensor, pair: torch.Tensor, mask: torch.Ten
             return ops.outer_linear_pair(pair_in, xn, u, w, b, residual=True, out=out)
         return ops.outer_linear_pair(out, xn, u, w, b, residual=False, out=out)
 
-    fuse = big and FUSED_RESIDUAL
-    if fuse:
-        pair = OuterLinearFn.apply(single, ol.linear.weight, ol.linear.bias, ol_hip, pair)
-    elif big:
-        pair = pair + OuterLinearFn.apply(single, ol.linear.weight, ol.linear.bias, ol_hip)
-    else:
-        pair = pair + HipOp.apply(ol_hip, R.outer_linear, single, ol.linear.weight, ol.linear.bias)
-
+    olw = (single, ol.linear.weight, ol.linear.bias)
+    pair = update(pair, lambda residual=False: OuterLinearFn.apply(*olw, ol_hip, pair if residual else None),
+                  lambda: HipOp.apply(ol_hip, R.outer_linear, *olw))
     for tm in (blk.pair_mul_outgoing, blk.pair_mul_incoming):
-        pair = tri_mul_update(tm, pair, mask, residual=True) if fuse else pair + tri_mul_update(tm, pair, mask)
-
+        pair = update(pair, functools.partial(tri_mul_update, tm, pair, mask))
     for ta in (blk.pair_attn_starting, blk.pair_attn_ending):
-        pair = tri_attn_update(ta, pair, mask, residual=True) if fuse else pair + tri_attn_update(ta, pair, mask)
-
+        pair = update(pair, functools.partial(tri_attn_update, ta, pair, mask))
     pf = blk.pair_fc
     pfw = (pf[1].weight, pf[1].bias, pf[3].weight, pf[3].bias)
-    if fuse:
-        pair = PairTransitionFn.apply(pair, *pfw, True)
-    elif big:
-        pair = pair + PairTransitionFn.apply(pair, *pfw)
-    else:
-        pair = pair + HipOp.apply(lambda x, *w: ops.pair_transition(x.contiguous(), *w, residual=False),
-                                  R.transition, pair, *pfw)
+    pair = update(pair, lambda residual=False: PairTransitionFn.apply(pair, *pfw, residual),
+                  lambda: HipOp.apply(lambda x, *w: ops.pair_transition(x.contiguous(), *w, residual=False), R.transition, pair, *pfw))
     return single, pair
 
 
 # ---------------------------------------------------------------------------------------------------
 # the whole network (model.py:254-316), differentiable with respect to every trainable parameter
 # ---------------------------------------------------------------------------------------------------
+
+def _input_stage_hand_ok(model, z: torch.Tensor, bond_tabs) -> bool:
+    """InputStageFn rather than the torch restatement of the input stage.  (Like HeadsFn it returns no gradient for the coordinates: a
+    caller who differentiates with respect to z -- guidance, a gradient check -- gets the restatement instead of a silent None.)"""
+    centers = model.embed_dist[0].center
+    return (z.is_cuda and not z.requires_grad                               # on the device; nobody differentiates the coordinates
+            and LIBRARY_BWD and INPUT_STAGE_BWD                             # neither A/B switch asks for the restatement
+            and model.embed_dist[1].weight.shape[0] <= 64                   # pair_dim within a row of prd_embed_wgrad
+            and centers.numel() % 4 == 0 and not centers.requires_grad      # prd_rbf_rows takes the centres in fours, and gives them no gradient
+            and all(tab.shape[0] <= 128                                     # prd_embed_wgrad: tables of at most 128 rows
+                    for tab in (*bond_tabs, model.embed_bond_distance.weight, model.embed_relpos.weight)))
+
+
+def _heads_hand_ok(pair: torch.Tensor, z: torch.Tensor, wr) -> bool:
+    """HeadsFn rather than the torch restatement of the heads; ``wr`` = model.weight_radial."""
+    return (pair.is_cuda and not z.requires_grad                            # on the device; nobody differentiates the coordinates
+            and LIBRARY_BWD and HEADS_BWD                                   # neither A/B switch asks for the restatement
+            and pair.shape[-1] % 64 == 0 and wr[1].weight.shape[0] % 64 == 0    # widths of the row kernel and the slab reductions
+            and wr[3].weight.shape[0] == 1)                                 # one output channel: dw is a scalar per pair position
+
 
 def network(model, batch: Dict[str, torch.Tensor], z: torch.Tensor, seq_t: torch.Tensor, mask: torch.Tensor, t: torch.Tensor,
             use_checkpoint: Optional[bool] = None):
@@ -564,12 +551,7 @@ def network(model, batch: Dict[str, torch.Tensor], z: torch.Tensor, seq_t: torch
         pair = ops.pair_init(static["pair"], z_.contiguous(), mask, model.embed_dist[0].center, model.embed_dist[1].weight, eb)
         return single, pair
 
-    P_ = model.embed_dist[1].weight.shape[0]
-    # (the hand-written backwards below return no gradient for the coordinates: a caller who differentiates with respect to z --
-    # guidance, a gradient check on the positions -- gets the differentiable torch restatement instead of a silent None)
-    hand = (z.is_cuda and not z.requires_grad and LIBRARY_BWD and INPUT_STAGE_BWD and P_ <= 64 and model.embed_dist[0].center.numel() % 4 == 0 and not model.embed_dist[0].center.requires_grad
-            and all(tab.shape[0] <= 128 for tab in (*bond_tabs, model.embed_bond_distance.weight, model.embed_relpos.weight)))
-    if hand:                                            # hand-written backward of the pair half (InputStageFn)
+    if _input_stage_hand_ok(model, z, bond_tabs):       # hand-written backward of the pair half (InputStageFn)
         meta = dict(batch=batch, mask=mask, t=t, na=na, nb=nb, num_steps=model.num_steps, max_bond_distance=model.max_bond_distance,
                     max_relpos=model.max_relpos)
         single, pair = InputStageFn.apply(in_hip, meta, z, seq_t, *in_params)
@@ -605,7 +587,7 @@ def network(model, batch: Dict[str, torch.Tensor], z: torch.Tensor, seq_t: torch
         bias_ = spa.bias_from_pair(p_) if spa.pair_bias else torch.zeros(s_.shape[0], spa.no_heads, s_.shape[1], s_.shape[1], device=s_.device)
         return spa.attend(mn_, qkvg_, bias_, logits_fp32=True)
 
-    if pair.is_cuda and LIBRARY_BWD and pair.numel() // pair.shape[-1] >= ops.WGRAD_MIN_ROWS and spa.pair_bias:
+    if _big(pair) and spa.pair_bias:
         # the pair bias as its own node with the hand-written backward (PairBiasFn, affine LayerNorm); the attention itself, whose
         # tensors are single-sized, keeps its torch restatement for the backward
         spa_bias = PairBiasFn.apply(pair, spa.linear_z[1].weight, None, spa.linear_z[0].weight, spa.linear_z[0].bias)
@@ -646,9 +628,7 @@ def network(model, batch: Dict[str, torch.Tensor], z: torch.Tensor, seq_t: torch
         h = ops.linear(s_.contiguous(), w[3], w[4], act=1, ln_a=True)
         return eps, ops.linear(h, w[5])
 
-    P_h = pair.shape[-1]
-    if (pair.is_cuda and not z.requires_grad and LIBRARY_BWD and HEADS_BWD and P_h % 64 == 0 and wr[1].weight.shape[0] % 64 == 0
-            and wr[3].weight.shape[0] == 1):
+    if _heads_hand_ok(pair, z, wr):
         return HeadsFn.apply(heads_hip, z, mask, single, pair, *head_params)
     if z.requires_grad:             # the coordinates as an INPUT of the node: the restatement differentiates them too (r_ij and the distances)
         return HipOp.apply(lambda s_, p_, z_, *w: heads_hip(s_, p_, *w), lambda s_, p_, z_, *w: R.heads(s_, p_, z_, mask, *w),

@@ -104,7 +104,8 @@ def backward_table(lines):
             def old():
                 return torch.autograd.grad(recompute_update(pair, mask, wts, H, c), [pair, *wts], dy)
 
-            def general():                  # 4 x 16 at N <= 416: the general core where the tuned cores are the dispatch
+            def general():                  # 4 x 16 at N <= 416: the general core where the tuned cores are the dispatch (the limit is read
+                                            # by forward and backward alike: the forward keeps no statistics, the core finds them)
                 prev, ops.TRI_ATTN_BWD_TUNED_MAX_N = ops.TRI_ATTN_BWD_TUNED_MAX_N, 0
                 try:
                     return new()
