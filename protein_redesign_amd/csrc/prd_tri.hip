@@ -156,7 +156,7 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_proj_kernel(int* queue, float
     extern __shared__ __attribute__((aligned(16))) float smem[];
     PhaseTimer pt;
     constexpr int WSZ = B3 ? OUT * P : OUT * (P + 4);    // floats per staged weight matrix (fp16 hi | lo planes, or fp32 rows)
-    float* Wpl = smem;                       // fp32: [2P][P+4]; bf16 x 3: 3 planes of [2P] rows (prd_common.h)
+    float* Wpl = smem;                       // fp32: [2P][P+4]; B3 (split-16): fp16 hi | lo planes of [2P][P] (prd_common.h: stage_weight_h2)
     float* Wgl = Wpl + WSZ;
     float* bpl = Wgl + WSZ;                  // [2P] CLL
     float* bgl = bpl + OUT;
@@ -841,6 +841,38 @@ PRD_DEV void ta_prio(int rem, int npad) {
     else __builtin_amdgcn_s_setprio(0);
 }
 
+// ---- pieces of a triangle-attention row that every fp32 core states the same way ----
+// the per-key logit override (see the header comment): 0 = keep the logit, else the value that replaces it
+PRD_DEV float ta_key_override(bool keep, bool inside) { return keep ? 0.f : (inside ? -32768.0f * LOG2E : -INFINITY); }
+// pair position of sequence element v of row bu = bb * N + u: (bb, u, v), or (bb, v, u) for the ending node.  A kernel that has
+// (bb, u) of its row at hand passes them: the 64-bit division of the other form is ~150 instructions at every place it is used.
+PRD_DEV long row_pos(int bb, int u, int v, int N, int ending) {
+    return ending ? (((long)bb * N + v) * N + u) : (((long)bb * N + u) * N + v);
+}
+PRD_DEV long row_pos(long bu, int v, int N, int ending) {
+    const long bb = bu / N;
+    const long u = bu - bb * N;
+    return ending ? ((bb * N + v) * N + u) : (bu * N + v);
+}
+// [k; v] accumulator of the 32-position block holding position v -> K tile and V^T.  D rows of a block: channels {4hi+e} in
+// registers 0-3 and {8+4hi+e} in 4-7 of each 16-row group.  (The two V^T row bases are formed once: with the row index inside the
+// loop the 12-wave short core, which sits at its 168-register limit, spills.)
+PRD_DEV void ta_store_kv(float* Kl, float* Vt, f32x16 kv, int v, int npad, int hi) {
+    *reinterpret_cast<float4*>(Kl + v * KP + 4 * hi) = make_float4(kv[0], kv[1], kv[2], kv[3]);
+    *reinterpret_cast<float4*>(Kl + v * KP + 8 + 4 * hi) = make_float4(kv[4], kv[5], kv[6], kv[7]);
+    float *v0 = Vt + 4 * hi * (npad + 4) + v, *v1 = Vt + (8 + 4 * hi) * (npad + 4) + v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        v0[e * (npad + 4)] = kv[8 + e];
+        v1[e * (npad + 4)] = kv[12 + e];
+    }
+}
+// gate * (o / l): the gated, normalised output of one query's four channels.  (It returns the value and the caller stores it, so that
+// the quotients are formed before the store address, as an assignment does: the other order costs the short core registers.)
+PRD_DEV float4 ta_gated(const float4& gf, const f32x4& o, float l) {
+    return make_float4(gf.x * (o[0] / l), gf.y * (o[1] / l), gf.z * (o[2] / l), gf.w * (o[3] / l));
+}
+
 // One 64-key block (JT = 4 tiles of 16 keys) of the key loop.
 //   ONLINE: running maximum, rescale of o / l (the classic online softmax).
 //   !ONLINE: the reference maximum m_run stays frozen; the logits come out of the MFMA already relative to it (the
@@ -1107,7 +1139,8 @@ __global__ __launch_bounds__(256) void single_attn_core_kernel(float* __restrict
         float m_all = part[0][0][lane];
 #pragma unroll
         for (int w = 1; w < 4; ++w) m_all = fmaxf(m_all, part[w][0][lane]);
-        float l_tot = 0.f, ot[4] = {0.f, 0.f, 0.f, 0.f};
+        float l_tot = 0.f;
+        f32x4 ot = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int w = 0; w < 4; ++w) {                              // fixed order; a wave without keys has l = 0, o = 0
             const float sc = __builtin_amdgcn_exp2f(part[w][0][lane] - m_all);
@@ -1116,8 +1149,7 @@ __global__ __launch_bounds__(256) void single_attn_core_kernel(float* __restrict
             for (int e = 0; e < 4; ++e) ot[e] += part[w][2 + e][lane] * sc;
         }
         const float4 gf = *reinterpret_cast<const float4*>(base + (size_t)q * L + 3 * HC + h * C + 4 * g4);
-        *reinterpret_cast<float4*>(o_out + ((size_t)bb * N + q) * HC + h * C + 4 * g4) =
-            make_float4(gf.x * (ot[0] / l_tot), gf.y * (ot[1] / l_tot), gf.z * (ot[2] / l_tot), gf.w * (ot[3] / l_tot));
+        *reinterpret_cast<float4*>(o_out + ((size_t)bb * N + q) * HC + h * C + 4 * g4) = ta_gated(gf, ot, l_tot);
     }
 }
 
@@ -1129,16 +1161,15 @@ __global__ __launch_bounds__(256) void single_attn_core_kernel(float* __restrict
 //            share a SIMD), two tiles at a time through ta_keyloop.
 // LDS bytes: weights [64][P + 4] | K, V, Q tiles [npad][KP] | gate [16][npad + 4] | override [npad] | bias [32]
 size_t tri_attn_core_lds_bytes(int P, int npad) { return ((size_t)64 * (P + 4) + (size_t)3 * npad * KP + 16 * (npad + 4) + npad + 32) * sizeof(float); }
-template <int P, int NW, bool PREFETCH, bool B3>
+template <int P, int NW>
 __global__ __launch_bounds__(NW * 64) void tri_attn_core_kernel(
     float* __restrict__ og, const float* __restrict__ pair, const float* __restrict__ mask,
     const float* __restrict__ wq, const float* __restrict__ wk, const float* __restrict__ wv,
     const float* __restrict__ wg, const float* __restrict__ bg, int b, int N, int npad, int H, int ending) {
     constexpr int C = 16, HC = 64, NT = NW * 64, KH = P / 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int WSZ = B3 ? 3 * 64 * (2 * (P / 16) + 1) * 4 : 64 * (P + 4);   // B3: opt-in bf16 x 3 projections (prd_common.h)
     float* Wl = smem;                          // [64][P+4]: rows 0-15 k_h, 16-31 v_h, 32-47 q_h, 48-63 g_h
-    float* Kl = Wl + WSZ;                      // [npad][KP]           (npad = round_up(N, 64))
+    float* Kl = Wl + 64 * (P + 4);             // [npad][KP]           (npad = round_up(N, 64))
     float* Vt = Kl + npad * KP;                // [16][npad+4]
     float* kadd = Vt + C * (npad + 4);         // [npad]: 0 = keep the logit, else the value that replaces it
     float* Ql = kadd + npad;                   // [npad][KP]
@@ -1162,32 +1193,16 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_kernel(
         slot = blockIdx.x / H;
     }
     const float sc = 0.25f * LOG2E;            // 1/sqrt(c) (modules.py:176,216) in the exp2 domain, folded into Wq
-    if (B3) {       // one image of 64 rows; stage_weight_b3_rows takes (first row pointer, rows staged, plane stride in rows)
-        u32x4* Wb = reinterpret_cast<u32x4*>(Wl);
-        constexpr int PITCH = 2 * (P / 16) + 1;
-        stage_weight_b3_rows<P>(Wb, 64, 0, wk + (long)h * C * P, C, P, tid, NT, 1.0f);
-        stage_weight_b3_rows<P>(Wb, 64, C, wv + (long)h * C * P, C, P, tid, NT, 1.0f);
-        stage_weight_b3_rows<P>(Wb, 64, 2 * C, wq + (long)h * C * P, C, P, tid, NT, sc);
-        stage_weight_b3_rows<P>(Wb, 64, 3 * C, wg + (long)h * C * P, C, P, tid, NT, NEG_LOG2E);
-        (void)PITCH;
-    } else {
-        stage_weight_cll<P>(Wl, wk + (long)h * C * P, C, P, tid, NT);
-        stage_weight_cll<P>(Wl + C * (P + 4), wv + (long)h * C * P, C, P, tid, NT);
-        stage_weight_cll<P>(Wl + 2 * C * (P + 4), wq + (long)h * C * P, C, P, tid, NT, sc);
-        stage_weight_cll<P>(Wl + 3 * C * (P + 4), wg + (long)h * C * P, C, P, tid, NT, NEG_LOG2E);   // gate_from_scaled
-    }
+    stage_weight_cll<P>(Wl, wk + (long)h * C * P, C, P, tid, NT);
+    stage_weight_cll<P>(Wl + C * (P + 4), wv + (long)h * C * P, C, P, tid, NT);
+    stage_weight_cll<P>(Wl + 2 * C * (P + 4), wq + (long)h * C * P, C, P, tid, NT, sc);
+    stage_weight_cll<P>(Wl + 3 * C * (P + 4), wg + (long)h * C * P, C, P, tid, NT, NEG_LOG2E);   // gate_from_scaled
     // accumulator preload of the [q; g] half: lane half hi owns D rows q{4hi+e}, q{8+4hi+e}, g{4hi+e}, g{8+4hi+e}
     if (tid < 32) {
         const int hh = tid >> 4, e = tid & 15;
         bqg[tid] = e < 8 ? 0.f : NEG_LOG2E * bg[h * C + (e < 12 ? 4 * hh + (e - 8) : 8 + 4 * hh + (e - 12))];
     }
     const long nrows = (long)b * N;
-
-    auto row_pos = [&](long bu, int v) -> long {          // pair position of sequence element v of row bu
-        const long bb = bu / N;
-        const long u = bu - bb * N;
-        return ending ? ((bb * N + v) * N + u) : (bu * N + v);
-    };
     // ---- phase-1 work of this wave: (block, halves) units.  Half 0 = [k; v], half 1 = [q; gate] (32 MFMAs each).
     // Whole rounds of NW blocks go one block per wave; of the R blocks left, as many as needed are split in halves
     // over two waves so that the SIMDs (waves w, w+4, w+8 share one) end together: N = 320 -> waves 0-7 a block each,
@@ -1208,11 +1223,11 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_kernel(
     }
     // prefetch of this wave's first block of the first row
     float xnext[KH];
-    if (PREFETCH) {
+    {
         const long bu0 = slot;
         const int v = first_blk * 32 + r;
         const bool ok = bu0 < nrows && first_blk >= 0 && v < N;
-        load_row_cll<P>(pair + row_pos(ok ? bu0 : 0, ok ? v : 0) * P, hi, ok, xnext);
+        load_row_cll<P>(pair + row_pos(ok ? bu0 : 0, ok ? v : 0, N, ending) * P, hi, ok, xnext);
     }
     int it = 0;
     for (long bu = slot; bu < nrows; bu += rstride, ++it) {
@@ -1227,38 +1242,27 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_kernel(
             const int v = vb * 32 + r;
             const bool valid = v < N;
             float x[KH];
-            if (PREFETCH && un == 0) {
+            if (un == 0) {
 #pragma unroll
                 for (int s = 0; s < KH; ++s) x[s] = xnext[s];
             } else {
-                load_row_cll<P>(pair + row_pos(bu, valid ? v : 0) * P, hi, valid, x);
+                load_row_cll<P>(pair + row_pos(bu, valid ? v : 0, N, ending) * P, hi, valid, x);
             }
             ln_cll<KH>(x);
-            u32x4 xs[3][P / 16];
-            if (B3) split3_cll<P>(x, xs);
             if (halves & 1) {
                 if (hi == 0) {                                // per-key logit override of this row (see header comment)
                     const bool keep = valid && (mu * mask[(long)bb * N + (valid ? v : 0)] >= 0.5f);
-                    kadd[v] = keep ? 0.f : (valid ? -32768.0f * LOG2E : -INFINITY);
+                    kadd[v] = ta_key_override(keep, valid);
                 }
                 f32x16 acc[1];
                 zero_acc(acc);
-                if (B3) rowgemm_b3<P, 1>(reinterpret_cast<const u32x4*>(Wl), 64, 0, xs, acc, r, hi);
-                else rowgemm<P, 1>(Wl, x, acc, r, hi);
-                // D rows of a block: channels {4hi+e} in registers 0-3 and {8+4hi+e} in 4-7 of each 16-row group
-                *reinterpret_cast<float4*>(Kl + v * KP + 4 * hi) = make_float4(acc[0][0], acc[0][1], acc[0][2], acc[0][3]);
-                *reinterpret_cast<float4*>(Kl + v * KP + 8 + 4 * hi) = make_float4(acc[0][4], acc[0][5], acc[0][6], acc[0][7]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    Vt[(4 * hi + e) * (npad + 4) + v] = acc[0][8 + e];
-                    Vt[(8 + 4 * hi + e) * (npad + 4) + v] = acc[0][12 + e];
-                }
+                rowgemm<P, 1>(Wl, x, acc, r, hi);
+                ta_store_kv(Kl, Vt, acc[0], v, npad, hi);
             }
             if (halves & 2) {
                 f32x16 acc[1];
                 bias_acc(acc, bqg + 16 * hi);
-                if (B3) rowgemm_b3<P, 1>(reinterpret_cast<const u32x4*>(Wl), 64, 32, xs, acc, r, hi);
-                else rowgemm<P, 1>(Wl + 2 * C * (P + 4), x, acc, r, hi);
+                rowgemm<P, 1>(Wl + 2 * C * (P + 4), x, acc, r, hi);
                 *reinterpret_cast<float4*>(Ql + v * KP + 4 * hi) = make_float4(acc[0][0], acc[0][1], acc[0][2], acc[0][3]);
                 *reinterpret_cast<float4*>(Ql + v * KP + 8 + 4 * hi) = make_float4(acc[0][4], acc[0][5], acc[0][6], acc[0][7]);
                 *reinterpret_cast<float4*>(Gl + v * KP + 4 * hi) = make_float4(gate_from_scaled(acc[0][8]), gate_from_scaled(acc[0][9]),
@@ -1270,12 +1274,11 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_kernel(
         PRD_STAMP(1);
         __syncthreads();
         PRD_STAMP(2);
-        // next row's first block: in flight during the whole key loop
-        if (PREFETCH) {
+        {   // next row's first block: in flight during the whole key loop
             const long bun = bu + rstride;
             const int v = first_blk * 32 + r;
             const bool ok = bun < nrows && first_blk >= 0 && v < N;
-            load_row_cll<P>(pair + row_pos(ok ? bun : 0, ok ? v : 0) * P, hi, ok, xnext);
+            load_row_cll<P>(pair + row_pos(ok ? bun : 0, ok ? v : 0, N, ending) * P, hi, ok, xnext);
         }
         // ---- phase 2 ----
         // rows without masked or padded keys (the common case) take a key loop without the per-key override
@@ -1297,9 +1300,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_kernel(
                     const int v = 16 * (t == 0 ? t0 : t1) + ql;
                     if (v < N) {
                         const float4 gf = *reinterpret_cast<const float4*>(Gl + v * KP + 4 * g4);
-                        *reinterpret_cast<float4*>(og + row_pos(bu, v) * HC + h * C + 4 * g4) =
-                            make_float4(gf.x * (o[t][0] / l_tot[t]), gf.y * (o[t][1] / l_tot[t]),
-                                        gf.z * (o[t][2] / l_tot[t]), gf.w * (o[t][3] / l_tot[t]));
+                        *reinterpret_cast<float4*>(og + row_pos(bu, v, N, ending) * HC + h * C + 4 * g4) = ta_gated(gf, o[t], l_tot[t]);
                     }
                 }
             } else {
@@ -1312,9 +1313,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_kernel(
                 const int v = 16 * t0 + ql;
                 if (v < N) {
                     const float4 gf = *reinterpret_cast<const float4*>(Gl + v * KP + 4 * g4);
-                    *reinterpret_cast<float4*>(og + row_pos(bu, v) * HC + h * C + 4 * g4) =
-                        make_float4(gf.x * (o[0][0] / l_tot[0]), gf.y * (o[0][1] / l_tot[0]),
-                                    gf.z * (o[0][2] / l_tot[0]), gf.w * (o[0][3] / l_tot[0]));
+                    *reinterpret_cast<float4*>(og + row_pos(bu, v, N, ending) * HC + h * C + 4 * g4) = ta_gated(gf, o[0], l_tot[0]);
                 }
             }
         }
@@ -1333,7 +1332,7 @@ size_t tri_attn_core_split_long_lds_bytes(int P, int npad) { return (size_t)64 *
 #ifdef PRD_AB
 // ---------------------------------------------------------------------------------------------------------------------
 // Triangle attention core on the 16-bit matrix pipes (gemm mode 1), fp32-accurate by operand splitting:
-//   * projections: bf16 x 3 row GEMM (rowgemm_b3), as in the kernel above;
+//   * projections: fp16 x 2 row GEMM (prd_common.h: rowgemm_h2), weights staged x 16;
 //   * S^T = K Q^T: K and Q are split exactly into three bf16 parts ONCE per row in phase 1 (the key loop pays nothing for it).
 //     The head width is 16 but v_mfma_f32_16x16x32_bf16 contracts 32: two 16-wide products ride in one instruction,
 //       [kh | kh] x [qh | qm],  [km | kl] x [qh | qh],  [km | kh] x [qm | ql]
@@ -1580,11 +1579,6 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_kernel(
         bqg[tid] = e < 8 ? 0.f : H2_WSCALE * NEG_LOG2E * bg[h * C + (e < 12 ? 4 * hh + (e - 8) : 8 + 4 * hh + (e - 12))];
     }
     const long nrows = (long)b * N;
-    auto row_pos = [&](long bu, int v) -> long {
-        const long bb = bu / N;
-        const long u = bu - bb * N;
-        return ending ? ((bb * N + v) * N + u) : (bu * N + v);
-    };
     const int full_rounds = nqb / NW, R = nqb - full_rounds * NW;
     const int S = 2 * R <= NW ? R : NW - R;
     const int F = R - S;
@@ -1610,7 +1604,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_kernel(
         const long bu0 = slot;
         const int v = first_blk * 32 + r;
         const bool ok = bu0 < nrows && first_blk >= 0 && v < N;
-        load_row_cll<P>(pair + row_pos(ok ? bu0 : 0, ok ? v : 0) * P, hi, ok, reinterpret_cast<float (&)[KH]>(xnext));
+        load_row_cll<P>(pair + row_pos(ok ? bu0 : 0, ok ? v : 0, N, ending) * P, hi, ok, reinterpret_cast<float (&)[KH]>(xnext));
     }
     // per-lane operand bases of the three QK^T MFMAs (see the header comment): A = K planes, B = Q planes
     const unsigned kbase[3] = {L.kp[0], g4 < 2 ? L.kp[1] : L.kp[2], g4 < 2 ? L.kp[1] : L.kp[0]};
@@ -1632,10 +1626,10 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_kernel(
 #pragma unroll
                 for (int s_ = 0; s_ < KH; ++s_) x[s_] = xnext[PREFETCH ? s_ : 0];
             } else {
-                load_row_cll<P>(pair + row_pos(bu, valid ? v : 0) * P, hi, valid, x);
+                load_row_cll<P>(pair + row_pos(bu, valid ? v : 0, N, ending) * P, hi, valid, x);
             }
             if (FUSE) {                         // x += og_in W_o^T + b_o: the previous attention's residual update of this row
-                const long pos = row_pos(bu, valid ? v : 0);
+                const long pos = row_pos(bu, valid ? v : 0, N, ending);
                 float xo[HC / 2];
                 load_row_cll<HC>(og_in + pos * HC, hi, valid, xo);
                 u32x4 os[2][HC / 16];
@@ -1653,7 +1647,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_kernel(
             if (halves & 1) {
                 if (hi == 0) {
                     const bool keep = valid && (mu * mask[(long)bb * N + (valid ? v : 0)] >= 0.5f);
-                    kadd[v] = keep ? 0.f : (valid ? -32768.0f * LOG2E : -INFINITY);
+                    kadd[v] = ta_key_override(keep, valid);
                 }
                 f32x16 acc[1];
                 zero_acc(acc);
@@ -1717,7 +1711,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_kernel(
             const long bun = bu + rstride;
             const int v = first_blk * 32 + r;
             const bool ok = bun < nrows && first_blk >= 0 && v < N;
-            load_row_cll<P>(pair + row_pos(ok ? bun : 0, ok ? v : 0) * P, hi, ok, reinterpret_cast<float (&)[KH]>(xnext));
+            load_row_cll<P>(pair + row_pos(ok ? bun : 0, ok ? v : 0, N, ending) * P, hi, ok, reinterpret_cast<float (&)[KH]>(xnext));
         }
         // ---- phase 2 ----
         bool row_masked = false;
@@ -1744,7 +1738,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_kernel(
                     if (v < N) {
                         const float4 gf = *reinterpret_cast<const float4*>(Gl + v * KP + 4 * g4);
                         const float il = inv_vs / l_tot[t];
-                        *reinterpret_cast<float4*>(og + row_pos(bu, v) * HC + h * C + 4 * g4) =
+                        *reinterpret_cast<float4*>(og + row_pos(bu, v, N, ending) * HC + h * C + 4 * g4) =
                             make_float4(gf.x * (o[t][0] * il), gf.y * (o[t][1] * il), gf.z * (o[t][2] * il), gf.w * (o[t][3] * il));
                     }
                 }
@@ -1761,7 +1755,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_kernel(
                 if (v < N) {
                     const float4 gf = *reinterpret_cast<const float4*>(Gl + v * KP + 4 * g4);
                     const float il = inv_vs / l_tot[0];
-                    *reinterpret_cast<float4*>(og + row_pos(bu, v) * HC + h * C + 4 * g4) =
+                    *reinterpret_cast<float4*>(og + row_pos(bu, v, N, ending) * HC + h * C + 4 * g4) =
                         make_float4(gf.x * (o[0][0] * il), gf.y * (o[0][1] * il), gf.z * (o[0][2] * il), gf.w * (o[0][3] * il));
                 }
             }
@@ -1833,11 +1827,6 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_long_kernel(
     // operand bases of the two QK^T MFMAs: A = [kh | kh], [kl | kl];  B = [qh | ql], [qh | 0]
     const unsigned kbase[2] = {L.kp[0], L.kp[1]};
     const long nrows = (long)b * N;
-    auto row_pos = [&](long bu, int v) -> long {
-        const long bb = bu / N;
-        const long u = bu - bb * N;
-        return ending ? ((bb * N + v) * N + u) : (bu * N + v);
-    };
     for (long bu = slot; bu < nrows; bu += rstride) {
         const int bb = (int)(bu / N);
         __syncthreads();                        // previous row's K / V fully consumed (and weights staged)
@@ -1850,7 +1839,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_long_kernel(
             zero_acc(acc);
             if (vb < nqb) {
                 float x[KH];
-                load_row_cll<P>(pair + row_pos(bu, valid ? v : 0) * P, hi, valid, x);
+                load_row_cll<P>(pair + row_pos(bu, valid ? v : 0, N, ending) * P, hi, valid, x);
                 ln_cll<KH>(x);
                 u32x4 xs[2][P / 16];
                 split2h_cll<KH>(x, xs);
@@ -1858,7 +1847,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_long_kernel(
             }
             if (hi == 0) {
                 const bool keep = valid && (mu * mask[(long)bb * N + (valid ? v : 0)] >= 0.5f);
-                kadd[v] = keep ? 0.f : (valid ? -32768.0f * LOG2E : -INFINITY);
+                kadd[v] = ta_key_override(keep, valid);
             }
             unsigned kh0, kl0, kh1, kl1, kh2, kl2, kh3, kl3;
             split2h(acc[0][0] * H2_INV_WSCALE, acc[0][1] * H2_INV_WSCALE, kh0, kl0);
@@ -1890,7 +1879,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_long_kernel(
                 const int v = qb_ * 32 + r;
                 const bool valid = v < N;
                 float x[KH];
-                load_row_cll<P>(pair + row_pos(bu, valid ? v : 0) * P, hi, valid, x);
+                load_row_cll<P>(pair + row_pos(bu, valid ? v : 0, N, ending) * P, hi, valid, x);
                 ln_cll<KH>(x);
                 u32x4 xs[2][P / 16];
                 split2h_cll<KH>(x, xs);
@@ -1933,7 +1922,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_long_kernel(
                 if (v < N) {
                     const float4 gf = *reinterpret_cast<const float4*>(Gs + (16 * t + ql) * 16 + 4 * g4);
                     const float il = inv_vs / l_tot[t];
-                    *reinterpret_cast<float4*>(og + row_pos(bu, v) * HC + h * C + 4 * g4) =
+                    *reinterpret_cast<float4*>(og + row_pos(bu, v, N, ending) * HC + h * C + 4 * g4) =
                         make_float4(gf.x * (o[t][0] * il), gf.y * (o[t][1] * il), gf.z * (o[t][2] * il), gf.w * (o[t][3] * il));
                 }
             }
@@ -1948,11 +1937,14 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_split_long_kernel(
 // LDS bytes of the fp32 long-row core and of its key-chunked form (nkeys = the keys a launch holds, a multiple of 64):
 // weights [64][P + 4] | K tiles [nkeys][KP] | V [16][nkeys + 4] | override [nkeys]
 size_t tri_attn_core_long_lds_bytes(int P, int nkeys) { return ((size_t)64 * (P + 4) + (size_t)nkeys * KP + 16 * (nkeys + 4) + nkeys) * sizeof(float); }
-template <int P, int NW>
-__global__ __launch_bounds__(NW * 64) void tri_attn_core_long_kernel(
-    float* __restrict__ og, const float* __restrict__ pair, const float* __restrict__ mask,
+// The body of both forms: all queries of a row against the keys [key0, key0 + klen) of it, npad = klen rounded up to 64.  The resident
+// form (!CHUNKED) holds the whole row (key0 = 0, klen = N) and stores the gated, normalised output; the chunked form also merges
+// with what the earlier chunks of the row left in og / stats (see tri_attn_core_chunk_kernel), unless this chunk is the `first`.
+template <int P, int NW, bool CHUNKED>
+PRD_DEV void tri_attn_core_long_body(
+    float* __restrict__ og, float* __restrict__ stats, const float* __restrict__ pair, const float* __restrict__ mask,
     const float* __restrict__ wq, const float* __restrict__ wk, const float* __restrict__ wv,
-    const float* __restrict__ wg, const float* __restrict__ bg, int b, int N, int npad, int H, int ending) {
+    const float* __restrict__ wg, const float* __restrict__ bg, int b, int N, int key0, int klen, int npad, int first, int H, int ending) {
     constexpr int C = 16, HC = 64, NT = NW * 64, KH = P / 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Wl = smem;                          // [64][P+4]: rows 0-15 k_h, 16-31 v_h, 32-47 q_h, 48-63 g_h
@@ -1976,30 +1968,22 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_long_kernel(
         __syncthreads();
         const float mu = mask[bu];
         for (int k = tid; k < npad; k += NT) {
-            const bool inside = k < N;
-            const bool keep = inside && (mu * mask[(long)bb * N + (inside ? k : 0)] >= 0.5f);
-            kadd[k] = keep ? 0.f : (inside ? -32768.0f * LOG2E : -INFINITY);
+            const bool inside = k < klen;
+            const bool keep = inside && (mu * mask[(long)bb * N + (inside ? key0 + k : 0)] >= 0.5f);
+            kadd[k] = ta_key_override(keep, inside);
         }
         for (int vb = wave; vb < nvb; vb += NW) {
-            const int v = vb * 32 + r;
-            const bool valid = v < N;
-            const int vv = valid ? v : 0;
-            const long pos = ending ? (((long)bb * N + vv) * N + u) : (bu * N + vv);
+            const int kk = vb * 32 + r;                  // key index inside [key0, key0 + klen)
+            const bool valid = kk < klen;
             f32x16 kv[1];
             zero_acc(kv);
-            if (vb < nqb) {
+            if (vb * 32 < klen) {
                 float x[KH];
-                load_row_cll<P>(pair + pos * P, hi, valid, x);
+                load_row_cll<P>(pair + row_pos(bb, u, valid ? key0 + kk : 0, N, ending) * P, hi, valid, x);
                 ln_cll<KH>(x);
                 rowgemm<P, 1>(Wl, x, kv, r, hi);
             }
-            *reinterpret_cast<float4*>(Kl + v * KP + 4 * hi) = make_float4(kv[0][0], kv[0][1], kv[0][2], kv[0][3]);
-            *reinterpret_cast<float4*>(Kl + v * KP + 8 + 4 * hi) = make_float4(kv[0][4], kv[0][5], kv[0][6], kv[0][7]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                Vt[(4 * hi + e) * (npad + 4) + v] = kv[0][8 + e];
-                Vt[(8 + 4 * hi + e) * (npad + 4) + v] = kv[0][12 + e];
-            }
+            ta_store_kv(Kl, Vt, kv[0], kk, npad, hi);
         }
         __syncthreads();
         for (int qb = wave; qb < nqb; qb += NW) {
@@ -2007,10 +1991,8 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_long_kernel(
             {
                 const int v = qb * 32 + r;
                 const bool valid = v < N;
-                const int vv = valid ? v : 0;
-                const long pos = ending ? (((long)bb * N + vv) * N + u) : (bu * N + vv);
                 float x[KH];
-                load_row_cll<P>(pair + pos * P, hi, valid, x);
+                load_row_cll<P>(pair + row_pos(bb, u, valid ? v : 0, N, ending) * P, hi, valid, x);
                 ln_cll<KH>(x);
                 f32x16 acc[1];
                 zero_acc(acc);
@@ -2044,19 +2026,49 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_long_kernel(
             }
             f32x4 o[2];
             float l_tot[2];
-            ta_keyloop<2, true>(Kl, Vt, kadd, qf, npad, ql, g4, o, l_tot);
+            [[maybe_unused]] float m_ref[2];
+            if constexpr (CHUNKED) ta_keyloop<2, true>(Kl, Vt, kadd, qf, npad, ql, g4, o, l_tot, m_ref);
+            else ta_keyloop<2, true>(Kl, Vt, kadd, qf, npad, ql, g4, o, l_tot);
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int v = qb * 32 + 16 * t + ql;
                 if (v < N) {
-                    const long pos = ending ? (((long)bb * N + v) * N + u) : (bu * N + v);
-                    *reinterpret_cast<float4*>(og + pos * HC + h * C + 4 * g4) =
-                        make_float4(gf[t].x * (o[t][0] / l_tot[t]), gf[t].y * (o[t][1] / l_tot[t]),
-                                    gf[t].z * (o[t][2] / l_tot[t]), gf[t].w * (o[t][3] / l_tot[t]));
+                    const long pos = row_pos(bb, u, v, N, ending);
+                    if constexpr (!CHUNKED) {
+                        *reinterpret_cast<float4*>(og + pos * HC + h * C + 4 * g4) = ta_gated(gf[t], o[t], l_tot[t]);
+                    } else {
+                        float4* dst = reinterpret_cast<float4*>(og + pos * HC + h * C + 4 * g4);
+                        float* st = stats + (pos * H + h) * 2;
+                        const float il = 1.0f / l_tot[t];
+                        float4 mine = make_float4(gf[t].x * (o[t][0] * il), gf[t].y * (o[t][1] * il), gf[t].z * (o[t][2] * il), gf[t].w * (o[t][3] * il));
+                        float m_new = m_ref[t], l_new = l_tot[t];
+                        if (!first) {
+                            const float m0 = st[0], l0 = st[1];
+                            const float4 prev = *dst;
+                            const float M = fmaxf(m0, m_ref[t]);
+                            const float w0 = l0 * exp2f(m0 - M), w1 = l_tot[t] * exp2f(m_ref[t] - M);
+                            const float iw = 1.0f / (w0 + w1);
+                            const float a0 = w0 * iw, a1 = w1 * iw;
+                            mine = make_float4(a0 * prev.x + a1 * mine.x, a0 * prev.y + a1 * mine.y, a0 * prev.z + a1 * mine.z, a0 * prev.w + a1 * mine.w);
+                            m_new = M;
+                            l_new = w0 + w1;
+                        }
+                        *dst = mine;
+                        // the four lanes (g4) of a query read the statistics above before lane g4 = 0 replaces them: one wave, program order
+                        if (g4 == 0) { st[0] = m_new; st[1] = l_new; }
+                    }
                 }
             }
         }
     }
+}
+
+template <int P, int NW>
+__global__ __launch_bounds__(NW * 64) void tri_attn_core_long_kernel(
+    float* __restrict__ og, const float* __restrict__ pair, const float* __restrict__ mask,
+    const float* __restrict__ wq, const float* __restrict__ wk, const float* __restrict__ wv,
+    const float* __restrict__ wg, const float* __restrict__ bg, int b, int N, int npad, int H, int ending) {
+    tri_attn_core_long_body<P, NW, false>(og, nullptr, pair, mask, wq, wk, wv, wg, bg, b, N, 0, N, npad, 1, H, ending);
 }
 
 // Rows of any length (N > 960: K / V of a whole row no longer fit the LDS): the long-row kernel over ONE contiguous chunk of
@@ -2070,125 +2082,8 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_core_chunk_kernel(
     float* __restrict__ og, float* __restrict__ stats, const float* __restrict__ pair, const float* __restrict__ mask,
     const float* __restrict__ wq, const float* __restrict__ wk, const float* __restrict__ wv,
     const float* __restrict__ wg, const float* __restrict__ bg, int b, int N, int key0, int klen, int first, int H, int ending) {
-    constexpr int C = 16, HC = 64, NT = NW * 64, KH = P / 2;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
     const int npad = (klen + 63) / 64 * 64;    // keys of this chunk, padded
-    float* Wl = smem;                          // [64][P+4]: rows 0-15 k_h, 16-31 v_h, 32-47 q_h, 48-63 g_h
-    float* Kl = Wl + 64 * (P + 4);             // [npad][KP]
-    float* Vt = Kl + npad * KP;                // [16][npad+4]
-    float* kadd = Vt + C * (npad + 4);         // [npad]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, hi = lane >> 5;
-    const int ql = lane & 15, g4 = lane >> 4;
-    const int nvb = npad / 32;
-    const int nqb = (N + 31) / 32;
-    const int h = blockIdx.x % H;
-    const int rstride = gridDim.x / H;
-    stage_weight_cll<P>(Wl, wk + (long)h * C * P, C, P, tid, NT);
-    stage_weight_cll<P>(Wl + C * (P + 4), wv + (long)h * C * P, C, P, tid, NT);
-    stage_weight_cll<P>(Wl + 2 * C * (P + 4), wq + (long)h * C * P, C, P, tid, NT);
-    stage_weight_cll<P>(Wl + 3 * C * (P + 4), wg + (long)h * C * P, C, P, tid, NT);
-    const float sc = 0.25f * LOG2E;
-    for (long bu = blockIdx.x / H; bu < (long)b * N; bu += rstride) {
-        const int bb = (int)(bu / N), u = (int)(bu - (long)bb * N);
-        __syncthreads();
-        const float mu = mask[bu];
-        for (int k = tid; k < npad; k += NT) {
-            const bool inside = k < klen;
-            const bool keep = inside && (mu * mask[(long)bb * N + (inside ? key0 + k : 0)] >= 0.5f);
-            kadd[k] = keep ? 0.f : (inside ? -32768.0f * LOG2E : -INFINITY);
-        }
-        for (int vb = wave; vb < nvb; vb += NW) {
-            const int kk = vb * 32 + r;                  // key index inside the chunk
-            const bool valid = kk < klen;
-            const int vv = valid ? key0 + kk : 0;
-            const long pos = ending ? (((long)bb * N + vv) * N + u) : (bu * N + vv);
-            f32x16 kv[1];
-            zero_acc(kv);
-            if (vb * 32 < klen) {
-                float x[KH];
-                load_row_cll<P>(pair + pos * P, hi, valid, x);
-                ln_cll<KH>(x);
-                rowgemm<P, 1>(Wl, x, kv, r, hi);
-            }
-            *reinterpret_cast<float4*>(Kl + kk * KP + 4 * hi) = make_float4(kv[0][0], kv[0][1], kv[0][2], kv[0][3]);
-            *reinterpret_cast<float4*>(Kl + kk * KP + 8 + 4 * hi) = make_float4(kv[0][4], kv[0][5], kv[0][6], kv[0][7]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                Vt[(4 * hi + e) * (npad + 4) + kk] = kv[0][8 + e];
-                Vt[(8 + 4 * hi + e) * (npad + 4) + kk] = kv[0][12 + e];
-            }
-        }
-        __syncthreads();
-        for (int qb = wave; qb < nqb; qb += NW) {
-            float qg[16];
-            {
-                const int v = qb * 32 + r;
-                const bool valid = v < N;
-                const int vv = valid ? v : 0;
-                const long pos = ending ? (((long)bb * N + vv) * N + u) : (bu * N + vv);
-                float x[KH];
-                load_row_cll<P>(pair + pos * P, hi, valid, x);
-                ln_cll<KH>(x);
-                f32x16 acc[1];
-                zero_acc(acc);
-                rowgemm<P, 1>(Wl + 2 * C * (P + 4), x, acc, r, hi);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) qg[i] = acc[0][i];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    qg[8 + e] = acc[0][8 + e] + bg[h * C + 4 * hi + e];
-                    qg[12 + e] = acc[0][12 + e] + bg[h * C + 8 + 4 * hi + e];
-                }
-            }
-            float4 qf[2], gf[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {              // same redistribution as tri_attn_core_long_kernel
-                const int src = 16 * t + ql + 32 * (g4 & 1);
-                float lo[4], up[4], glo[4], gup[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    lo[e] = __shfl(qg[e], src);
-                    up[e] = __shfl(qg[4 + e], src);
-                    glo[e] = __shfl(qg[8 + e], src);
-                    gup[e] = __shfl(qg[12 + e], src);
-                }
-                const bool hiq = (g4 >> 1) != 0;
-                qf[t] = make_float4(sc * (hiq ? up[0] : lo[0]), sc * (hiq ? up[1] : lo[1]), sc * (hiq ? up[2] : lo[2]), sc * (hiq ? up[3] : lo[3]));
-                gf[t] = make_float4(sigmoid_fast(hiq ? gup[0] : glo[0]), sigmoid_fast(hiq ? gup[1] : glo[1]),
-                                    sigmoid_fast(hiq ? gup[2] : glo[2]), sigmoid_fast(hiq ? gup[3] : glo[3]));
-            }
-            f32x4 o[2];
-            float l_tot[2], m_ref[2];
-            ta_keyloop<2, true>(Kl, Vt, kadd, qf, npad, ql, g4, o, l_tot, m_ref);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int v = qb * 32 + 16 * t + ql;
-                if (v < N) {
-                    const long pos = ending ? (((long)bb * N + v) * N + u) : (bu * N + v);
-                    float4* dst = reinterpret_cast<float4*>(og + pos * HC + h * C + 4 * g4);
-                    float* st = stats + (pos * H + h) * 2;
-                    const float il = 1.0f / l_tot[t];
-                    float4 mine = make_float4(gf[t].x * (o[t][0] * il), gf[t].y * (o[t][1] * il), gf[t].z * (o[t][2] * il), gf[t].w * (o[t][3] * il));
-                    float m_new = m_ref[t], l_new = l_tot[t];
-                    if (!first) {
-                        const float m0 = st[0], l0 = st[1];
-                        const float4 prev = *dst;
-                        const float M = fmaxf(m0, m_ref[t]);
-                        const float w0 = l0 * exp2f(m0 - M), w1 = l_tot[t] * exp2f(m_ref[t] - M);
-                        const float iw = 1.0f / (w0 + w1);
-                        const float a0 = w0 * iw, a1 = w1 * iw;
-                        mine = make_float4(a0 * prev.x + a1 * mine.x, a0 * prev.y + a1 * mine.y, a0 * prev.z + a1 * mine.z, a0 * prev.w + a1 * mine.w);
-                        m_new = M;
-                        l_new = w0 + w1;
-                    }
-                    *dst = mine;
-                    // the four lanes (g4) of a query read the statistics above before lane g4 = 0 replaces them: one wave, program order
-                    if (g4 == 0) { st[0] = m_new; st[1] = l_new; }
-                }
-            }
-        }
-    }
+    tri_attn_core_long_body<P, NW, true>(og, stats, pair, mask, wq, wk, wv, wg, bg, b, N, key0, klen, npad, first, H, ending);
 }
 
 template <int P, int NW, bool B3>
@@ -2457,7 +2352,7 @@ extern "C" int prd_tri_attn_core(float* og, const float* pair, const float* mask
     (void)variant;
 #endif
     if (plan.kind != TaKind::SHORT) return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(8, (tri_attn_core_long_kernel<PP, 8>)));
-    return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(12, (tri_attn_core_kernel<PP, 12, true, false>)));
+    return PRD_FOR_P(P, PP, PRD_TA_LAUNCH(12, (tri_attn_core_kernel<PP, 12>)));
 #undef PRD_TA_NOT_FUSED
 #undef PRD_TA_LAUNCH
 }

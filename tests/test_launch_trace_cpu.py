@@ -3,7 +3,8 @@ values of the host-only queries, held to a recording.  The trace build of the li
 -DPRD_LAUNCH_TRACE, build.py variant "trace") prints a line per launch instead of launching; tests/native/launch_trace.c walks the
 entry points over a sweep of shapes, arithmetics, switches and head layouts.  tests/golden/launch_trace.txt.xz is that output for the
 commit BEFORE the LDS sizes and the dispatch decisions were gathered into named host functions (only the trace #ifdef applied to it):
-a refactor of the launch sites must reproduce it line for line.  No device is touched."""
+a refactor of the launch sites must reproduce it line for line.  The fixture is still that pre-refactor recording, with one kernel
+renamed in it: tri_attn_core_kernel<P, 12, true, false> became <P, 12> when its two dead template parameters went.  No device is touched."""
 import lzma
 import os
 import re
