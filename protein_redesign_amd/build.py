@@ -22,6 +22,8 @@ HEADERS = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_launch.h"
 #   align    libprd_align.so (include/prd_align.h): superposition and TM-score of generated samples
 #   tmalign  libprd_tmalign.so (include/prd_tmalign.h): structural alignment of samples to a reference of another length
 #   quality  libprd_quality.so (include/prd_quality.h): lDDT and pair censuses of samples, no superposition
+#   condition  libprd_condition.so (include/prd_condition.h): the kept rows of structure-conditioned sampling (conditioning.py); the one
+#            side library the sampling loop itself calls, and only when a scaffold is given
 # csrc/prd_superpose.h is the fit that the two share: touching it makes both stale and no object of the denoiser.
 SideLib = collections.namedtuple("SideLib", "sources headers lib flag")
 _INCLUDE, PRD_SUPERPOSE_H = os.path.join(os.path.dirname(HERE), "include"), os.path.join(CSRC, "prd_superpose.h")
@@ -29,10 +31,12 @@ SIDE_LIBS = {
     "align": SideLib(["prd_align.hip"], [os.path.join(_INCLUDE, "prd_align.h"), PRD_SUPERPOSE_H], os.path.join(HERE, "libprd_align.so"), "--align"),
     "tmalign": SideLib(["prd_tmalign.hip"], [os.path.join(_INCLUDE, "prd_tmalign.h"), PRD_SUPERPOSE_H], os.path.join(HERE, "libprd_tmalign.so"), "--tmalign"),
     "quality": SideLib(["prd_quality.hip"], [os.path.join(_INCLUDE, "prd_quality.h")], os.path.join(HERE, "libprd_quality.so"), "--quality"),
+    "condition": SideLib(["prd_condition.hip"], [os.path.join(_INCLUDE, "prd_condition.h")], os.path.join(HERE, "libprd_condition.so"), "--condition"),
 }
 LIB_ALIGN, ALIGN_SOURCES = SIDE_LIBS["align"].lib, SIDE_LIBS["align"].sources
 LIB_TMALIGN, TMALIGN_SOURCES = SIDE_LIBS["tmalign"].lib, SIDE_LIBS["tmalign"].sources
 LIB_QUALITY, QUALITY_SOURCES = SIDE_LIBS["quality"].lib, SIDE_LIBS["quality"].sources
+LIB_CONDITION, CONDITION_SOURCES = SIDE_LIBS["condition"].lib, SIDE_LIBS["condition"].sources
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -215,6 +219,11 @@ def build_tmalign(force: bool = False, verbose: bool = True) -> str:
 def build_quality(force: bool = False, verbose: bool = True) -> str:
     """libprd_quality.so (include/prd_quality.h, protein_redesign_amd/quality.py)"""
     return build_side("quality", force, verbose)
+
+
+def build_condition(force: bool = False, verbose: bool = True) -> str:
+    """libprd_condition.so (include/prd_condition.h, protein_redesign_amd/conditioning.py)"""
+    return build_side("condition", force, verbose)
 
 
 def build_asan(verbose: bool = True) -> str:

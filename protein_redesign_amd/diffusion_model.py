@@ -27,6 +27,7 @@ from torch import nn
 from . import _lib, ops
 from .constants import ATOM_FEATURE_CARDS, BOND_FEATURE_CARDS, NUM_RESIDUE_CLASSES
 from .schedule import reverse_coefficients, schedule_tables
+from .conditioning import BATCH_KEY as SCAFFOLD_KEY, Scaffold, condition_rows_, level_table
 from .masking import MaskDraws, Redesign
 from .synthetic import NoiseSource
 from .trunk import Denoiser, Linear
@@ -417,9 +418,10 @@ class ProteinReDiffModel(_Base):
                                   + (": outside the operand range of the split arithmetic (include/prd_hip.h); set model.arithmetic = 'fp32' "
                                      "or nonfinite_policy = 'fp32'" if cur == 1 else ": the weights / inputs themselves produce inf or NaN"))
 
-    def predict_step(self, batch, batch_idx, redesign: Optional[Redesign] = None):
+    def predict_step(self, batch, batch_idx, redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None):
+        kw = {} if scaffold is None else {"scaffold": scaffold}
         with self.ema.average_parameters(self.parameters()):
-            return self.sample(batch, batch_idx=batch_idx, redesign=redesign)
+            return self.sample(batch, batch_idx=batch_idx, redesign=redesign, **kw)
 
     # ------------------------------------------------------------------ batch preparation (model.py:424-468)
     def _sources(self, b: int, batch_idx: Optional[int] = None) -> List[NoiseSource]:
@@ -499,6 +501,19 @@ class ProteinReDiffModel(_Base):
         if self.training_mode:
             raise ValueError("a redesign region applies to inference; under training_mode=True the training recipe draws its own masks")
         return spec
+
+    def _scaffold_spec(self, scaffold: Optional[Scaffold]) -> Optional[Scaffold]:
+        """The scaffold of a call: the keyword or None -- there is no attribute.  Conditioning holds rows to the input structure at
+        inference; the training recipe noises every row: a scaffold under ``training_mode=True`` is an error."""
+        if scaffold is None:
+            return None
+        if not isinstance(scaffold, Scaffold):
+            raise TypeError(f"scaffold must be a conditioning.Scaffold, got {type(scaffold).__name__}")
+        if self.training_mode:
+            raise ValueError("a scaffold conditions inference on the input structure; under training_mode=True it is refused")
+        if scaffold.start is not None and scaffold.start >= self.num_steps:
+            raise ValueError(f"Scaffold: start must be a level in [0, {self.num_steps - 1}] (num_steps = {self.num_steps}), got {scaffold.start}")
+        return scaffold
 
     def _redesign_mask(self, batch, spec: Redesign):
         """(extra, inv) of a design region, built on the device without a host synchronisation.  ``within`` / ``nearest``: ONE
@@ -645,9 +660,12 @@ class ProteinReDiffModel(_Base):
     # ------------------------------------------------------------------ reverse diffusion (model.py:377-422)
     @torch.inference_mode()
     def sample(self, batch, sources: Optional[Sequence] = None, batch_idx: Optional[int] = None, mask_draws: Optional[MaskDraws] = None,
-               redesign: Optional[Redesign] = None):
+               redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None):
+        """``scaffold`` (conditioning.Scaffold, keyword only): keep rows of the complex where the input structure has them and / or
+        start from the noised input (``ReverseDiffusion``); the positions then come back in the INPUT's frame."""
         self.check_widths()
         redesign = self._redesign_spec(redesign)        # deterministic: the fp32 repeat below prepares the same mask, nothing memoised
+        cond = {} if self._scaffold_spec(scaffold) is None else {"scaffold": scaffold}
         if sources is None:
             sources = self._sources(batch["atom_mask"].shape[0], batch_idx)
         if self.training_mode and mask_draws is None:
@@ -655,7 +673,7 @@ class ProteinReDiffModel(_Base):
         # the keyed generators are consumed by a loop: remember where they stood so that a repeat draws the same noise
         states = [s.g.get_state() if hasattr(s, "g") else None for s in sources]
         with _lib.arithmetic(self.arithmetic):
-            loop = ReverseDiffusion(self, batch, sources, mask_draws, redesign)
+            loop = ReverseDiffusion(self, batch, sources, mask_draws, redesign, **cond)
             loop.run()
             cur = _lib.arith()
             if self.nonfinite_policy == "off" or loop.finite():
@@ -672,7 +690,7 @@ class ProteinReDiffModel(_Base):
             self.arith_fallbacks += 1
             self.arithmetic = "fp32"
             with _lib.arithmetic("fp32"):
-                loop = ReverseDiffusion(self, batch, sources, mask_draws, redesign)
+                loop = ReverseDiffusion(self, batch, sources, mask_draws, redesign, **cond)
                 loop.run()
                 if loop.finite():
                     return loop.result()
@@ -692,11 +710,23 @@ class ReverseDiffusion:
     table.  ``z``, ``seq_t`` and the step counter ``t`` live on the device and are advanced by the
     kernels themselves, so ONE captured hipGraph of a whole step (network forward + reverse update)
     is replayed for every remaining step: no per-step host work and no ``(t == 0).all()``
-    device->host sync (model.py:415)."""
+    device->host sync (model.py:415).
+
+    ``scaffold`` (conditioning.Scaffold; beyond the reference): replacement conditioning in the centred frame.  The
+    rows K the spec keeps never follow the reverse update: the state entering the step with counter l has
+    ``z[K] = A[l] x0c[K] + S[l] eps_l[K]`` (x0c: ``batch["x"]`` minus its masked mean, A / S: the model's sqrt_alphas_cumprod /
+    sqrt_one_minus_alphas_cumprod, eps_l: mean-free noise of its own per level), and ``z[K] = x0c[K]`` after the last step; one
+    launch of prd_condition_rows after every boundary, inside the captured graph, does it (and, with ``sequence=True``, puts the known
+    residues' one-hot rows back, followed by one prd_single_init under the fused boundary).  ``start = L`` begins at level L from the
+    noised input and runs L + 1 steps on the noise rows the uninterrupted loop consumes from there.  ``result()`` is then in the
+    input's frame.  The conditioning noise -- per source L + 1 tensors [N,3] for the levels L .. 0 (L = T - 1 without ``start``), drawn
+    AFTER everything an unconditioned loop draws, so the other draws are what they were -- is a second device table
+    ``[L+1, b, N, 3]``: with a scaffold the loop's noise memory doubles."""
 
     def __init__(self, model: "ProteinReDiffModel", batch, sources: Optional[Sequence] = None, mask_draws: Optional[MaskDraws] = None,
-                 redesign: Optional[Redesign] = None):
+                 redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None):
         m = self.model = model
+        self.scaffold = scaffold = m._scaffold_spec(scaffold)
         if not m.setup_schedule:
             m.run_setup_schedule()
             m.setup_schedule = True
@@ -714,15 +744,23 @@ class ReverseDiffusion:
             noise = torch.stack([torch.stack([s.randn(N, 3) for _ in range(T - 1)]) for s in sources], dim=1)
         else:
             noise = torch.zeros(1, b, N, 3)
-        self.noise = noise.to(dev).contiguous()                      # [T-1, b, N, 3]
-        self.z = ops.remove_mean(z0.to(dev).contiguous(), self.mask)
-        seq_t = ops.remove_mean(s0.to(dev).contiguous(), self.rm)
+        # with a scaffold the tables go up from pinned staging, ordered on the current stream, so that a conditioned loop is set up
+        # without a host synchronisation; without one the uploads are the pageable copies they were
+        pinned = scaffold is not None and dev.type == "cuda"
+        up = self._upload = (lambda x: x.pin_memory().to(dev, non_blocking=True)) if pinned else (lambda x: x.to(dev))
+        self.noise = up(noise).contiguous()                          # [T-1, b, N, 3]
+        self.z = ops.remove_mean(up(z0).contiguous(), self.mask)
+        seq_t = ops.remove_mean(up(s0).contiguous(), self.rm)
         self.seq_t = (batch["residue_extra_mask"].unsqueeze(-1) * batch["residue_one_hot"]
                       + batch["residue_inv_extra_mask"].unsqueeze(-1) * seq_t).contiguous()
         self.static = m._static_inputs(batch)
+        self._first = (T - 1, 0)                # (counter, steps done) of a fresh loop
+        self.cond = None                        # the arguments of condition_rows_ after every boundary (None: nothing to hold)
         self.t = torch.full((b,), T - 1, dtype=torch.int64, device=dev)
+        if scaffold is not None:
+            self._condition(scaffold, sources, b, N, dev)
         self._init = (self.z.clone(), self.seq_t.clone())
-        self.steps_done = 0
+        self.steps_done = self._first[1]
         self.graph = None
         self.seq_pred = None
         # inputs of the coming step that the previous step's boundary kernel prepares (single, time embedding)
@@ -733,6 +771,41 @@ class ReverseDiffusion:
         self._seq_pred_buf = None               # logits of the last step (written by the step-boundary kernel)
         self.single_in, self.eb_in = m._step_inputs(self.static, self.seq_t, self.rm, self.t)
 
+    def _condition(self, scaffold: Scaffold, sources, b, N, dev):
+        """Set-up of a conditioned loop: x0c, centre, the kept rows K, the level table [T,2], the conditioning noise [L+1,b,N,3] (drawn
+        here, after every draw of an unconditioned loop; mean-removed once), the initial state and the first counter.  No host sync."""
+        m, batch, T = self.model, self.batch, self.T
+        L = T - 1 if scaffold.start is None else scaffold.start
+        x0 = batch["x"].to(torch.float32).contiguous()
+        self.x0c = ops.remove_mean(x0, self.mask)
+        valid = self.mask.unsqueeze(-1)
+        self.centre = (valid * x0).sum(dim=1, keepdim=True) / valid.sum(dim=1, keepdim=True)       # [b,1,3]: the masked mean
+        self._offset = valid * self.centre                                                         # what result() adds: valid rows only
+        self.keep = scaffold.rows(batch)                                                           # K [b,N] or None
+        batch[SCAFFOLD_KEY] = self.keep if self.keep is not None else torch.zeros_like(self.mask)
+        self.level = level_table({k: getattr(m, k) for k in ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod")})
+        draws = torch.stack([torch.stack([s.randn(N, 3) for _ in range(L + 1)]) for s in sources], dim=1)     # [L+1,b,N,3]: levels L .. 0
+        table = self._upload(draws.flip(0).contiguous())                                               # indexed by level
+        self.cond_noise = ops.remove_mean(table.view((L + 1) * b, N, 3), self.mask.repeat(L + 1, 1)).view(L + 1, b, N, 3)
+        seq = dict(seq0=batch["residue_one_hot"].to(torch.float32).contiguous(),
+                   keep_seq=batch["residue_extra_mask"].to(torch.float32).contiguous()) if scaffold.sequence else {}
+        held = dict(x0c=self.x0c, noise=self.cond_noise, level=self.level)
+        self.t.fill_(L)
+        self._first = (L, T - 1 - L)
+        # the initial state: with ``start`` every valid row is the noised input, otherwise the kept ones
+        first = self.mask if scaffold.start is not None else self.keep
+        if first is not None or seq:
+            condition_rows_(self.z, self.seq_t, self.t, keep_z=first, **(held if first is not None else {}), **seq)
+        if self.keep is not None or seq:
+            self.cond = dict(keep_z=self.keep, **(held if self.keep is not None else {}), **seq)
+
+    def _hold_rows(self):
+        """The kept rows back onto the noised input at the counter the boundary left (conditioning.condition_rows_); with the sequence
+        clamp under the fused boundary, the coming step's single input from the clamped seq_t."""
+        condition_rows_(self.z, self.seq_t, self.t, **self.cond)
+        if self.fused_boundary and self.cond.get("keep_seq") is not None:
+            ops.single_init(self.static["single"], self.seq_t, self.rm, self.model.embed_residue_type[1].weight, out=self.single_in)
+
     def _refresh_step_inputs(self):
         single, eb = self.model._step_inputs(self.static, self.seq_t, self.rm, self.t)
         self.single_in.copy_(single)
@@ -742,8 +815,8 @@ class ReverseDiffusion:
         """Back to step T-1 with the same initial noise (bench / repeated runs)."""
         self.z.copy_(self._init[0])
         self.seq_t.copy_(self._init[1])
-        self.t.fill_(self.T - 1)
-        self.steps_done = 0
+        self.t.fill_(self._first[0])
+        self.steps_done = self._first[1]
         self._refresh_step_inputs()
 
     def restart(self, step: int, z: torch.Tensor, seq_t: torch.Tensor):
@@ -756,6 +829,8 @@ class ReverseDiffusion:
         self.seq_t.copy_(seq_t.to(self.seq_t.device))
         self.t.fill_(self.T - 1 - step)
         self.steps_done = step
+        if self.cond is not None:               # the kept rows of the given state, at its level
+            condition_rows_(self.z, self.seq_t, self.t, **self.cond)
         self._refresh_step_inputs()
 
     def _enqueue_step(self):
@@ -765,6 +840,8 @@ class ReverseDiffusion:
         if not self.fused_boundary:             # the four separate launches (kept for A/B measurements: PRD_FUSED_BOUNDARY=0)
             noise_pred, seq_pred = m._network(self.batch, self.z, self.seq_t, self.mask, self.t, static=self.static)
             ops.reverse_update_(self.z, self.seq_t, self.t, noise_pred, seq_pred, self.noise, self.mask, m._coef, self.T)
+            if self.cond is not None:
+                self._hold_rows()
             return seq_pred
         eps_raw, seq_h = m._network(self.batch, self.z, self.seq_t, self.mask, self.t, static=self.static,
                                     step_inputs=(self.single_in, self.eb_in), raw_noise=True, defer_seq_head=True)
@@ -774,6 +851,8 @@ class ReverseDiffusion:
                            self.single_in, self.static["single"], self.rm, m.embed_residue_type[1].weight,
                            self.eb_in, m.embed_beta[0].weight, m.embed_beta[1].weight, self.sync,
                            seq_h=seq_h, w_seq=m.seq_mlp[3].weight)
+        if self.cond is not None:
+            self._hold_rows()
         return self._seq_pred_buf
 
     @torch.inference_mode()
@@ -783,7 +862,7 @@ class ReverseDiffusion:
             raise RuntimeError("all num_steps denoising steps already done; call reset()")
         if self.graph is not None:
             self.graph.replay()
-        elif self.model.use_hip_graph and self.steps_done >= 1:
+        elif self.model.use_hip_graph and self.steps_done >= 1 + self._first[1]:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self.seq_pred = self._enqueue_step()      # capture only; the replay below executes it
@@ -807,5 +886,8 @@ class ReverseDiffusion:
         return not bool(bad)
 
     def result(self):
-        """(positions in Angstrom, residue-masked logits) as in model.py:421-422."""
+        """(positions in Angstrom, residue-masked logits) as in model.py:421-422.  With a scaffold the valid rows come back in the
+        input's frame, ``10 (z + centre)``: the kept rows at the input's own coordinates, the rebuilt ones beside them."""
+        if self.scaffold is not None:
+            return 10.0 * (self.z + self._offset), self.rm.unsqueeze(-1) * self.seq_pred
         return 10.0 * self.z, self.rm.unsqueeze(-1) * self.seq_pred

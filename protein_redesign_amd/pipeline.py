@@ -490,9 +490,25 @@ def _structural_reference(align_to):
     return ref, ca
 
 
-def _references(model, data, redesign, align_to, correspondence, assess):
+def check_scaffold_structure(data: Mapping[str, Any], scaffold) -> None:
+    """ValueError unless the featurised complex carries what ``scaffold`` (conditioning.Scaffold) holds rows to: C-alpha coordinates
+    for any scaffold, ligand positions where the ligand is kept or the rows are chosen by their distance to it.  Host data only."""
+    from .conditioning import Scaffold
+    if not isinstance(scaffold, Scaffold):
+        raise TypeError(f"scaffold must be a conditioning.Scaffold, got {type(scaffold).__name__}")
+    what = _ca_trace_problem(data)
+    if what is not None:
+        raise ValueError("a scaffold keeps rows at, or starts from, the complex's own coordinates: " + what
+                         + "; an input without a structure cannot be conditioned on")
+    if scaffold.needs_ligand and (int(data.get("num_atoms", 0)) < 1 or "atom_pos" not in data
+                                  or torch.as_tensor(data["atom_pos"]).shape[0] < 1):
+        raise ValueError("Scaffold(ligand=True) and Scaffold.beyond need the ligand's coordinates: there is no ligand atom with a position")
+
+
+def _references(model, data, redesign, align_to, correspondence, assess, scaffold=None):
     """Stage (a) of generate_samples: every refusal that host data alone decides, in the order callers rely on, before ``model.device``
-    is read.  Returns (structural reference or None, index-wise alignment reference or None, quality reference or None, redesign spec)."""
+    is read; those of ``scaffold`` come after the references' and before the model's own design region is looked up.  Returns (structural reference or None, index-wise alignment reference or None, quality
+    reference or None, redesign spec)."""
     if correspondence not in ("index", "structure"):
         raise ValueError(f"correspondence must be 'index' or 'structure', got {correspondence!r}")
     struct_ref = _structural_reference(align_to) if correspondence == "structure" else None
@@ -504,22 +520,26 @@ def _references(model, data, redesign, align_to, correspondence, assess):
                              f"structure takes at most {MAX_N} (PRD_TMALIGN_MAX_N)")
     align_ref = _alignment_reference(data, align_to) if align_to is not None and struct_ref is None else None
     quality_ref = _quality_reference(data, assess) if assess is not None else None
+    if scaffold is not None:                    # before the model is asked for its own design region: host data alone decides
+        check_scaffold_structure(data, scaffold)
     spec = redesign if redesign is not None else getattr(model, "redesign", None)
     if spec is not None and spec.needs_structure:
         check_complex_structure(data)
     return struct_ref, align_ref, quality_ref, spec
 
 
-def _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device):
-    """Stage (b): the sampling loop, with no synchronisation beyond its copies to the host.  Returns (positions per batch -- left on the
+def _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device, scaffold=None):
+    """Stage (b): the sampling loop, with no synchronisation beyond its copies to the host; ``scaffold`` reaches ``model.sample`` only when
+    one is given.  Returns (positions per batch -- left on the
     device if ``keep_on_device``, for the stages that score them there --, logits per batch on the host, the first prepared batch)."""
     from .synthetic import NoiseSource, batch_to
     positions, logits, first_batch = [], [], None
+    cond = {} if scaffold is None else {"scaffold": scaffold}
     for start in range(0, num_samples, batch_size):
         idx = list(range(start, min(start + batch_size, num_samples)))
         batch = collate_fn([data] * len(idx))
         batch = batch_to({k: v for k, v in batch.items() if torch.is_tensor(v)}, device)
-        pos, lg = model.sample(batch, sources=[NoiseSource(seed, k) for k in idx], redesign=spec)
+        pos, lg = model.sample(batch, sources=[NoiseSource(seed, k) for k in idx], redesign=spec, **cond)
         if first_batch is None:
             first_batch = batch                 # sample() prepared it in place: it carries the mask that was used
         positions.append(pos if keep_on_device else pos.cpu())
@@ -587,7 +607,7 @@ def _decode(data, positions, logits, na, nr):
     return proteins, ligands
 
 
-def _write(output_dir, proteins, ligands, used_mask, alignment, quality):
+def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffold=None):
     """Stage (f): the files of ``output_dir``"""
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
@@ -608,12 +628,15 @@ def _write(output_dir, proteins, ligands, used_mask, alignment, quality):
             f.write("# " + " ".join(cols) + "\n")
             for k in range(len(proteins)):
                 f.write(" ".join(str(quality[c][k].item()) for c in cols) + "\n")
+    if scaffold is not None:
+        np.savez(out / "sample_scaffold.npz", keep=scaffold["keep"], ligand=scaffold["ligand"], sequence=scaffold["sequence"],
+                 start=-1 if scaffold["start"] is None else scaffold["start"])
 
 
 @torch.inference_mode()
 def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_size: int = 1, seed: int = 0,
                      output_dir: Optional[Union[str, Path]] = None, redesign=None, align_to=None, mirror: bool = True,
-                     correspondence: str = "index", assess=None):
+                     correspondence: str = "index", assess=None, scaffold=None):
     """Draw ``num_samples`` samples of one featurised complex ``data`` (the dict of ligand_to_data ∪ protein_to_data).
 
     Returns (positions [S,N,3] in Angstrom, logits [S,N,21], proteins, ligand_positions).  With ``output_dir`` the CA
@@ -665,16 +688,33 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     the same reason a mirror image scores like the original.  The return value gains one more trailing ``dict`` of numpy arrays, after
     the alignment dict when both are requested.  ``output_dir`` also receives ``sample_quality.npz`` (the dict) and
     ``sample_quality.txt``: a ``#`` line naming the columns, then one line per sample holding the scalar metrics in the order of
-    ``quality.SCALAR_COLUMNS`` (those present)."""
-    struct_ref, align_ref, quality_ref, spec = _references(model, data, redesign, align_to, correspondence, assess)
+    ``quality.SCALAR_COLUMNS`` (those present).
+
+    ``scaffold`` (conditioning.Scaffold, keyword only, default None: nothing below happens, every return value and file is what it was):
+    keep rows of the complex where the input has them -- the residues outside the design region, those beyond a radius of the ligand,
+    an explicit mask, optionally the ligand pose -- and / or start the loop from the input noised to a chosen level, and optionally
+    hold the known residues' sequence rows at every step (``diffusion_model.ReverseDiffusion``).  The samples then come back in the
+    INPUT's frame, the kept rows at the input's own coordinates (``align_to`` then moves them as it moves every row).  Refused, before anything is uploaded, for an input without
+    coordinates such as ``protein_from_sequence``, and for ``ligand=True`` / ``Scaffold.beyond`` without ligand positions.  The return
+    value gains one more trailing ``dict``, after all of the above: ``keep`` ([N] 0/1 over the collated row, the rows that were kept,
+    the same for every sample of the complex), ``ligand``, ``sequence`` and ``start`` of the spec.  ``output_dir`` also receives
+    ``sample_scaffold.npz`` with the same entries (``start`` is -1 there when it is None)."""
+    struct_ref, align_ref, quality_ref, spec = _references(model, data, redesign, align_to, correspondence, assess, scaffold)
     device = model.device
+    if scaffold is not None:
+        scaffold = scaffold.to(device)          # a keep mask is uploaded once, not per batch
     if spec is not None:
         spec = spec.to(device)                  # a positions mask is uploaded once, not per batch
     na, nr = int(data["num_atoms"]), int(data["num_residues"])
     scored = align_to is not None or assess is not None         # then the samples stay on the device until they are scored
-    drawn, logits, first_batch = _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device=scored)
+    drawn, logits, first_batch = _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device=scored, scaffold=scaffold)
     # every sample of the complex shares the mask: read from the first prepared batch, after the loop (no synchronisation inside it)
     used_mask = first_batch["residue_inv_extra_mask"][0].cpu().numpy() if spec is not None and first_batch is not None else None
+    kept = None
+    if scaffold is not None:                    # like the mask: read from the first prepared batch, after the loop
+        from .conditioning import BATCH_KEY
+        kept = {"keep": first_batch[BATCH_KEY][0].cpu().numpy(), "ligand": scaffold.ligand, "sequence": scaffold.sequence,
+                "start": scaffold.start}
     pos = torch.cat(drawn)
     quality = _assess(pos, first_batch, quality_ref, na, nr) if assess is not None else None
     pos, alignment = _superpose(pos, data, struct_ref, align_ref, mirror, na, nr) if align_to is not None else (pos, None)
@@ -683,6 +723,7 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         alignment = {k: float(v.cpu()) if k == "diversity" else v.cpu().numpy() for k, v in alignment.items()}
     proteins, ligands = _decode(data, positions, logits, na, nr)
     if output_dir is not None:
-        _write(output_dir, proteins, ligands, used_mask, alignment, quality)
+        _write(output_dir, proteins, ligands, used_mask, alignment, quality, kept)
     result = (positions, logits, proteins, ligands) + ((used_mask,) if spec is not None else ())
-    return result + ((alignment,) if alignment is not None else ()) + ((quality,) if quality is not None else ())
+    result = result + ((alignment,) if alignment is not None else ()) + ((quality,) if quality is not None else ())
+    return result + ((kept,) if kept is not None else ())
