@@ -24,6 +24,8 @@ HEADERS = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_launch.h"
 #   quality  libprd_quality.so (include/prd_quality.h): lDDT and pair censuses of samples, no superposition
 #   condition  libprd_condition.so (include/prd_condition.h): the kept rows of structure-conditioned sampling (conditioning.py); the one
 #            side library the sampling loop itself calls, and only when a scaffold is given
+#   sequence  libprd_sequence.so (include/prd_sequence.h): the sequence rules of sampling (sequence.py) -- the ruled rows of seq_t inside
+#            the loop, only when rules are given, and the decoding and census of generate_samples(decode=...)
 # csrc/prd_superpose.h is the fit that the two share: touching it makes both stale and no object of the denoiser.
 SideLib = collections.namedtuple("SideLib", "sources headers lib flag")
 _INCLUDE, PRD_SUPERPOSE_H = os.path.join(os.path.dirname(HERE), "include"), os.path.join(CSRC, "prd_superpose.h")
@@ -32,11 +34,13 @@ SIDE_LIBS = {
     "tmalign": SideLib(["prd_tmalign.hip"], [os.path.join(_INCLUDE, "prd_tmalign.h"), PRD_SUPERPOSE_H], os.path.join(HERE, "libprd_tmalign.so"), "--tmalign"),
     "quality": SideLib(["prd_quality.hip"], [os.path.join(_INCLUDE, "prd_quality.h")], os.path.join(HERE, "libprd_quality.so"), "--quality"),
     "condition": SideLib(["prd_condition.hip"], [os.path.join(_INCLUDE, "prd_condition.h")], os.path.join(HERE, "libprd_condition.so"), "--condition"),
+    "sequence": SideLib(["prd_sequence.hip"], [os.path.join(_INCLUDE, "prd_sequence.h")], os.path.join(HERE, "libprd_sequence.so"), "--sequence"),
 }
 LIB_ALIGN, ALIGN_SOURCES = SIDE_LIBS["align"].lib, SIDE_LIBS["align"].sources
 LIB_TMALIGN, TMALIGN_SOURCES = SIDE_LIBS["tmalign"].lib, SIDE_LIBS["tmalign"].sources
 LIB_QUALITY, QUALITY_SOURCES = SIDE_LIBS["quality"].lib, SIDE_LIBS["quality"].sources
 LIB_CONDITION, CONDITION_SOURCES = SIDE_LIBS["condition"].lib, SIDE_LIBS["condition"].sources
+LIB_SEQUENCE, SEQUENCE_SOURCES = SIDE_LIBS["sequence"].lib, SIDE_LIBS["sequence"].sources
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -224,6 +228,11 @@ def build_quality(force: bool = False, verbose: bool = True) -> str:
 def build_condition(force: bool = False, verbose: bool = True) -> str:
     """libprd_condition.so (include/prd_condition.h, protein_redesign_amd/conditioning.py)"""
     return build_side("condition", force, verbose)
+
+
+def build_sequence(force: bool = False, verbose: bool = True) -> str:
+    """libprd_sequence.so (include/prd_sequence.h, protein_redesign_amd/sequence.py)"""
+    return build_side("sequence", force, verbose)
 
 
 def build_asan(verbose: bool = True) -> str:

@@ -34,15 +34,15 @@ def level_table(tables: Mapping[str, torch.Tensor]) -> torch.Tensor:
     return torch.stack([tables["sqrt_alphas_cumprod"], tables["sqrt_one_minus_alphas_cumprod"]], dim=1).to(torch.float32).contiguous()
 
 
-def _tensor(t, name, shape, like, dtype=torch.float32):
+def _tensor(t, name, shape, like, dtype=torch.float32, runs="the conditioning runs", ref="the state"):
     if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
         raise ValueError(f"{name} must be a tensor of shape {tuple(shape)}, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
     if t.dtype != dtype:
         raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
     if not t.is_cuda:
-        raise RuntimeError(f"{name}: the conditioning runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+        raise RuntimeError(f"{name}: {runs} on the GPU only (got a CPU tensor); there is no CPU fallback")
     if like is not None and t.device != like.device:
-        raise ValueError(f"{name} is on {t.device}, the state on {like.device}")
+        raise ValueError(f"{name} is on {t.device}, {ref} on {like.device}")
     if not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
     return t

@@ -29,6 +29,7 @@ from .constants import ATOM_FEATURE_CARDS, BOND_FEATURE_CARDS, NUM_RESIDUE_CLASS
 from .schedule import reverse_coefficients, schedule_tables
 from .conditioning import BATCH_KEY as SCAFFOLD_KEY, Scaffold, condition_rows_, level_table
 from .masking import MaskDraws, Redesign
+from .sequence import BATCH_KEY as RULES_KEY, SequenceRules, constrain_rows_
 from .synthetic import NoiseSource
 from .trunk import Denoiser, Linear
 
@@ -418,8 +419,11 @@ class ProteinReDiffModel(_Base):
                                   + (": outside the operand range of the split arithmetic (include/prd_hip.h); set model.arithmetic = 'fp32' "
                                      "or nonfinite_policy = 'fp32'" if cur == 1 else ": the weights / inputs themselves produce inf or NaN"))
 
-    def predict_step(self, batch, batch_idx, redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None):
+    def predict_step(self, batch, batch_idx, redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None,
+                     sequence_rules: Optional[SequenceRules] = None):
         kw = {} if scaffold is None else {"scaffold": scaffold}
+        if sequence_rules is not None:
+            kw["sequence_rules"] = sequence_rules
         with self.ema.average_parameters(self.parameters()):
             return self.sample(batch, batch_idx=batch_idx, redesign=redesign, **kw)
 
@@ -514,6 +518,17 @@ class ProteinReDiffModel(_Base):
         if scaffold.start is not None and scaffold.start >= self.num_steps:
             raise ValueError(f"Scaffold: start must be a level in [0, {self.num_steps - 1}] (num_steps = {self.num_steps}), got {scaffold.start}")
         return scaffold
+
+    def _rules_spec(self, rules: Optional[SequenceRules]) -> Optional[SequenceRules]:
+        """The sequence rules of a call: the keyword or None -- there is no attribute.  Rules say what inference may design; the
+        training recipe learns from the data's own sequence: rules under ``training_mode=True`` are an error."""
+        if rules is None:
+            return None
+        if not isinstance(rules, SequenceRules):
+            raise TypeError(f"sequence_rules must be a sequence.SequenceRules, got {type(rules).__name__}")
+        if self.training_mode:
+            raise ValueError("sequence rules constrain what inference designs; under training_mode=True they are refused")
+        return rules
 
     def _redesign_mask(self, batch, spec: Redesign):
         """(extra, inv) of a design region, built on the device without a host synchronisation.  ``within`` / ``nearest``: ONE
@@ -660,12 +675,16 @@ class ProteinReDiffModel(_Base):
     # ------------------------------------------------------------------ reverse diffusion (model.py:377-422)
     @torch.inference_mode()
     def sample(self, batch, sources: Optional[Sequence] = None, batch_idx: Optional[int] = None, mask_draws: Optional[MaskDraws] = None,
-               redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None):
+               redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None, sequence_rules: Optional[SequenceRules] = None):
         """``scaffold`` (conditioning.Scaffold, keyword only): keep rows of the complex where the input structure has them and / or
-        start from the noised input (``ReverseDiffusion``); the positions then come back in the INPUT's frame."""
+        start from the noised input (``ReverseDiffusion``); the positions then come back in the INPUT's frame.  ``sequence_rules``
+        (sequence.SequenceRules, keyword only): the classes the ruled residues may take and the bias on their logits, applied to the
+        sequence state after every step and to the returned logits (``ReverseDiffusion``)."""
         self.check_widths()
         redesign = self._redesign_spec(redesign)        # deterministic: the fp32 repeat below prepares the same mask, nothing memoised
         cond = {} if self._scaffold_spec(scaffold) is None else {"scaffold": scaffold}
+        if self._rules_spec(sequence_rules) is not None:         # deterministic too: the repeat prepares the same tables
+            cond["sequence_rules"] = sequence_rules
         if sources is None:
             sources = self._sources(batch["atom_mask"].shape[0], batch_idx)
         if self.training_mode and mask_draws is None:
@@ -721,12 +740,22 @@ class ReverseDiffusion:
     noised input and runs L + 1 steps on the noise rows the uninterrupted loop consumes from there.  ``result()`` is then in the
     input's frame.  The conditioning noise -- per source L + 1 tensors [N,3] for the levels L .. 0 (L = T - 1 without ``start``), drawn
     AFTER everything an unconditioned loop draws, so the other draws are what they were -- is a second device table
-    ``[L+1, b, N, 3]``: with a scaffold the loop's noise memory doubles."""
+    ``[L+1, b, N, 3]``: with a scaffold the loop's noise memory doubles.
+
+    ``sequence_rules`` (sequence.SequenceRules; beyond the reference): the bias table goes up once and the ruled rows
+    (the design region, or every residue) are built once.  After every boundary, inside the captured graph, one launch of
+    prd_sequence_constrain rewrites the ruled rows of ``seq_t`` from the logits of that step: ``2 p - 1`` with p the softmax of
+    ``seq_pred + bias`` over the allowed classes, exactly -1 at a banned class; under the fused boundary one prd_single_init then
+    rebuilds the coming step's single input.  With ``Scaffold(sequence=True)`` as well the order is constrain, hold, one
+    prd_single_init: a held row wins.  A spec without any ban or bias (``inert``) rules no row by construction and launches nothing.
+    The initial ``seq_t`` is noise on the design rows, as the reference initialises it, and stays as it is.  ``result()`` returns the
+    logits with the rules applied on the ruled rows."""
 
     def __init__(self, model: "ProteinReDiffModel", batch, sources: Optional[Sequence] = None, mask_draws: Optional[MaskDraws] = None,
-                 redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None):
+                 redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None, sequence_rules: Optional[SequenceRules] = None):
         m = self.model = model
         self.scaffold = scaffold = m._scaffold_spec(scaffold)
+        self.sequence_rules = sequence_rules = m._rules_spec(sequence_rules)
         if not m.setup_schedule:
             m.run_setup_schedule()
             m.setup_schedule = True
@@ -744,9 +773,9 @@ class ReverseDiffusion:
             noise = torch.stack([torch.stack([s.randn(N, 3) for _ in range(T - 1)]) for s in sources], dim=1)
         else:
             noise = torch.zeros(1, b, N, 3)
-        # with a scaffold the tables go up from pinned staging, ordered on the current stream, so that a conditioned loop is set up
-        # without a host synchronisation; without one the uploads are the pageable copies they were
-        pinned = scaffold is not None and dev.type == "cuda"
+        # with a scaffold or sequence rules the tables go up from pinned staging, ordered on the current stream, so that such a loop is
+        # set up without a host synchronisation; without either the uploads are the pageable copies they were
+        pinned = (scaffold is not None or sequence_rules is not None) and dev.type == "cuda"
         up = self._upload = (lambda x: x.pin_memory().to(dev, non_blocking=True)) if pinned else (lambda x: x.to(dev))
         self.noise = up(noise).contiguous()                          # [T-1, b, N, 3]
         self.z = ops.remove_mean(up(z0).contiguous(), self.mask)
@@ -756,6 +785,11 @@ class ReverseDiffusion:
         self.static = m._static_inputs(batch)
         self._first = (T - 1, 0)                # (counter, steps done) of a fresh loop
         self.cond = None                        # the arguments of condition_rows_ after every boundary (None: nothing to hold)
+        self.rules = None                       # (bias table [1 or b,N,21], ruled rows [b,N]) of constrain_rows_ after every boundary
+        if sequence_rules is not None:          # an inert spec (no ban, no bias) rules no row by construction: nothing is launched for it
+            if not sequence_rules.inert:
+                self.rules = (sequence_rules.table(batch), sequence_rules.rows(batch))
+            batch[RULES_KEY] = self.rules[1] if self.rules is not None else torch.zeros_like(self.rm)
         self.t = torch.full((b,), T - 1, dtype=torch.int64, device=dev)
         if scaffold is not None:
             self._condition(scaffold, sources, b, N, dev)
@@ -799,11 +833,17 @@ class ReverseDiffusion:
         if self.keep is not None or seq:
             self.cond = dict(keep_z=self.keep, **(held if self.keep is not None else {}), **seq)
 
-    def _hold_rows(self):
-        """The kept rows back onto the noised input at the counter the boundary left (conditioning.condition_rows_); with the sequence
-        clamp under the fused boundary, the coming step's single input from the clamped seq_t."""
-        condition_rows_(self.z, self.seq_t, self.t, **self.cond)
-        if self.fused_boundary and self.cond.get("keep_seq") is not None:
+    def _hold_rows(self, seq_pred):
+        """After a boundary: the ruled rows of seq_t retaken under the sequence rules from the step's logits ``seq_pred``
+        (sequence.constrain_rows_), then the kept rows back onto the noised input at the counter the boundary left and, with the clamp,
+        onto the known sequence (conditioning.condition_rows_) -- a held row wins.  If either rewrote seq_t under the fused boundary,
+        ONE prd_single_init builds the coming step's single input from it."""
+        clamp = self.cond is not None and self.cond.get("keep_seq") is not None
+        if self.rules is not None:
+            constrain_rows_(self.seq_t, seq_pred, *self.rules)
+        if self.cond is not None:
+            condition_rows_(self.z, self.seq_t, self.t, **self.cond)
+        if self.fused_boundary and (clamp or self.rules is not None):
             ops.single_init(self.static["single"], self.seq_t, self.rm, self.model.embed_residue_type[1].weight, out=self.single_in)
 
     def _refresh_step_inputs(self):
@@ -840,8 +880,8 @@ class ReverseDiffusion:
         if not self.fused_boundary:             # the four separate launches (kept for A/B measurements: PRD_FUSED_BOUNDARY=0)
             noise_pred, seq_pred = m._network(self.batch, self.z, self.seq_t, self.mask, self.t, static=self.static)
             ops.reverse_update_(self.z, self.seq_t, self.t, noise_pred, seq_pred, self.noise, self.mask, m._coef, self.T)
-            if self.cond is not None:
-                self._hold_rows()
+            if self.cond is not None or self.rules is not None:
+                self._hold_rows(seq_pred.contiguous())
             return seq_pred
         eps_raw, seq_h = m._network(self.batch, self.z, self.seq_t, self.mask, self.t, static=self.static,
                                     step_inputs=(self.single_in, self.eb_in), raw_noise=True, defer_seq_head=True)
@@ -851,8 +891,8 @@ class ReverseDiffusion:
                            self.single_in, self.static["single"], self.rm, m.embed_residue_type[1].weight,
                            self.eb_in, m.embed_beta[0].weight, m.embed_beta[1].weight, self.sync,
                            seq_h=seq_h, w_seq=m.seq_mlp[3].weight)
-        if self.cond is not None:
-            self._hold_rows()
+        if self.cond is not None or self.rules is not None:
+            self._hold_rows(self._seq_pred_buf)
         return self._seq_pred_buf
 
     @torch.inference_mode()
@@ -887,7 +927,12 @@ class ReverseDiffusion:
 
     def result(self):
         """(positions in Angstrom, residue-masked logits) as in model.py:421-422.  With a scaffold the valid rows come back in the
-        input's frame, ``10 (z + centre)``: the kept rows at the input's own coordinates, the rebuilt ones beside them."""
+        input's frame, ``10 (z + centre)``: the kept rows at the input's own coordinates, the rebuilt ones beside them.  With sequence
+        rules the logits of the ruled rows are ``seq_pred + bias`` where allowed and exactly BANNED where banned, so that a host argmax
+        (pipeline.predict_seq) honours them: one elementwise expression here, after the loop."""
+        logits = self.rm.unsqueeze(-1) * self.seq_pred
+        if self.rules is not None:              # the ruled rows are residues: the mask above left them as they were
+            logits = self.sequence_rules.apply(logits, *self.rules)
         if self.scaffold is not None:
-            return 10.0 * (self.z + self._offset), self.rm.unsqueeze(-1) * self.seq_pred
-        return 10.0 * self.z, self.rm.unsqueeze(-1) * self.seq_pred
+            return 10.0 * (self.z + self._offset), logits
+        return 10.0 * self.z, logits

@@ -505,7 +505,26 @@ def check_scaffold_structure(data: Mapping[str, Any], scaffold) -> None:
         raise ValueError("Scaffold(ligand=True) and Scaffold.beyond need the ligand's coordinates: there is no ligand atom with a position")
 
 
-def _references(model, data, redesign, align_to, correspondence, assess, scaffold=None):
+def check_sequence_options(data: Mapping[str, Any], sequence_rules, decode) -> None:
+    """The refusals of ``sequence_rules`` / ``decode`` that host data alone decides: the types, a bias table that does not fit the
+    ``num_atoms + num_residues`` rows of the complex, and ``Decode(against="input")`` on an input whose ``residue_type`` is all unknown."""
+    from .sequence import Decode, SequenceRules
+    if sequence_rules is not None:
+        if not isinstance(sequence_rules, SequenceRules):
+            raise TypeError(f"sequence_rules must be a sequence.SequenceRules, got {type(sequence_rules).__name__}")
+        n = int(data["num_atoms"]) + int(data["num_residues"])
+        if sequence_rules.bias.shape[-2] != n:
+            raise ValueError(f"sequence_rules: a bias table of {sequence_rules.bias.shape[-2]} rows does not fit the complex's {n} "
+                             f"({int(data['num_atoms'])} ligand atoms + {int(data['num_residues'])} residues)")
+    if decode is not None:
+        if not isinstance(decode, Decode):
+            raise TypeError(f"decode must be a sequence.Decode, got {type(decode).__name__}")
+        if decode.against == "input" and not bool((torch.as_tensor(data["residue_type"]) >= 0).any()):
+            raise ValueError("Decode(against='input') counts the recovery of the input's sequence: every residue_type of the input is "
+                             "unknown (a protein without a sequence?)")
+
+
+def _references(model, data, redesign, align_to, correspondence, assess, scaffold=None, sequence_rules=None, decode=None):
     """Stage (a) of generate_samples: every refusal that host data alone decides, in the order callers rely on, before ``model.device``
     is read; those of ``scaffold`` come after the references' and before the model's own design region is looked up.  Returns (structural reference or None, index-wise alignment reference or None, quality
     reference or None, redesign spec)."""
@@ -522,29 +541,36 @@ def _references(model, data, redesign, align_to, correspondence, assess, scaffol
     quality_ref = _quality_reference(data, assess) if assess is not None else None
     if scaffold is not None:                    # before the model is asked for its own design region: host data alone decides
         check_scaffold_structure(data, scaffold)
+    if sequence_rules is not None or decode is not None:
+        check_sequence_options(data, sequence_rules, decode)
     spec = redesign if redesign is not None else getattr(model, "redesign", None)
     if spec is not None and spec.needs_structure:
         check_complex_structure(data)
     return struct_ref, align_ref, quality_ref, spec
 
 
-def _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device, scaffold=None):
-    """Stage (b): the sampling loop, with no synchronisation beyond its copies to the host; ``scaffold`` reaches ``model.sample`` only when
-    one is given.  Returns (positions per batch -- left on the
-    device if ``keep_on_device``, for the stages that score them there --, logits per batch on the host, the first prepared batch)."""
+def _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device, scaffold=None, sequence_rules=None, keep_logits=False):
+    """Stage (b): the sampling loop, with no synchronisation beyond its copies to the host; ``scaffold`` and ``sequence_rules`` reach
+    ``model.sample`` only when given.  Returns (positions per batch -- left on the
+    device if ``keep_on_device``, for the stages that score them there --, logits per batch on the host -- on the device if
+    ``keep_logits``, for the decoding there --, the first prepared batch, the keyed noise source of every sample as sample() left it)."""
     from .synthetic import NoiseSource, batch_to
-    positions, logits, first_batch = [], [], None
+    positions, logits, first_batch, used = [], [], None, []
     cond = {} if scaffold is None else {"scaffold": scaffold}
+    if sequence_rules is not None:
+        cond["sequence_rules"] = sequence_rules
     for start in range(0, num_samples, batch_size):
         idx = list(range(start, min(start + batch_size, num_samples)))
         batch = collate_fn([data] * len(idx))
         batch = batch_to({k: v for k, v in batch.items() if torch.is_tensor(v)}, device)
-        pos, lg = model.sample(batch, sources=[NoiseSource(seed, k) for k in idx], redesign=spec, **cond)
+        sources = [NoiseSource(seed, k) for k in idx]
+        pos, lg = model.sample(batch, sources=sources, redesign=spec, **cond)
         if first_batch is None:
             first_batch = batch                 # sample() prepared it in place: it carries the mask that was used
         positions.append(pos if keep_on_device else pos.cpu())
-        logits.append(lg.cpu())
-    return positions, logits, first_batch
+        logits.append(lg if keep_logits else lg.cpu())
+        used += sources
+    return positions, logits, first_batch, used
 
 
 def _assess(pos, first_batch, quality_ref, na, nr):
@@ -589,15 +615,56 @@ def _superpose(pos, data, struct_ref, align_ref, mirror, na, nr):
     return moved, alignment
 
 
-def _decode(data, positions, logits, na, nr):
-    """Stage (e): (proteins, ligand positions) of the samples, every protein with its decoded sequence; warns of undetermined residues"""
+def _decode_on_device(data, logits, sources, decode, ruled, design_mask, na, nr):
+    """Stage (e'), ``decode=``: one prd_sequence_decode over all samples (Gumbel noise of each sample's own keyed source when the
+    temperature is not 0), one prd_sequence_census over the residue rows, then the one copy to the host.  ``logits`` [S,N,21] on the
+    device, ``ruled``: sequence rules were applied to them (their banned entries hold BANNED).  Returns the dict of numpy arrays."""
+    from . import sequence as SQ
+    S, N, _ = logits.shape
+    device = logits.device
+    logits = logits.float().contiguous()
+    residues = torch.zeros(N)
+    residues[na: na + nr] = 1.0
+    residues = residues.to(device)
+    rows = residues.unsqueeze(0).expand(S, N).contiguous()
+    # the bans of the rules, read off the returned logits: one elementwise expression, no bias (it is in the logits already)
+    bans = torch.where(logits <= SQ.BANNED, torch.full_like(logits, SQ.BANNED), torch.zeros_like(logits)) if ruled else None
+    gumbel = None
+    if decode.temperature > 0.0:
+        gumbel = torch.stack([s.gumbel(N, SQ.N_CLS) for s in sources]).to(device)
+    tokens, logp, entropy = SQ.decode(logits, rows, bias=bans, gumbel=gumbel, temperature=decode.temperature)
+    ref = None
+    if decode.against == "input":
+        ref = torch.full((N,), -1, dtype=torch.int32)
+        ref[na: na + nr] = torch.as_tensor(data["residue_type"]).to(torch.int32) + 1        # class 0 is X
+        ref[ref == 0] = -1                                                                  # an unknown residue recovers nothing
+        ref = ref.to(device)
+    identity, recovery, profile = SQ.census(tokens, residues, ref)
+    tokens, logp, entropy = (t[:, na: na + nr].cpu().numpy() for t in (tokens, logp, entropy))
+    ident = identity.cpu().numpy().astype(np.float64) / nr
+    out = {"tokens": tokens, "sequences": ["".join(SQ.ALPHABET[c] if c >= 0 else "X" for c in row) for row in tokens], "logp": logp,
+           "entropy": entropy, "identity": ident,
+           "diversity": float(1.0 - (ident.sum() - np.trace(ident)) / (S * (S - 1))) if S > 1 else float("nan"),
+           "profile": profile[na: na + nr].cpu().numpy()}
+    if ref is not None:
+        known = ref[na: na + nr].cpu().numpy() >= 0
+        design = known & (design_mask[na: na + nr] > 0.5) if design_mask is not None else known
+        same = (tokens == (ref[na: na + nr].cpu().numpy())[None]) & known[None]
+        out["recovery"] = recovery.cpu().numpy().astype(np.float64) / max(int(known.sum()), 1)
+        out["recovery_design"] = (same & design[None]).sum(axis=1).astype(np.float64) / max(int(design.sum()), 1)
+    return out
+
+
+def _decode(data, positions, logits, na, nr, tokens=None):
+    """Stage (e): (proteins, ligand positions) of the samples, every protein with its decoded sequence -- the host argmax of the logits,
+    or ``tokens`` [S,nr] decoded on the device --; warns of undetermined residues"""
     template = Protein(np.asarray(data["residue_chain_index"]), np.asarray(data["residue_index"]),
                        np.asarray(data["residue_type"]), np.asarray(data["residue_atom_pos"], dtype=np.float32),
                        np.asarray(data["residue_atom_mask"], dtype=np.float32))
     proteins, ligands = [], []
-    for pos, lg in zip(positions, logits):
+    for k, (pos, lg) in enumerate(zip(positions, logits)):
         prot, lig = update_pos(template, na, pos)
-        seq = predict_seq(lg[na: na + nr])
+        seq = predict_seq(lg[na: na + nr]) if tokens is None else [("X" + "".join(RESIDUE_TYPES))[max(int(c), 0)] for c in tokens[k]]
         prot = dataclasses.replace(prot, aatype=np.array([RESIDUE_TYPES.index(s) if s != "X" else -1 for s in seq], dtype=np.int64))
         proteins.append(prot)
         ligands.append(lig)
@@ -607,7 +674,7 @@ def _decode(data, positions, logits, na, nr):
     return proteins, ligands
 
 
-def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffold=None):
+def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffold=None, sequences=None):
     """Stage (f): the files of ``output_dir``"""
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
@@ -631,12 +698,18 @@ def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffol
     if scaffold is not None:
         np.savez(out / "sample_scaffold.npz", keep=scaffold["keep"], ligand=scaffold["ligand"], sequence=scaffold["sequence"],
                  start=-1 if scaffold["start"] is None else scaffold["start"])
+    if sequences is not None:
+        np.savez(out / "sample_sequences.npz", **{k: (np.array(v) if k == "sequences" else v) for k, v in sequences.items()})
+        with open(out / "sample_sequences.fasta", "w") as f:
+            for k, seq in enumerate(sequences["sequences"]):
+                recovered = f" recovery={sequences['recovery'][k]:.4f}" if "recovery" in sequences else ""
+                f.write(f">sample_{k} mean_logp={float(sequences['logp'][k].mean()):.4f}{recovered}\n{seq}\n")
 
 
 @torch.inference_mode()
 def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_size: int = 1, seed: int = 0,
                      output_dir: Optional[Union[str, Path]] = None, redesign=None, align_to=None, mirror: bool = True,
-                     correspondence: str = "index", assess=None, scaffold=None):
+                     correspondence: str = "index", assess=None, scaffold=None, sequence_rules=None, decode=None):
     """Draw ``num_samples`` samples of one featurised complex ``data`` (the dict of ligand_to_data ∪ protein_to_data).
 
     Returns (positions [S,N,3] in Angstrom, logits [S,N,21], proteins, ligand_positions).  With ``output_dir`` the CA
@@ -698,16 +771,39 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     coordinates such as ``protein_from_sequence``, and for ``ligand=True`` / ``Scaffold.beyond`` without ligand positions.  The return
     value gains one more trailing ``dict``, after all of the above: ``keep`` ([N] 0/1 over the collated row, the rows that were kept,
     the same for every sample of the complex), ``ligand``, ``sequence`` and ``start`` of the spec.  ``output_dir`` also receives
-    ``sample_scaffold.npz`` with the same entries (``start`` is -1 there when it is None)."""
-    struct_ref, align_ref, quality_ref, spec = _references(model, data, redesign, align_to, correspondence, assess, scaffold)
+    ``sample_scaffold.npz`` with the same entries (``start`` is -1 there when it is None).
+
+    ``sequence_rules`` (sequence.SequenceRules, keyword only, default None: nothing changes): which residue classes the ruled residues
+    may take and an additive bias on their logits -- ``SequenceRules.for_residues(na, nr, omit="C", allow={57: "AVLI"}, bias={"G": 1.5})``
+    -- applied to the sequence state after every step of the loop and to the returned logits (``diffusion_model.ReverseDiffusion``), so
+    the rules show in ``logits`` and in the decoded proteins.  Refused, before the model is touched, if the table does not fit the
+    ``num_atoms + num_residues`` rows of the complex.  The return value gains no element for it.
+
+    ``decode`` (sequence.Decode, keyword only, default None: nothing below happens, decoding stays the host argmax): the logits stay on
+    the device until they are decoded there by ``protein_redesign_amd.sequence`` -- the argmax at ``temperature == 0``, otherwise a draw
+    from softmax(logits / temperature) by Gumbel-max, the noise coming from each sample's own keyed ``NoiseSource`` after ``sample()`` has
+    returned (every earlier draw is what it was) -- and the decoded sequences are counted there.  The proteins carry the decoded tokens
+    (class 0 is aatype -1, as above).  The return value gains one more trailing ``dict`` of numpy arrays, after all of the above:
+    ``tokens`` [S,nr], ``sequences`` (a list of str), ``logp`` [S,nr] (the log-probability of each token at temperature 1), ``entropy``
+    [S,nr] (nats), ``identity`` [S,S] (the fraction of the residues two samples share), ``diversity`` (1 - the mean off-diagonal
+    identity; NaN for S = 1), ``profile`` [nr,21] (how many samples carry each class) and, with ``against="input"``, ``recovery`` [S]
+    (the fraction of the input's known residues a sample reproduces) and ``recovery_design`` [S] (the same over the redesigned residues
+    only); ``against="input"`` is refused, before anything is uploaded, for an input whose ``residue_type`` is all unknown.
+    ``output_dir`` also receives ``sample_sequences.fasta`` (one record per sample, the header carrying the mean ``logp`` and the
+    recovery) and ``sample_sequences.npz`` (the dict)."""
+    struct_ref, align_ref, quality_ref, spec = _references(model, data, redesign, align_to, correspondence, assess, scaffold,
+                                                           sequence_rules, decode)
     device = model.device
+    if sequence_rules is not None:
+        sequence_rules = sequence_rules.to(device)      # the table is uploaded once, not per batch
     if scaffold is not None:
         scaffold = scaffold.to(device)          # a keep mask is uploaded once, not per batch
     if spec is not None:
         spec = spec.to(device)                  # a positions mask is uploaded once, not per batch
     na, nr = int(data["num_atoms"]), int(data["num_residues"])
     scored = align_to is not None or assess is not None         # then the samples stay on the device until they are scored
-    drawn, logits, first_batch = _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device=scored, scaffold=scaffold)
+    drawn, logits, first_batch, sources = _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device=scored,
+                                                scaffold=scaffold, sequence_rules=sequence_rules, keep_logits=decode is not None)
     # every sample of the complex shares the mask: read from the first prepared batch, after the loop (no synchronisation inside it)
     used_mask = first_batch["residue_inv_extra_mask"][0].cpu().numpy() if spec is not None and first_batch is not None else None
     kept = None
@@ -718,12 +814,19 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     pos = torch.cat(drawn)
     quality = _assess(pos, first_batch, quality_ref, na, nr) if assess is not None else None
     pos, alignment = _superpose(pos, data, struct_ref, align_ref, mirror, na, nr) if align_to is not None else (pos, None)
+    sequences = None
+    if decode is not None:
+        design = first_batch.get("residue_inv_extra_mask") if first_batch is not None else None      # the prepared batch carries it
+        design = design[0].cpu().numpy() if design is not None else None
+        on_device = torch.cat(logits)
+        sequences = _decode_on_device(data, on_device, sources, decode, sequence_rules is not None, design, na, nr)
+        logits = [on_device.cpu()]
     positions, logits = pos.cpu().numpy(), torch.cat(logits).numpy()       # the one copy of scored samples; unscored ones are on the host
     if alignment is not None:
         alignment = {k: float(v.cpu()) if k == "diversity" else v.cpu().numpy() for k, v in alignment.items()}
-    proteins, ligands = _decode(data, positions, logits, na, nr)
+    proteins, ligands = _decode(data, positions, logits, na, nr, sequences["tokens"] if sequences is not None else None)
     if output_dir is not None:
-        _write(output_dir, proteins, ligands, used_mask, alignment, quality, kept)
+        _write(output_dir, proteins, ligands, used_mask, alignment, quality, kept, sequences)
     result = (positions, logits, proteins, ligands) + ((used_mask,) if spec is not None else ())
     result = result + ((alignment,) if alignment is not None else ()) + ((quality,) if quality is not None else ())
-    return result + ((kept,) if kept is not None else ())
+    return result + ((kept,) if kept is not None else ()) + ((sequences,) if sequences is not None else ())

@@ -183,7 +183,7 @@ def deterministic_state_dict(spec: Mapping[str, torch.Tensor], seed: int = 1, st
     return out
 
 
-_torch_randperm, _torch_randn = torch.randperm, torch.randn   # bound early: harnesses may patch torch.*
+_torch_randperm, _torch_randn, _torch_rand = torch.randperm, torch.randn, torch.rand   # bound early: harnesses may patch torch.*
 
 
 class NoiseSource:
@@ -204,3 +204,10 @@ class NoiseSource:
 
     def randn(self, *shape) -> torch.Tensor:
         return _torch_randn(*shape, generator=self.g)
+
+    def gumbel(self, *shape) -> torch.Tensor:
+        """Standard Gumbel noise ``-log(-log u)``, u uniform on [tiny, 1): the argmax of ``logits / T + gumbel`` is a draw from
+        softmax(logits / T).  Consumed by the device decoding of ``pipeline.generate_samples`` AFTER the sampling loop has returned, so
+        every draw listed above is what it was."""
+        u = _torch_rand(*shape, generator=self.g).clamp_(min=torch.finfo(torch.float32).tiny)
+        return -torch.log(-torch.log(u))
