@@ -289,6 +289,9 @@ class ProteinReDiffModel(_Base):
         params = list(self.parameters())
         fused = bool(params) and all(p.is_cuda and p.is_floating_point() for p in params)
         optimizer = torch.optim.Adam(params, lr=self.learning_rate, **({"fused": True} if fused else {}))
+        # the fused step writes the parameters without moving their version counter: the packed weights (ops.cached_pack) are
+        # told here, whoever calls step()
+        optimizer.register_step_post_hook(ops.invalidate_packs)
         sched = torch.optim.lr_scheduler.LinearLR(optimizer, start_factor=1.0 / self.warmup_steps,
                                                   total_iters=self.warmup_steps - 1)
         return {"optimizer": optimizer, "lr_scheduler": {"scheduler": sched, "interval": "step"}}

@@ -485,7 +485,11 @@ def tri_attn_backward(dy, pair, mask, wts, H: int, c: int, *, ending: bool, og=N
     plan = tri_attn_bwd_plan(N, P, H, c)
     if og is None:                                                                                # forward recompute: gated head outputs
         og, lse = tri_attn_core_for_bwd(pair, mask, wts[:5], H, c, ending=ending, plan=plan)
-    arith = 0 if plan.core == "heads" else None     # general core: fp32 MFMA (a split-16 GEMM loses training-scale gradients to the fp16 subnormals)
+    # The two activation-gradient GEMMs multiply RAW gradient rows.  The row kernel (pair_linear: rows >= WGRAD_MIN_ROWS, its
+    # shapes) normalises every row before the split; where it declines, the GEMM runs on fp32 MFMA whatever the core: a split-16
+    # GEMM loses training-scale gradients to the fp16 subnormals (measured at 2 x 24^2 rows, near-init weights: the gradients
+    # of the outer-product / outer-linear weights 2e-4 .. 3e-4 off the oracle's, 1e-7 in fp32).
+    arith = 0
     dog = rows_linear(dy2, wts[5], transposed=True, fallback_arith=arith)                         # d og = dy W_o
     dqkvg = torch.empty(b, N, N, 4, HC, device=pair.device, dtype=F32)
     x = torch.empty_like(pair) if plan.core != "tuned" else None                                  # LN(pair), left by the core
@@ -1012,9 +1016,32 @@ def tri_attn_out(pair, og, wo, bo, *, residual: bool, out=None) -> torch.Tensor:
 # single-track composites (LayerNorm + GEMMs + softmax)
 # ---------------------------------------------------------------------------------------------------
 
+_PACK_GENERATION = 0        # bumped by invalidate_packs(): part of every cached_pack key
+
+
+def invalidate_packs(*_, **__) -> None:
+    """Every pack ``cached_pack`` holds, on every module, is rebuilt at its next use.  Host-only: one integer, no launch, no
+    synchronisation.  Call it after changing parameter values by a route ``cached_pack`` cannot see (its docstring lists them): a
+    foreign optimiser, a write through ``p.data``.  Takes and ignores any arguments, so it serves as an optimiser hook as it
+    stands: ``optimizer.register_step_post_hook(ops.invalidate_packs)`` -- what ``configure_optimizers`` does."""
+    global _PACK_GENERATION
+    _PACK_GENERATION += 1
+
+
 def cached_pack(module, name: str, params, build):
-    """Memoise a packed copy of several parameters on ``module`` until any of them changes in place."""
-    key = tuple((p.data_ptr(), p._version) for p in params)
+    """Memoise ``build()`` -- a packed / concatenated / folded copy of the parameters ``params`` -- on ``module``.
+
+    The pack is rebuilt when, since it was built,
+    * a source parameter was written in place through autograd's version counter (``p.copy_`` / ``p.mul_`` ... under ``no_grad``
+      or ``inference_mode``, ``load_state_dict``, the EMA swap, an unfused or foreach optimiser step),
+    * a source parameter moved (``model.to(device)``, ``load_state_dict(assign=True)``: another ``data_ptr``), or
+    * ``invalidate_packs()`` was called.  The optimiser of ``configure_optimizers`` calls it after every ``step()`` (a step post
+      hook, whoever steps it), and so does ``training.Fitter`` for any optimiser it drives.  This is what covers the fused Adam:
+      its single kernel writes the parameters WITHOUT moving their version counter.
+    NOT seen: writes through ``p.data`` (a view with a version counter of its own), a foreign fused optimiser, raw-pointer writes
+    -- call ``invalidate_packs()`` after them.  The key is host-side integers only (no launch, no synchronisation); a replayed
+    inference graph never comes here."""
+    key = (_PACK_GENERATION, *((p.data_ptr(), p._version) for p in params))
     cache = module.__dict__.setdefault("_prd_pack_cache", {})
     hit = cache.get(name)
     if hit is None or hit[0] != key:

@@ -803,6 +803,7 @@ class Fitter:
             opt.grad_scale, opt.found_inf = None, found         # fused Adam: no update, no step count, when found_inf == 1
             self._pending = found
         opt.step()
+        ops.invalidate_packs()              # any optimiser, hooked or not: the packed weights follow the step (ops.cached_pack)
         if guard:
             opt.found_inf = None
         if self.scheduler is not None:
