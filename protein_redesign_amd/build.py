@@ -26,16 +26,20 @@ HEADERS = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_launch.h"
 #            side library the sampling loop itself calls, and only when a scaffold is given
 #   sequence  libprd_sequence.so (include/prd_sequence.h): the sequence rules of sampling (sequence.py) -- the ruled rows of seq_t inside
 #            the loop, only when rules are given, and the decoding and census of generate_samples(decode=...)
-# csrc/prd_superpose.h is the fit that the two share: touching it makes both stale and no object of the denoiser.
+# csrc/prd_superpose.h is the fit that align and tmalign share: touching it makes both stale and no object of the denoiser.
+# csrc/prd_launch.h is the host half of every launch, theirs as the denoiser's: touching it makes every object stale.  Each has a
+# trace form as well (build_side(name, variant="trace"): objects under csrc/trace, libprd_<name>_trace.so), which build_trace_side links
+# tests/native/side_launch_trace.c against.
 SideLib = collections.namedtuple("SideLib", "sources headers lib flag")
-_INCLUDE, PRD_SUPERPOSE_H = os.path.join(os.path.dirname(HERE), "include"), os.path.join(CSRC, "prd_superpose.h")
-SIDE_LIBS = {
-    "align": SideLib(["prd_align.hip"], [os.path.join(_INCLUDE, "prd_align.h"), PRD_SUPERPOSE_H], os.path.join(HERE, "libprd_align.so"), "--align"),
-    "tmalign": SideLib(["prd_tmalign.hip"], [os.path.join(_INCLUDE, "prd_tmalign.h"), PRD_SUPERPOSE_H], os.path.join(HERE, "libprd_tmalign.so"), "--tmalign"),
-    "quality": SideLib(["prd_quality.hip"], [os.path.join(_INCLUDE, "prd_quality.h")], os.path.join(HERE, "libprd_quality.so"), "--quality"),
-    "condition": SideLib(["prd_condition.hip"], [os.path.join(_INCLUDE, "prd_condition.h")], os.path.join(HERE, "libprd_condition.so"), "--condition"),
-    "sequence": SideLib(["prd_sequence.hip"], [os.path.join(_INCLUDE, "prd_sequence.h")], os.path.join(HERE, "libprd_sequence.so"), "--sequence"),
-}
+_INCLUDE, PRD_SUPERPOSE_H, PRD_LAUNCH_H = os.path.join(os.path.dirname(HERE), "include"), os.path.join(CSRC, "prd_superpose.h"), os.path.join(CSRC, "prd_launch.h")
+
+
+def _side(name, *headers):
+    return SideLib([f"prd_{name}.hip"], [os.path.join(_INCLUDE, f"prd_{name}.h"), PRD_LAUNCH_H, *headers], os.path.join(HERE, f"libprd_{name}.so"), f"--{name}")
+
+
+SIDE_LIBS = {"align": _side("align", PRD_SUPERPOSE_H), "tmalign": _side("tmalign", PRD_SUPERPOSE_H), "quality": _side("quality"),
+             "condition": _side("condition"), "sequence": _side("sequence")}
 LIB_ALIGN, ALIGN_SOURCES = SIDE_LIBS["align"].lib, SIDE_LIBS["align"].sources
 LIB_TMALIGN, TMALIGN_SOURCES = SIDE_LIBS["tmalign"].lib, SIDE_LIBS["tmalign"].sources
 LIB_QUALITY, QUALITY_SOURCES = SIDE_LIBS["quality"].lib, SIDE_LIBS["quality"].sources
@@ -203,11 +207,13 @@ def build(force: bool = False, verbose: bool = True) -> str:
     return _build(VARIANTS["shipped"], SOURCES, force, verbose)
 
 
-def build_side(name: str, force: bool = False, verbose: bool = True) -> str:
+def build_side(name: str, force: bool = False, verbose: bool = True, variant: str = "shipped") -> str:
     """The side library ``name`` of SIDE_LIBS: its sources with the committed FLAGS and the shipped variant's extras, objects beside
-    the denoiser's.  Not a variant of libprd_hip.so: ``build()`` compiles none of it, and no side library compiles another."""
-    s = SIDE_LIBS[name]
-    return _build(Variant(VARIANTS["shipped"].cflags, [], CSRC, s.lib, None), s.sources, force, verbose)
+    the denoiser's.  Not a variant of libprd_hip.so: ``build()`` compiles none of it, and no side library compiles another.
+    ``variant="trace"``: the trace variant's flags and object directory, the library libprd_<name>_trace.so."""
+    s, v = SIDE_LIBS[name], VARIANTS[variant]
+    lib = s.lib if variant == "shipped" else s.lib.replace(".so", f"_{variant}.so")
+    return _build(Variant(v.cflags, v.ldflags, v.objdir, lib, None), s.sources, force, verbose)
 
 
 def build_align(force: bool = False, verbose: bool = True) -> str:
@@ -261,6 +267,18 @@ def build_trace(verbose: bool = True) -> str:
     return exe
 
 
+def build_trace_side(verbose: bool = True) -> str:
+    """The launch trace of the side libraries: the five libprd_<name>_trace.so and the driver tests/native/side_launch_trace.c linked
+    against them, which walks every entry point of their headers over the shapes at which a host decision changes.  Host code only;
+    tests/test_launch_trace_cpu.py compares the driver's output with the recorded one.  Returns the path of the driver binary."""
+    libs = [build_side(name, verbose=verbose, variant="trace") for name in SIDE_LIBS]
+    exe = os.path.join(VARIANTS["trace"].objdir, "side_launch_trace")
+    driver = os.path.join(os.path.dirname(HERE), "tests", "native", "side_launch_trace.c")
+    if _stale(exe, [driver] + libs + [s.headers[0] for s in SIDE_LIBS.values()]):
+        _run([_hipcc(), "-x", "c", driver, "-x", "none", "-O1", "-Wno-format-extra-args", "-o", exe] + libs + ["-Wl,-rpath," + HERE], verbose)
+    return exe
+
+
 def build_ab(verbose: bool = True) -> str:
     """libprd_hip_ab.so: the library with -DPRD_AB, i.e. INCLUDING the superseded kernels the shipped library leaves out (the
     first-generation split-16 attention cores of csrc/prd_tri.hip, in their three wave-count forms, and the fused form built on
@@ -285,6 +303,8 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--trace" in sys.argv:
         sys.exit(subprocess.call([build_trace()]))
+    if "--trace-side" in sys.argv:
+        sys.exit(subprocess.call([build_trace_side()]))
     for side, s in SIDE_LIBS.items():
         if s.flag in sys.argv:
             print(build_side(side, force="--force" in sys.argv))

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/prd_align.h"
+#include "prd_launch.h"
 #include "prd_superpose.h"
 
 namespace {
@@ -295,6 +296,10 @@ __global__ __launch_bounds__(256) void align_apply_kernel(float* __restrict__ ou
 }
 
 // ---- host side: the shape of a call ----------------------------------------------------------------------------------------------
+// dynamic LDS of a search workgroup: the three planes of both structures
+constexpr size_t al_lds_bytes(int N) { return (size_t)6 * N * sizeof(float); }
+static_assert(al_lds_bytes(PRD_ALIGN_MAX_N) + 1024 <= PRD_LDS_MAX, "the search kernel's LDS at the longest row the plan accepts, and its static wrec");
+
 struct AlignPlan {
     int ok, self, nm, nw, G, nstruct;
     long npairs;
@@ -365,31 +370,20 @@ extern "C" int prd_align_superimpose(float* tm, float* rmsd, float* rot, float* 
     float* planes = reinterpret_cast<float*>(static_cast<char*>(ws) + P.off_planes);
     float* rec = reinterpret_cast<float*>(static_cast<char*>(ws) + P.off_rec);
 
-    const size_t lds = (size_t)6 * N * sizeof(float);
-    if (P.npairs > 0 && lds > 48 * 1024) {              // before anything is enqueued: a refusal leaves nothing launched
-        const hipError_t ea = hipFuncSetAttribute((const void*)align_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  6 * PRD_ALIGN_MAX_N * (int)sizeof(float));
-        if (ea != hipSuccess) return (int)ea;
-    }
-    hipLaunchKernelGGL(align_compact_kernel, dim3(P.nstruct), dim3(AL_COMPACT_WG), 0, stream, planes, hdr, x, x_struct_stride, x_row_stride,
-                       self ? x : y, self ? x_struct_stride : y_struct_stride, self ? x_row_stride : y_row_stride, mask, S, N);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    if (P.npairs > 0) {
-        hipLaunchKernelGGL(align_search_kernel, dim3((unsigned)(P.npairs * P.nm), P.G), dim3(64 * P.nw), lds, stream, rec, planes, hdr, S, R, N,
-                           self ? 1 : 0, mode, P.nm, P.G);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
+    const size_t lds = al_lds_bytes(N);
+    if (P.npairs > 0) PRD_TRY(prd_lds_ready<align_search_kernel>(lds));     // before anything is enqueued: a refusal leaves nothing launched
+    PRD_TRY(prd_launch<align_compact_kernel>(dim3(P.nstruct), dim3(AL_COMPACT_WG), 0, stream, planes, hdr, x, x_struct_stride, x_row_stride,
+                                             self ? x : y, self ? x_struct_stride : y_struct_stride, self ? x_row_stride : y_row_stride, mask, S, N));
+    if (P.npairs > 0)
+        PRD_TRY(prd_launch<align_search_kernel>(dim3((unsigned)(P.npairs * P.nm), P.G), dim3(64 * P.nw), lds, stream, rec, planes, hdr, S, R, N,
+                                                self ? 1 : 0, mode, P.nm, P.G));
     const long nblocks = P.npairs + (self ? S : 0);
-    hipLaunchKernelGGL(align_finalize_kernel, dim3((unsigned)nblocks), dim3(64), 0, stream, tm, rmsd, rot, trans, mirrored, rec, planes, hdr, S, R, N,
-                       self ? 1 : 0, P.nm, P.G, P.npairs);
-    return (int)hipGetLastError();
+    return prd_launch<align_finalize_kernel>(dim3((unsigned)nblocks), dim3(64), 0, stream, tm, rmsd, rot, trans, mirrored, rec, planes, hdr, S, R, N,
+                                             self ? 1 : 0, P.nm, P.G, P.npairs);
 }
 
 extern "C" int prd_align_apply(float* out, const float* pos, const float* rot, const float* trans, int S, int N, hipStream_t stream) {
     if (!out || !pos || !rot || !trans || S <= 0 || N <= 0) return PRD_ALIGN_ERR_ARG;
     if (S > 65535) return PRD_ALIGN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(align_apply_kernel, dim3((N + 255) / 256, S), dim3(256), 0, stream, out, pos, rot, trans, N);
-    return (int)hipGetLastError();
+    return prd_launch<align_apply_kernel>(dim3((N + 255) / 256, S), dim3(256), 0, stream, out, pos, rot, trans, N);
 }

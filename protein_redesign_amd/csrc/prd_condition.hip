@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/prd_condition.h"
+#include "prd_launch.h"
 
 namespace {
 
@@ -62,7 +63,6 @@ extern "C" int prd_condition_rows(float* z, float* seq_t, const int64_t* t, cons
     if (b > PRD_CONDITION_MAX_B || N > PRD_CONDITION_MAX_N) return PRD_CONDITION_ERR_UNSUPPORTED;
     if (!keep_z && !keep_seq) return 0;
     const int per = N * (3 + (keep_seq ? n_cls : 0));           // <= 24 * 2^24 < 2^31
-    hipLaunchKernelGGL(condition_rows_kernel, dim3((per + C_THREADS - 1) / C_THREADS, b), dim3(C_THREADS), 0, stream, z, seq_t, t, x0c,
-                       keep_z, noise, level, seq0, keep_seq, b, N, n_cls, levels);
-    return (int)hipGetLastError();
+    return prd_launch<condition_rows_kernel>(dim3((per + C_THREADS - 1) / C_THREADS, b), dim3(C_THREADS), 0, stream, z, seq_t, t, x0c,
+                                             keep_z, noise, level, seq0, keep_seq, b, N, n_cls, levels);
 }

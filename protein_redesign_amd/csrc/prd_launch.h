@@ -1,20 +1,32 @@
-// Host half of every denoiser kernel launch (libprd_hip.so): the checked launch, the pair_dim dispatch and the launch geometry.
-// Host code only -- nothing here reaches a kernel.  The side libraries (prd_align.hip, prd_tmalign.hip) do not include it.
+// Host half of every kernel launch of the project -- the denoiser (libprd_hip.so) and the five side libraries (prd_align.hip,
+// prd_tmalign.hip, prd_quality.hip, prd_condition.hip, prd_sequence.hip): the checked launch, the raise of a kernel's dynamic-LDS limit,
+// the memset ahead of a launch, the pair_dim dispatch and the launch geometry.  Host code only -- nothing here reaches a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <mutex>
 
 // ---- 1. the launch ---------------------------------------------------------------------------------------------------------------
 // Dynamic LDS up to PRD_LDS_DEFAULT_LIMIT needs no attribute; a launch that asks for more first raises the kernel's limit to the
-// hardware maximum, once per process and kernel (thread-safe: std::call_once; not a stream operation, so it is legal during hipGraph
-// capture).  The result of the raise is kept: if it failed, nothing is launched and every call returns that error.
+// hardware maximum less the kernel's static LDS, once per process and kernel (thread-safe: std::call_once; not a stream operation, so
+// it is legal during hipGraph capture).  The result of the raise is kept: if it failed, nothing is launched and every call returns that
+// error.  prd_launch makes the raise itself; an entry point with several launches calls prd_lds_ready ahead of its first one, so that
+// a refusal leaves nothing launched.  PRD_LDS_MAX is the one limit raised to: a source whose kernels take dynamic LDS shows that its
+// largest size fits, with room for whatever the kernel declares statically.
 constexpr size_t PRD_LDS_DEFAULT_LIMIT = 48 * 1024;
 constexpr int PRD_LDS_MAX = 160 * 1024;
 
+// an entry point with several launches returns the first non-zero result and launches nothing after it
+#define PRD_TRY(launch)                                                                                         \
+    do {                                                                                                        \
+        const int prd_e_ = (launch);                                                                            \
+        if (prd_e_) return prd_e_;                                                                              \
+    } while (0)
+
 #ifdef PRD_LAUNCH_TRACE
-// The trace build (build.py: variant "trace"; tests/native/launch_trace.c): a launch prints one line -- kernel, grid, block, LDS bytes and
-// every argument (integers and floats by value, pointers by address, structures as their bytes in hex) -- and returns 0.  No HIP function
-// is called, so every host decision above a launch can be compared between two trees on a machine without a GPU.
+// The trace build (build.py: variant "trace"; tests/native/launch_trace.c for the denoiser, side_launch_trace.c for the side libraries): a
+// launch prints one line -- kernel, grid, block, LDS bytes and every argument (integers and floats by value, pointers by address,
+// structures as their bytes in hex) -- and returns 0; the raise is a no-op and the memset a line of its own.  No HIP function is
+// called, so every host decision above a launch can be compared between two trees on a machine without a GPU.
 #include <cxxabi.h>
 #include <cstdio>
 #include <cstdlib>
@@ -62,27 +74,42 @@ static int prd_launch(dim3 grid, dim3 block, size_t lds, hipStream_t, Args... ar
     free(full);
     return 0;
 }
+template <auto Kernel>
+static int prd_lds_ready(size_t) {
+    return 0;
+}
+// the memset that precedes a launch: one line "M address value bytes"
+static int prd_memset_async(void* ptr, int value, size_t bytes, hipStream_t) {
+    printf("M %p %d %zu\n", ptr, value, bytes);
+    return 0;
+}
 #else
+// Kernel may be launched with lds bytes of dynamic LDS: 0, or the kept hipError_t of the raise
+template <auto Kernel>
+static int prd_lds_ready(size_t lds) {
+    if (lds <= PRD_LDS_DEFAULT_LIMIT) return 0;
+    static std::once_flag once;
+    static hipError_t raised = hipSuccess;
+    std::call_once(once, [] {           // static and dynamic LDS share the 160 KiB: a limit that leaves the static part no room is refused
+        hipFuncAttributes attr;
+        raised = hipFuncGetAttributes(&attr, (const void*)Kernel);
+        if (raised == hipSuccess)
+            raised = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PRD_LDS_MAX - (int)attr.sharedSizeBytes);
+    });
+    return (int)raised;
+}
 // launches Kernel<<<grid, block, lds, stream>>>(args...); returns 0 or the hipError_t of the raise / the launch
 template <auto Kernel, class... Args>
 static int prd_launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
-    if (lds > PRD_LDS_DEFAULT_LIMIT) {
-        static std::once_flag once;
-        static hipError_t raised = hipSuccess;
-        std::call_once(once, [] { raised = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PRD_LDS_MAX); });
-        if (raised != hipSuccess) return (int)raised;
-    }
+    PRD_TRY(prd_lds_ready<Kernel>(lds));
     hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
     return (int)hipGetLastError();
 }
+// the memset that precedes a launch
+static int prd_memset_async(void* ptr, int value, size_t bytes, hipStream_t stream) {
+    return (int)hipMemsetAsync(ptr, value, bytes, stream);
+}
 #endif
-
-// an entry point with several launches returns the first non-zero result and launches nothing after it
-#define PRD_TRY(launch)                                                                                         \
-    do {                                                                                                        \
-        const int prd_e_ = (launch);                                                                            \
-        if (prd_e_) return prd_e_;                                                                              \
-    } while (0)
 
 // ---- 2. run-time value -> compile-time constant ------------------------------------------------------------------------------------
 // PRD_FOR_P(P, PP, expr) evaluates expr once with `constexpr int PP` bound to 64 or 32 (pair_dim is validated by the caller), so a

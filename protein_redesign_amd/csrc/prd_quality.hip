@@ -13,6 +13,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/prd_quality.h"
+#include "prd_launch.h"
 
 namespace {
 
@@ -161,9 +162,8 @@ extern "C" int prd_quality_lddt(int* preserved, int* total, const float* x, long
     if (!preserved || !total || !y || !row_mask || !col_mask || y_row_stride < 3) return PRD_QUALITY_ERR_ARG;
     const int refused = quality_refuse(x, x_struct_stride, x_row_stride, radius, S, N);
     if (refused) return refused;
-    hipLaunchKernelGGL(quality_lddt_kernel, dim3((N + Q_ROWS - 1) / Q_ROWS, S), dim3(Q_COLS), 0, stream, preserved, total, x, x_struct_stride,
-                       x_row_stride, y, y_row_stride, row_mask, col_mask, radius * radius, N);
-    return (int)hipGetLastError();
+    return prd_launch<quality_lddt_kernel>(dim3((N + Q_ROWS - 1) / Q_ROWS, S), dim3(Q_COLS), 0, stream, preserved, total, x, x_struct_stride,
+                                           x_row_stride, y, y_row_stride, row_mask, col_mask, radius * radius, N);
 }
 
 extern "C" int prd_quality_contacts(int* count, float* nearest, const float* x, long long x_struct_stride, int x_row_stride,
@@ -172,9 +172,7 @@ extern "C" int prd_quality_contacts(int* count, float* nearest, const float* x, 
     if (!count || !nearest || !a_mask || !b_mask) return PRD_QUALITY_ERR_ARG;
     const int refused = quality_refuse(x, x_struct_stride, x_row_stride, cutoff, S, N);
     if (refused) return refused;
-    const hipError_t e = hipMemsetAsync(count, 0, (size_t)S * sizeof(int), stream);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(quality_contacts_kernel, dim3((N + Q_ROWS - 1) / Q_ROWS, S), dim3(Q_COLS), 0, stream, count, nearest, x, x_struct_stride,
-                       x_row_stride, a_mask, b_mask, exclude, cutoff * cutoff, N);
-    return (int)hipGetLastError();
+    PRD_TRY(prd_memset_async(count, 0, (size_t)S * sizeof(int), stream));
+    return prd_launch<quality_contacts_kernel>(dim3((N + Q_ROWS - 1) / Q_ROWS, S), dim3(Q_COLS), 0, stream, count, nearest, x, x_struct_stride,
+                                               x_row_stride, a_mask, b_mask, exclude, cutoff * cutoff, N);
 }

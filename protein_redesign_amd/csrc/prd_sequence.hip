@@ -15,6 +15,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/prd_sequence.h"
+#include "prd_launch.h"
 
 namespace {
 
@@ -182,9 +183,7 @@ extern "C" int prd_sequence_constrain(float* seq_t, const float* logits, const f
     if (bias && bias_b != 1 && bias_b != b) return PRD_SEQUENCE_ERR_ARG;
     if (!rows) return 0;
     if (!seq_t || !logits) return PRD_SEQUENCE_ERR_ARG;
-    hipLaunchKernelGGL(constrain_kernel, dim3((N + Q_ROWS - 1) / Q_ROWS, b), dim3(Q_THREADS), 0, stream, seq_t, logits, bias, rows, N, n_cls,
-                       bias_b);
-    return (int)hipGetLastError();
+    return prd_launch<constrain_kernel>(dim3((N + Q_ROWS - 1) / Q_ROWS, b), dim3(Q_THREADS), 0, stream, seq_t, logits, bias, rows, N, n_cls, bias_b);
 }
 
 extern "C" int prd_sequence_decode(int32_t* tokens, float* logp, float* entropy, const float* logits, const float* bias, const float* rows,
@@ -192,9 +191,8 @@ extern "C" int prd_sequence_decode(int32_t* tokens, float* logp, float* entropy,
     if (const int r = refuse(S, PRD_SEQUENCE_MAX_S, N, n_cls)) return r;
     if (bias && bias_b != 1 && bias_b != S) return PRD_SEQUENCE_ERR_ARG;
     if (!tokens || !logp || !entropy || !logits || !rows) return PRD_SEQUENCE_ERR_ARG;
-    hipLaunchKernelGGL(decode_kernel, dim3((N + Q_ROWS - 1) / Q_ROWS, S), dim3(Q_THREADS), 0, stream, tokens, logp, entropy, logits, bias,
-                       rows, gumbel, inv_temperature, N, n_cls, bias_b);
-    return (int)hipGetLastError();
+    return prd_launch<decode_kernel>(dim3((N + Q_ROWS - 1) / Q_ROWS, S), dim3(Q_THREADS), 0, stream, tokens, logp, entropy, logits, bias, rows,
+                                     gumbel, inv_temperature, N, n_cls, bias_b);
 }
 
 extern "C" int prd_sequence_census(int32_t* identity, int32_t* recovery, int32_t* profile, const int32_t* tokens, const int32_t* ref_tokens,
@@ -204,7 +202,5 @@ extern "C" int prd_sequence_census(int32_t* identity, int32_t* recovery, int32_t
     if ((recovery == nullptr) != (ref_tokens == nullptr)) return PRD_SEQUENCE_ERR_ARG;
     const int pairs = S * (S + (ref_tokens ? 1 : 0));             // <= 4096 * 4097; with the profile's blocks below 2^31
     const int blocks = pairs + (N * n_cls + Q_WAVE - 1) / Q_WAVE;
-    hipLaunchKernelGGL(census_kernel, dim3(blocks), dim3(Q_WAVE), 0, stream, identity, recovery, profile, tokens, ref_tokens, mask, S, N, n_cls,
-                       pairs);
-    return (int)hipGetLastError();
+    return prd_launch<census_kernel>(dim3(blocks), dim3(Q_WAVE), 0, stream, identity, recovery, profile, tokens, ref_tokens, mask, S, N, n_cls, pairs);
 }

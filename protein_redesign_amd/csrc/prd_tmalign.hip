@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/prd_tmalign.h"
+#include "prd_launch.h"
 #include "prd_superpose.h"
 
 namespace {
@@ -342,12 +343,17 @@ struct Lds {
     int *prev, *bestmap;
     unsigned char *secx, *secy;
 };
-__host__ __device__ inline size_t ta_lds_bytes(int Nx, int Ny, bool refine) {
+__host__ __device__ constexpr size_t ta_lds_bytes(int Nx, int Ny, bool refine) {
     size_t b = refine ? (size_t)3 * (Nx + 1) * sizeof(double) : 0;
     b += (size_t)3 * (Nx + Ny) * sizeof(float) + (size_t)(refine ? 4 : 2) * Nx * sizeof(int);
     if (refine) b += (size_t)3 * (Nx + 1) + Nx + Ny;
     return (b + 15) & ~(size_t)15;
 }
+// (the size grows with both lengths and the refine workgroup's is the larger: the longest rows the plan accepts bound every launch;
+// 1024: more than the static wrec and nslot of the two kernels, which share the 160 KiB)
+static_assert(ta_lds_bytes(PRD_TMALIGN_MAX_N, PRD_TMALIGN_MAX_N, true) + 1024 <= PRD_LDS_MAX &&
+                  ta_lds_bytes(PRD_TMALIGN_MAX_N, PRD_TMALIGN_MAX_N, false) + 1024 <= PRD_LDS_MAX,
+              "the refine and search kernels' LDS at the longest rows the plan accepts");
 TA_DEV Lds ta_carve(unsigned char* base, int Nx, int Ny, bool refine, int* nslot) {
     Lds l;
     unsigned char* p = base;
@@ -690,29 +696,14 @@ extern "C" int prd_tmalign_align(float* tm, float* rmsd, float* rot, float* tran
     unsigned* dirs = reinterpret_cast<unsigned*>(w + P.off_dirs);
 
     const size_t lds_refine = ta_lds_bytes(Nx, Ny, true), lds_search = ta_lds_bytes(Nx, Ny, false);
-    if (lds_refine > 48 * 1024) {                       // before anything is enqueued: a refusal leaves nothing launched
-        const hipError_t ea = hipFuncSetAttribute((const void*)tmalign_refine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)ta_lds_bytes(PRD_TMALIGN_MAX_N, PRD_TMALIGN_MAX_N, true));
-        if (ea != hipSuccess) return (int)ea;
-    }
-    if (lds_search > 48 * 1024) {
-        const hipError_t ea = hipFuncSetAttribute((const void*)tmalign_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)ta_lds_bytes(PRD_TMALIGN_MAX_N, PRD_TMALIGN_MAX_N, false));
-        if (ea != hipSuccess) return (int)ea;
-    }
-    hipLaunchKernelGGL(tmalign_compact_kernel, dim3(S + R), dim3(TA_COMPACT_WG), 0, stream, px, py, hdr, cposx, idxy, x, x_struct_stride,
-                       x_row_stride, mask_x, y, y_struct_stride, y_row_stride, mask_y, S, Nx, Ny);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(tmalign_refine_kernel, dim3((unsigned)P.nprob), dim3(TA_WG), lds_refine, stream, rec1, maps1, dirs, px, py, hdr, R, Nx, Ny,
-                       P.nm);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(tmalign_search_kernel, dim3((unsigned)P.npm), dim3(TA_WG), lds_search, stream, rec2, maps2, rec1, maps1, px, py, hdr, R, Nx,
-                       Ny, P.nm);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(tmalign_finalize_kernel, dim3((unsigned)P.npairs), dim3(64), 0, stream, tm, rmsd, rot, trans, n_aligned, mirrored, map, rec2,
-                       maps2, px, py, hdr, cposx, idxy, R, Nx, Ny, P.nm);
-    return (int)hipGetLastError();
+    PRD_TRY(prd_lds_ready<tmalign_refine_kernel>(lds_refine));      // before anything is enqueued: a refusal leaves nothing launched
+    PRD_TRY(prd_lds_ready<tmalign_search_kernel>(lds_search));
+    PRD_TRY(prd_launch<tmalign_compact_kernel>(dim3(S + R), dim3(TA_COMPACT_WG), 0, stream, px, py, hdr, cposx, idxy, x, x_struct_stride,
+                                               x_row_stride, mask_x, y, y_struct_stride, y_row_stride, mask_y, S, Nx, Ny));
+    PRD_TRY(prd_launch<tmalign_refine_kernel>(dim3((unsigned)P.nprob), dim3(TA_WG), lds_refine, stream, rec1, maps1, dirs, px, py, hdr, R, Nx, Ny,
+                                              P.nm));
+    PRD_TRY(prd_launch<tmalign_search_kernel>(dim3((unsigned)P.npm), dim3(TA_WG), lds_search, stream, rec2, maps2, rec1, maps1, px, py, hdr, R, Nx,
+                                              Ny, P.nm));
+    return prd_launch<tmalign_finalize_kernel>(dim3((unsigned)P.npairs), dim3(64), 0, stream, tm, rmsd, rot, trans, n_aligned, mirrored, map, rec2,
+                                               maps2, px, py, hdr, cposx, idxy, R, Nx, Ny, P.nm);
 }

@@ -173,14 +173,14 @@ def test_header_parses_with_the_derived_binding():
     assert conditioning.ABI_VERSION == conditioning._DEFINES["VERSION"] == 100 and conditioning.N_CLS == 21
     assert conditioning._DEFINES["ERR_ARG"] == -1 and conditioning._DEFINES["ERR_UNSUPPORTED"] == -3
     with open(os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_condition.hip")) as f:
-        assert "prd_launch.h" not in f.read()
+        assert '#include "prd_launch.h"' in f.read()         # the host half of its launch is the project's one
 
 
 def test_side_libs_has_the_entry_and_the_other_builds_issue_what_they_issued(monkeypatch):
     s, q = build.SIDE_LIBS["condition"], build.SIDE_LIBS["quality"]
     assert s.sources == ["prd_condition.hip"] == build.CONDITION_SOURCES and s.flag == "--condition"
     assert s.lib == build.LIB_CONDITION == os.path.join(ROOT, "protein_redesign_amd", "libprd_condition.so")
-    assert s.headers == [os.path.join(ROOT, "include", "prd_condition.h")]
+    assert s.headers == [os.path.join(ROOT, "include", "prd_condition.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
     assert [x.replace("condition", "quality") for x in (s.sources[0], s.headers[0], s.lib, s.flag)] == [q.sources[0], q.headers[0], q.lib, q.flag]
     monkeypatch.delenv("HIPCC", raising=False)
     monkeypatch.setattr(build, "_stale", lambda out, deps: True)

@@ -1,6 +1,6 @@
-"""CPU: the host half of the denoiser's kernel launches (protein_redesign_amd/csrc/prd_launch.h) -- that it is the only place that raises
-a kernel's dynamic-LDS limit or launches a kernel, that every denoiser object and no side library depends on it, and that its launch
-geometry is the arithmetic the launch sites spelled out before the header existed."""
+"""CPU: the host half of every kernel launch (protein_redesign_amd/csrc/prd_launch.h) -- that it is the only place that raises a kernel's
+dynamic-LDS limit or launches a kernel, for the denoiser and for the side libraries, that every object of either depends on it, and
+that its launch geometry is the arithmetic the launch sites spelled out before the header existed."""
 import os
 import re
 import subprocess
@@ -39,24 +39,27 @@ def test_one_raise_one_launcher():
     # one definition of the geometry
     for fn in ("grid_for", "prd_rows_per_head", "prd_rows_per_head_xcd8"):
         assert [n for n, t in files.items() if re.search(r"\b(?:int|long)\s+%s\s*\(" % fn, t)] == ["prd_launch.h"], fn
-    # every denoiser source includes the header, no side library does
+    # every denoiser source includes the header, and so does every side source: the same holds for them (prd_superpose.h is device code)
     for src in build.SOURCES:
         assert '#include "prd_launch.h"' in files[src], src
     for name in SIDE:
         with open(os.path.join(CSRC, name)) as f:
-            assert "prd_launch.h" not in f.read(), name
+            text = f.read()
+        assert ('#include "prd_launch.h"' in text) == name.endswith(".hip"), name
+        for word in ("hipFuncSetAttribute", "hipLaunchKernelGGL", "<<<", "hipGetLastError", "hipMemsetAsync", "std::once_flag"):
+            assert word not in text, (name, word)
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-def test_the_launch_header_makes_every_denoiser_object_stale_and_no_side_library(monkeypatch):
+def test_the_launch_header_makes_every_object_stale(monkeypatch):
     """``_stale`` is the real one and no compiler runs: csrc/prd_launch.h is given the newest time stamp, and a command that is recorded
     makes its output newer still, as the compiler would have."""
     build.build(verbose=False)
-    build.build_align(verbose=False)
-    build.build_tmalign(verbose=False)
+    for side in build.SIDE_LIBS:
+        build.build_side(side, verbose=False)
     header, real, written = os.path.join(CSRC, "prd_launch.h"), os.path.getmtime, []
-    assert header in build.HEADERS and all(header not in s.headers for s in build.SIDE_LIBS.values())
-    newest = max(real(p) for p in (build.LIB, build.LIB_ALIGN, build.LIB_TMALIGN)) + 10.0
+    assert header in build.HEADERS and all(header in s.headers for s in build.SIDE_LIBS.values())
+    newest = max(real(p) for p in [build.LIB] + [s.lib for s in build.SIDE_LIBS.values()]) + 10.0
     monkeypatch.setattr(os.path, "getmtime", lambda p: newest + 10.0 * (1 + written.index(p)) if p in written else newest if p == header else real(p))
 
     class Touching(Recorder):
@@ -65,9 +68,13 @@ def test_the_launch_header_makes_every_denoiser_object_stale_and_no_side_library
             return super().__call__(kind, cmd, *a, **kw)
     rec = Touching(execute=False)
     rec.install(monkeypatch)
-    build.build_align(verbose=False)
-    build.build_tmalign(verbose=False)
-    assert rec.cmds == []
+    for side, s in build.SIDE_LIBS.items():          # a side library: its one object, then its link, and nothing of another library
+        src, lib = "{ROOT}/protein_redesign_amd/csrc/" + s.sources[0], s.lib.replace(ROOT, "{ROOT}")
+        build.build_side(side, verbose=False)
+        assert [c[-3:] for c in rec.cmds] == [[src, "-o", src.replace(".hip", ".o")], ["-o", lib, src.replace(".hip", ".o")]], side
+        rec.cmds = []
+        build.build_side(side, verbose=False)
+        assert rec.cmds == []
     build.build(verbose=False)
     objs = ["{ROOT}/protein_redesign_amd/csrc/" + s.replace(".hip", ".o") for s in build.SOURCES]
     assert len(build.SOURCES) == 9

@@ -110,7 +110,8 @@ def test_side_libs_has_the_entry_and_the_other_builds_issue_what_they_issued(mon
     s = build.SIDE_LIBS["quality"]
     assert s.sources == ["prd_quality.hip"] == build.QUALITY_SOURCES and s.flag == "--quality"
     assert s.lib == build.LIB_QUALITY == os.path.join(ROOT, "protein_redesign_amd", "libprd_quality.so")
-    assert s.headers == [os.path.join(ROOT, "include", "prd_quality.h")]        # the shared fit of the other two is not its concern
+    # its own header and the host half of its launches; the shared fit of the other two is not its concern
+    assert s.headers == [os.path.join(ROOT, "include", "prd_quality.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
     monkeypatch.delenv("HIPCC", raising=False)
     monkeypatch.setattr(build, "_stale", lambda out, deps: True)
     rec = Recorder(execute=False)

@@ -242,14 +242,14 @@ def test_header_parses_with_the_derived_binding():
     assert SQ.ABI_VERSION == SQ._DEFINES["VERSION"] == 100 and SQ._DEFINES["ERR_ARG"] == -1 and SQ._DEFINES["ERR_UNSUPPORTED"] == -3
     assert (SQ._DEFINES["MAX_B"], SQ._DEFINES["MAX_N"], SQ._DEFINES["MAX_S"]) == (65535, 16777216, 4096)
     with open(os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_sequence.hip")) as f:
-        assert "prd_launch.h" not in f.read()
+        assert '#include "prd_launch.h"' in f.read()         # the host half of its launch is the project's one
 
 
 def test_side_libs_has_the_entry_and_the_other_builds_issue_what_they_issued(monkeypatch):
     s, q = build.SIDE_LIBS["sequence"], build.SIDE_LIBS["condition"]
     assert s.sources == ["prd_sequence.hip"] == build.SEQUENCE_SOURCES and s.flag == "--sequence"
     assert s.lib == build.LIB_SEQUENCE == os.path.join(ROOT, "protein_redesign_amd", "libprd_sequence.so")
-    assert s.headers == [os.path.join(ROOT, "include", "prd_sequence.h")]
+    assert s.headers == [os.path.join(ROOT, "include", "prd_sequence.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
     assert [x.replace("sequence", "condition") for x in (s.sources[0], s.headers[0], s.lib, s.flag)] == [q.sources[0], q.headers[0], q.lib, q.flag]
     monkeypatch.delenv("HIPCC", raising=False)
     monkeypatch.setattr(build, "_stale", lambda out, deps: True)
