@@ -353,9 +353,13 @@ PRD_DEV int h2_slot(int row, int j) {
     return j ^ ((row >> 1) & (SL - 1));           // SL = 8: rows 2a, 2a+1 differ in bit 3 of the bank-group index already
 }
 // G row pieces (2 x 16 bytes each) in flight per thread before the first split / LDS write, as in stage_weight_cll.  (Measured:
-// the prologue of a row kernel is NOT these round trips -- pair_tail 10.0k -> 8.8k cycles for 151 KB on 768 threads, while an
-// L2-warm copy of the same bytes takes 4.1k, 3.2k with global_load_lds: tools/ubench/lds_fill_bench.hip.  The image is L2-cold
-// at kernel start -- the previous kernel streamed 80-130 MB through the 4 MB L2s -- and 32 CUs of an XCD ask for the same lines.)
+// G = 1 -> 4 took the prologue of pair_tail from 10.0k to 8.8k cycles for 151 KB on 768 threads, while an L2-warm copy of the same
+// bytes takes 4.1k, 3.2k with global_load_lds: tools/ubench/lds_fill_bench.hip.  The image is L2-cold at kernel start -- the previous
+// kernel streamed 80-130 MB through the 4 MB L2s -- and 32 CUs of an XCD ask for the same lines.  That is not ONE cold fetch,
+// though: a prologue built from these helpers is a CHAIN of cold round trips, one per staged operand, because each call compiles to
+// loads -> s_waitcnt vmcnt -> convert -> ds_write before the next call's loads are issued; G shortens one trip of the chain, not the
+// chain.  The kernels of the sampling step stage with the issue / commit pairs below (StageH2 ...), which request every operand
+// before the first wait; these loop forms stay for the backward kernels and the other head layouts.)
 template <int K>
 PRD_DEV void stage_weight_h2_rows(u32x4* Wh, int nout, int row0, const float* __restrict__ W, int nrows, int ldw, int tid, int nthreads,
                                   float scale) {
@@ -458,6 +462,196 @@ PRD_DEV void stage_weight_h2_nat(u32x4* Wh, const float* __restrict__ W, int nou
         }
     }
 }
+// ---- issue / commit staging -----------------------------------------------------------------------------------------------
+// The same LDS images as the loop helpers above, byte for byte, in two halves: issue() does the global loads of one operand into a
+// small register struct -- unconditional, the piece index clamped to piece 0 for a thread without a piece, so that the vmcnt
+// accounting is exact -- and commit() does the scale, split2h, slot swizzle and LDS write, in the expressions of the loop form.
+// Sizes and the thread count are template parameters: the piece list unrolls fully, and with __launch_bounds__(NT) the predicates
+// of whole rounds fold away.  A prologue reads: every issue() of every matrix and vector, stage_issue_fence(), every commit(),
+// __syncthreads() -- one cold round trip instead of one per operand; hipcc places the descending vmcnt waits between the commits.
+// An optional operand that is absent is issued from another operand's (valid) address and not committed, or committed as zeros.
+PRD_DEV void stage_issue_fence() { __builtin_amdgcn_sched_barrier(0); }        // no commit arithmetic is scheduled among the loads
+// The base of an issue(), made opaque: a load through a `const __restrict__` kernel argument is a load from constant memory to hipcc,
+// tied to nothing -- it sinks such loads across the fence to their first use, which rebuilds the chain of round trips (seen in the
+// assembly of pair_tail_h2_kernel: W_1's loads landed among the commits).  A pointer that came out of an asm statement is an
+// ordinary one, and its loads keep their place before the fence.  The base is wave-uniform: it stays in scalar registers.
+// (Not in an unoptimised device compile -- the launch-trace library, whose device code never runs: there every value lives in
+// vector registers, which the scalar constraint cannot take, and nothing is moved anyway.)
+typedef const float __attribute__((address_space(1))) * prd_gptr;                 // (global memory: what the asm statement forgets)
+typedef const f32x4 __attribute__((address_space(1))) * prd_gptr4;
+PRD_DEV prd_gptr stage_base(const float* p) {
+#ifdef __OPTIMIZE__
+    asm("" : "+s"(p));
+#endif
+    return (prd_gptr)p;
+}
+
+// stage_weight_h2_rows<K> of NROWS rows (stage_weight_h2<K>: row0 = 0, nout = NROWS) on NT threads
+template <int K, int NROWS, int NT>
+struct StageH2 {
+    static constexpr int S = K / 16, TOTAL = NROWS * S * 2, NP = (TOTAL + NT - 1) / NT;
+    f32x4 g0[NP], g1[NP];
+    PRD_DEV void issue(const float* Wg, int ldw, int tid) {
+        const prd_gptr W = stage_base(Wg);
+#pragma unroll
+        for (int u = 0; u < NP; ++u) {
+            const int idx = tid + u * NT;
+            const int ic = idx < TOTAL ? idx : 0;               // clamped: unconditional loads
+            const int o = ic / (2 * S), rem = ic - o * (2 * S), st = rem >> 1, h = rem & 1;
+            g0[u] = *(prd_gptr4)(W + (size_t)o * ldw + 16 * st + 4 * h);        // CLL elements 8st .. 8st+3
+            g1[u] = *(prd_gptr4)(W + (size_t)o * ldw + 16 * st + 8 + 4 * h);    // 8st+4 .. 8st+7
+        }
+    }
+    PRD_DEV void commit(u32x4* Wh, int nout, int row0, int tid, float scale) const {
+#pragma unroll
+        for (int u = 0; u < NP; ++u) {
+            const int idx = tid + u * NT;
+            if (idx < TOTAL) {
+                const int o = idx / (2 * S), rem = idx - o * (2 * S), st = rem >> 1, h = rem & 1;
+                const float v[8] = {scale * g0[u].x, scale * g0[u].y, scale * g0[u].z, scale * g0[u].w,
+                                    scale * g1[u].x, scale * g1[u].y, scale * g1[u].z, scale * g1[u].w};
+                u32x4 ph, pl;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    unsigned a, b;
+                    split2h(v[2 * q], v[2 * q + 1], a, b);
+                    ph[q] = a;
+                    pl[q] = b;
+                }
+                const int slot = h2_slot<K>(row0 + o, 2 * st + h);
+                Wh[(size_t)(row0 + o) * (K / 8) + slot] = ph;
+                Wh[(size_t)(nout + row0 + o) * (K / 8) + slot] = pl;
+            }
+        }
+    }
+};
+// stage_weight_h2_nat (runtime nout, K) in chunks of NPB pieces per thread, the stated in-flight budget: chunk c covers the pieces
+// tid + (c NPB + u) NT.  A kernel issues chunk 0 of its matrices with everything else and loops over the rest.
+template <int NT, int NPB>
+struct StageH2Nat {
+    f32x4 g0[NPB], g1[NPB];
+    static PRD_DEV int chunks(int nout, int K) { return (nout * (K / 8) + NPB * NT - 1) / (NPB * NT); }
+    PRD_DEV void issue(const float* Wg, int nout, int K, int ldw, int k0, int tid, int chunk) {
+        const prd_gptr W = stage_base(Wg);
+        const int SL = K / 8, total = nout * SL;
+#pragma unroll
+        for (int u = 0; u < NPB; ++u) {
+            const int idx = tid + (chunk * NPB + u) * NT;
+            const int ic = idx < total ? idx : 0;
+            const int o = ic / SL, j = ic - o * SL;
+            g0[u] = *(prd_gptr4)(W + (size_t)o * ldw + k0 + 8 * j);
+            g1[u] = *(prd_gptr4)(W + (size_t)o * ldw + k0 + 8 * j + 4);
+        }
+    }
+    PRD_DEV void commit(u32x4* Wh, int nout, int K, int tid, float scale, int chunk) const {
+        const int SL = K / 8, total = nout * SL;
+#pragma unroll
+        for (int u = 0; u < NPB; ++u) {
+            const int idx = tid + (chunk * NPB + u) * NT;
+            if (idx < total) {
+                const int o = idx / SL, j = idx - o * SL;
+                const float v[8] = {g0[u].x, g0[u].y, g0[u].z, g0[u].w, g1[u].x, g1[u].y, g1[u].z, g1[u].w};
+                u32x4 ph, pl;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    unsigned a_, b_;
+                    split2h(scale * v[2 * q], scale * v[2 * q + 1], a_, b_);
+                    ph[q] = a_;
+                    pl[q] = b_;
+                }
+                const int slot = j ^ (o & 15);
+                Wh[(size_t)o * SL + slot] = ph;
+                Wh[(size_t)(nout + o) * SL + slot] = pl;
+            }
+        }
+    }
+};
+// stage_vec_cll of a C-channel vector.  issue(): v must be readable (the caller passes another operand for an absent one);
+// commit(have = false) writes the zeros stage_vec_cll writes for a null vector.
+template <int C, int NT>
+struct StageVec {
+    static constexpr int NP = (C + NT - 1) / NT;
+    float x[NP];
+    PRD_DEV void issue(const float* vg, int tid) {
+        const prd_gptr v = stage_base(vg);
+#pragma unroll
+        for (int u = 0; u < NP; ++u) {
+            const int c = tid + u * NT;
+            x[u] = v[c < C ? c : 0];
+        }
+    }
+    PRD_DEV void commit(float* vl, int tid, float scale = 1.0f, bool have = true) const {
+#pragma unroll
+        for (int u = 0; u < NP; ++u) {
+            const int c = tid + u * NT;
+            if (c < C) {
+                const int f = c >> 2, e = c & 3;
+                vl[(f & 1) * (C / 2) + (f >> 1) * 4 + e] = have ? scale * x[u] : 0.f;
+            }
+        }
+    }
+};
+// `nrows` <= MAXR consecutive C-channel rows, v + h C -> vl + h C, each as stage_vec_cll (the rows of a bias head: the count is a
+// runtime value under a compile-time bound, the rows past it are neither loaded nor written)
+template <int C, int MAXR, int NT>
+struct StageVecRows {
+    static constexpr int NP = (C * MAXR + NT - 1) / NT;
+    float x[NP];
+    PRD_DEV void issue(const float* vg, int nrows, int tid) {
+        const prd_gptr v = stage_base(vg);
+#pragma unroll
+        for (int u = 0; u < NP; ++u) {
+            const int i = tid + u * NT;
+            x[u] = v[i < nrows * C ? i : 0];
+        }
+    }
+    PRD_DEV void commit(float* vl, int nrows, int tid) const {
+#pragma unroll
+        for (int u = 0; u < NP; ++u) {
+            const int i = tid + u * NT;
+            if (i < nrows * C) {
+                const int h = i / C, c = i - h * C;
+                const int f = c >> 2, e = c & 3;
+                vl[h * C + (f & 1) * (C / 2) + (f >> 1) * 4 + e] = x[u];
+            }
+        }
+    }
+};
+// the weight image of an attention core: four C-row operands (one head's slices of four projection matrices, row pitch K) at rows
+// 0, C, 2C, 3C of one [4 C]-row image, each with its own scale
+template <int K, int C, int NT>
+struct StageH2x4 {
+    StageH2<K, C, NT> s[4];
+    PRD_DEV void issue(const float* w0, const float* w1, const float* w2, const float* w3, int tid) {
+        s[0].issue(w0, K, tid); s[1].issue(w1, K, tid); s[2].issue(w2, K, tid); s[3].issue(w3, K, tid);
+    }
+    PRD_DEV void commit(u32x4* Wh, int tid, float sc0, float sc1, float sc2, float sc3) const {
+        s[0].commit(Wh, 4 * C, 0, tid, sc0); s[1].commit(Wh, 4 * C, C, tid, sc1);
+        s[2].commit(Wh, 4 * C, 2 * C, tid, sc2); s[3].commit(Wh, 4 * C, 3 * C, tid, sc3);
+    }
+};
+// plain copy of n floats (runtime n) in chunks of NPB per thread
+template <int NT, int NPB>
+struct StageRaw {
+    float x[NPB];
+    static PRD_DEV int chunks(int n) { return (n + NPB * NT - 1) / (NPB * NT); }
+    PRD_DEV void issue(const float* vg, int n, int tid, int chunk) {
+        const prd_gptr v = stage_base(vg);
+#pragma unroll
+        for (int u = 0; u < NPB; ++u) {
+            const int k = tid + (chunk * NPB + u) * NT;
+            x[u] = v[k < n ? k : 0];
+        }
+    }
+    PRD_DEV void commit(float* vl, int n, int tid, int chunk) const {
+#pragma unroll
+        for (int u = 0; u < NPB; ++u) {
+            const int k = tid + (chunk * NPB + u) * NT;
+            if (k < n) vl[k] = x[u];
+        }
+    }
+};
+
 // one K step of the natural-order form: acc[nb] += W[32 nb + r][16 st + 8 hi ..] * f (f = the lane's 8 generated operand values)
 template <int NB>
 PRD_DEV void h2_nat_step(const u32x4* Wh, int nout, int SL, int st, const float (&f)[8], f32x16 (&acc)[NB], int r, int hi) {

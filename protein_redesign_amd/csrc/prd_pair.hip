@@ -405,14 +405,48 @@ __global__ __launch_bounds__(NW * 64) void pair_head_h2_kernel(
     float* wl = bl + P;                                                  // [2][8 P] CLL rows of the bias heads
     float* gl = wl + 16 * P;                                             // [2][P]
     float* sl_ = gl + 2 * P;                                             // [2][P]
-    stage_weight_h2_nat(Wd, wd, P, DK, DK, 0, threadIdx.x, NT, H2_WSCALE);
-    stage_weight_h2_nat(Wo, wo, P, C, C, 0, threadIdx.x, NT, H2_WSCALE);
-    for (int k = threadIdx.x; k < DK; k += NT) cl[k] = centers[k];
-    stage_vec_cll(bl, bo, P, threadIdx.x, NT);
-    for (int h = 0; h < Ha; ++h) stage_vec_cll(wl + h * P, w_a + h * P, P, threadIdx.x, NT);
-    for (int h = 0; h < Hb; ++h) stage_vec_cll(wl + 8 * P + h * P, w_b + h * P, P, threadIdx.x, NT);
-    if (gamma_a) { stage_vec_cll(gl, gamma_a, P, threadIdx.x, NT); stage_vec_cll(sl_, beta_a, P, threadIdx.x, NT); }
-    if (gamma_b) { stage_vec_cll(gl + P, gamma_b, P, threadIdx.x, NT); stage_vec_cll(sl_ + P, beta_b, P, threadIdx.x, NT); }
+    {
+        // Every operand requested before the first wait (prd_common.h: issue / commit staging).  The matrices and the centers have
+        // runtime sizes: they go in chunks of a fixed in-flight budget per thread -- 4 pieces (128 B) of W_dist, 2 of W_out, 1 center;
+        // at dist_dim 256, C = 128 on 512 threads that is ONE chunk, issued together with all the vectors.  Larger operands
+        // (dist_dim 632) take further chunks, one round trip each.  Absent LayerNorm vectors are issued from b_o and not committed.
+        const int tid = threadIdx.x;
+        StageH2Nat<NT, 4> sd;
+        StageH2Nat<NT, 2> so;
+        StageRaw<NT, 1> sc;
+        StageVec<P, NT> vbo, vga, vba, vgb, vbb;
+        StageVecRows<P, 8, NT> va, vb;
+        sd.issue(wd, P, DK, DK, 0, tid, 0);
+        so.issue(wo, P, C, C, 0, tid, 0);
+        sc.issue(centers, DK, tid, 0);
+        vbo.issue(bo, tid);
+        va.issue(Ha > 0 ? w_a : bo, Ha, tid);
+        vb.issue(Hb > 0 ? w_b : bo, Hb, tid);
+        vga.issue(gamma_a ? gamma_a : bo, tid);
+        vba.issue(gamma_a ? beta_a : bo, tid);
+        vgb.issue(gamma_b ? gamma_b : bo, tid);
+        vbb.issue(gamma_b ? beta_b : bo, tid);
+        stage_issue_fence();
+        sd.commit(Wd, P, DK, tid, H2_WSCALE, 0);
+        so.commit(Wo, P, C, tid, H2_WSCALE, 0);
+        sc.commit(cl, DK, tid, 0);
+        vbo.commit(bl, tid);
+        va.commit(wl, Ha, tid);
+        vb.commit(wl + 8 * P, Hb, tid);
+        if (gamma_a) { vga.commit(gl, tid); vba.commit(sl_, tid); }
+        if (gamma_b) { vgb.commit(gl + P, tid); vbb.commit(sl_ + P, tid); }
+        const int nd = sd.chunks(P, DK), no = so.chunks(P, C), nc = sc.chunks(DK);
+        const int nch = nd > no ? (nd > nc ? nd : nc) : (no > nc ? no : nc);
+        for (int ch = 1; ch < nch; ++ch) {
+            sd.issue(wd, P, DK, DK, 0, tid, ch);
+            so.issue(wo, P, C, C, 0, tid, ch);
+            sc.issue(centers, DK, tid, ch);
+            stage_issue_fence();
+            sd.commit(Wd, P, DK, tid, H2_WSCALE, ch);
+            so.commit(Wo, P, C, tid, H2_WSCALE, ch);
+            sc.commit(cl, DK, tid, ch);
+        }
+    }
     __syncthreads();
     const float scale = (float)((DK - 1) / 2.0);
     const float c2 = -scale * 1.4426950408889634f;
@@ -1044,14 +1078,33 @@ __global__ __launch_bounds__(NW * 64) void pair_tail_h2_kernel(float* out, const
     float* wbl = bol + P;                                           // [8][P] CLL (bias head)
     const int NT = NW * 64;
     PairPhaseTimer pt;
-    stage_weight_h2<P>(W1h, w1, HID, P, threadIdx.x, NT, H2_WSCALE);
-    stage_weight_h2<HID>(W2h, w2, P, HID, threadIdx.x, NT, H2_WSCALE);
-    if (og) stage_weight_h2<HC>(Woh, wo, P, HC, threadIdx.x, NT, H2_WSCALE);
-    stage_vec_cll(b1l, b1, HID, threadIdx.x, NT);
-    stage_vec_cll(b2l, b2, P, threadIdx.x, NT);
-    stage_vec_cll(bol, og ? bo : nullptr, P, threadIdx.x, NT);
-    if (bias_out)
-        for (int h = 0; h < H; ++h) stage_vec_cll(wbl + h * P, wb + h * P, P, threadIdx.x, NT);
+    {
+        // every operand requested before the first wait (prd_common.h: issue / commit staging); an absent W_o / b_o / bias head is
+        // issued from W_1 / b_2 instead, so that the loads stay unconditional
+        const int tid = threadIdx.x;
+        const int hb = bias_out ? H : 0;
+        StageH2<P, HID, NT> s1;
+        StageH2<HID, P, NT> s2;
+        StageH2<HC, P, NT> so;
+        StageVec<HID, NT> v1;
+        StageVec<P, NT> v2, vo;
+        StageVecRows<P, 8, NT> vb;
+        s1.issue(w1, P, tid);
+        s2.issue(w2, HID, tid);
+        so.issue(og ? wo : w1, HC, tid);
+        v1.issue(b1, tid);
+        v2.issue(b2, tid);
+        vo.issue(og ? bo : b2, tid);
+        vb.issue(bias_out ? wb : b2, hb, tid);
+        stage_issue_fence();
+        s1.commit(W1h, HID, 0, tid, H2_WSCALE);
+        s2.commit(W2h, P, 0, tid, H2_WSCALE);
+        if (og) so.commit(Woh, P, 0, tid, H2_WSCALE);
+        v1.commit(b1l, tid);
+        v2.commit(b2l, tid);
+        vo.commit(bol, tid, 1.0f, og != nullptr);
+        vb.commit(wbl, hb, tid);
+    }
     __syncthreads();
     pt.mark(6);                                         // 6: prologue (weight staging, barrier)
     const int lane = threadIdx.x & 63, r_w = lane & 31, hi_w = lane >> 5;
@@ -1151,10 +1204,21 @@ __global__ __launch_bounds__(WG) void coord_head_kernel(float* __restrict__ eps,
     __shared__ __attribute__((aligned(16))) float b1l[P];
     __shared__ __attribute__((aligned(16))) float w2l[P];
     __shared__ float red[4][3];
-    if (B3) stage_weight_h2<P>(reinterpret_cast<u32x4*>(W1l), w1, P, P, threadIdx.x, WG, H2_WSCALE);
-    else stage_weight_cll<P>(W1l, w1, P, P, threadIdx.x, WG);
-    stage_vec_cll(b1l, b1, P, threadIdx.x, WG);
-    stage_vec_cll(w2l, w2, P, threadIdx.x, WG);
+    if (B3) {                                           // every operand requested before the first wait (prd_common.h)
+        StageH2<P, P, WG> s1;
+        StageVec<P, WG> v1, v2;
+        s1.issue(w1, P, threadIdx.x);
+        v1.issue(b1, threadIdx.x);
+        v2.issue(w2, threadIdx.x);
+        stage_issue_fence();
+        s1.commit(reinterpret_cast<u32x4*>(W1l), P, 0, threadIdx.x, H2_WSCALE);
+        v1.commit(b1l, threadIdx.x);
+        v2.commit(w2l, threadIdx.x);
+    } else {
+        stage_weight_cll<P>(W1l, w1, P, P, threadIdx.x, WG);
+        stage_vec_cll(b1l, b1, P, threadIdx.x, WG);
+        stage_vec_cll(w2l, w2, P, threadIdx.x, WG);
+    }
     __syncthreads();
     const int lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5, wave = threadIdx.x >> 6;
     const int nvb = (N + 31) / 32;

@@ -160,15 +160,24 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_proj_kernel(int* queue, float
     float* Wgl = Wpl + WSZ;
     float* bpl = Wgl + WSZ;                  // [2P] CLL
     float* bgl = bpl + OUT;
-    if (B3) {
-        stage_weight_h2<P>(reinterpret_cast<u32x4*>(Wpl), wp, OUT, P, threadIdx.x, NW * 64, H2_WSCALE);
-        stage_weight_h2<P>(reinterpret_cast<u32x4*>(Wgl), wg, OUT, P, threadIdx.x, NW * 64, NEG_LOG2E * H2_WSCALE);
+    if (B3) {                                           // every operand requested before the first wait (prd_common.h)
+        StageH2<P, OUT, NW * 64> sp, sg;
+        StageVec<OUT, NW * 64> vp, vg;
+        sp.issue(wp, P, threadIdx.x);
+        sg.issue(wg, P, threadIdx.x);
+        vp.issue(bp, threadIdx.x);
+        vg.issue(bg, threadIdx.x);
+        stage_issue_fence();
+        sp.commit(reinterpret_cast<u32x4*>(Wpl), OUT, 0, threadIdx.x, H2_WSCALE);
+        sg.commit(reinterpret_cast<u32x4*>(Wgl), OUT, 0, threadIdx.x, NEG_LOG2E * H2_WSCALE);
+        vp.commit(bpl, threadIdx.x, H2_WSCALE);                                               // biases ride in the accumulators
+        vg.commit(bgl, threadIdx.x, NEG_LOG2E * H2_WSCALE);
     } else {
         stage_weight_cll<P>(Wpl, wp, OUT, P, threadIdx.x, NW * 64);
         stage_weight_cll<P>(Wgl, wg, OUT, P, threadIdx.x, NW * 64, NEG_LOG2E);
+        stage_vec_cll(bpl, bp, OUT, threadIdx.x, NW * 64, 1.0f);                              // biases ride in the accumulators
+        stage_vec_cll(bgl, bg, OUT, threadIdx.x, NW * 64, NEG_LOG2E);
     }
-    stage_vec_cll(bpl, bp, OUT, threadIdx.x, NW * 64, B3 ? H2_WSCALE : 1.0f);                 // biases ride in the accumulators
-    stage_vec_cll(bgl, bg, OUT, threadIdx.x, NW * 64, NEG_LOG2E * (B3 ? H2_WSCALE : 1.0f));
     const int lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5;
     const int nvb = ldn / 32;
     const int nrb = b * N * nvb;                        // 32-row blocks
@@ -228,14 +237,30 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_out_proj_kernel(float* pair, 
     float* bgol = bol + P;                   // [P] CLL
     float* bpl = bgol + P;                   // [2P] CLL, x 16 (rides in the accumulators)
     float* bgl = bpl + OUT;                  // [2P] CLL, x -log2(e) x 16
-    stage_weight_h2<P>(reinterpret_cast<u32x4*>(Wol), wo, P, P, threadIdx.x, NW * 64, H2_WSCALE);
-    stage_weight_h2<P>(reinterpret_cast<u32x4*>(Wgol), wog, P, P, threadIdx.x, NW * 64, H2_WSCALE);
-    stage_weight_h2<P>(reinterpret_cast<u32x4*>(Wpl), wp, OUT, P, threadIdx.x, NW * 64, H2_WSCALE);
-    stage_weight_h2<P>(reinterpret_cast<u32x4*>(Wgl), wg, OUT, P, threadIdx.x, NW * 64, NEG_LOG2E * H2_WSCALE);
-    stage_vec_cll(bol, bo, P, threadIdx.x, NW * 64);
-    stage_vec_cll(bgol, bog, P, threadIdx.x, NW * 64);
-    stage_vec_cll(bpl, bp, OUT, threadIdx.x, NW * 64, H2_WSCALE);
-    stage_vec_cll(bgl, bg, OUT, threadIdx.x, NW * 64, NEG_LOG2E * H2_WSCALE);
+    {                                                   // every operand requested before the first wait (prd_common.h)
+        const int tid = threadIdx.x;
+        StageH2<P, P, NW * 64> so, sog;
+        StageH2<P, OUT, NW * 64> sp, sg;
+        StageVec<P, NW * 64> vo, vog;
+        StageVec<OUT, NW * 64> vp, vg;
+        so.issue(wo, P, tid);
+        sog.issue(wog, P, tid);
+        sp.issue(wp, P, tid);
+        sg.issue(wg, P, tid);
+        vo.issue(bo, tid);
+        vog.issue(bog, tid);
+        vp.issue(bp, tid);
+        vg.issue(bg, tid);
+        stage_issue_fence();
+        so.commit(reinterpret_cast<u32x4*>(Wol), P, 0, tid, H2_WSCALE);
+        sog.commit(reinterpret_cast<u32x4*>(Wgol), P, 0, tid, H2_WSCALE);
+        sp.commit(reinterpret_cast<u32x4*>(Wpl), OUT, 0, tid, H2_WSCALE);
+        sg.commit(reinterpret_cast<u32x4*>(Wgl), OUT, 0, tid, NEG_LOG2E * H2_WSCALE);
+        vo.commit(bol, tid);
+        vog.commit(bgol, tid);
+        vp.commit(bpl, tid, H2_WSCALE);
+        vg.commit(bgl, tid, NEG_LOG2E * H2_WSCALE);
+    }
     __syncthreads();
     const int lane = threadIdx.x & 63, r_w = lane & 31, hi_w = lane >> 5;
     const int nvb = ldn / 32;
@@ -661,15 +686,24 @@ __global__ __launch_bounds__(NW * 64) void tri_mul_out_kernel(int* queue, float*
     __shared__ __attribute__((aligned(16))) float bgl[P];
     constexpr float ASC = B3 ? H2_INV_WSCALE : 1.0f;     // accumulator scale of the split form
     PhaseTimer pt;
-    if (B3) {
-        stage_weight_h2<P>(reinterpret_cast<u32x4*>(Wol), wo, P, P, threadIdx.x, NW * 64, H2_WSCALE);
-        stage_weight_h2<P>(reinterpret_cast<u32x4*>(Wgl), wog, P, P, threadIdx.x, NW * 64, H2_WSCALE);
+    if (B3) {                                           // every operand requested before the first wait (prd_common.h)
+        StageH2<P, P, NW * 64> so, sog;
+        StageVec<P, NW * 64> vo, vog;
+        so.issue(wo, P, threadIdx.x);
+        sog.issue(wog, P, threadIdx.x);
+        vo.issue(bo, threadIdx.x);
+        vog.issue(bog, threadIdx.x);
+        stage_issue_fence();
+        so.commit(reinterpret_cast<u32x4*>(Wol), P, 0, threadIdx.x, H2_WSCALE);
+        sog.commit(reinterpret_cast<u32x4*>(Wgl), P, 0, threadIdx.x, H2_WSCALE);
+        vo.commit(bol, threadIdx.x);
+        vog.commit(bgl, threadIdx.x);
     } else {
         stage_weight_cll<P>(Wol, wo, P, P, threadIdx.x, NW * 64);
         stage_weight_cll<P>(Wgl, wog, P, P, threadIdx.x, NW * 64);
+        stage_vec_cll(bol, bo, P, threadIdx.x, NW * 64);
+        stage_vec_cll(bgl, bog, P, threadIdx.x, NW * 64);
     }
-    stage_vec_cll(bol, bo, P, threadIdx.x, NW * 64);
-    stage_vec_cll(bgl, bog, P, threadIdx.x, NW * 64);
     __syncthreads();
     pt.mark(6);                                         // 6: prologue (weight staging, barrier)
     const int lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5, wave = threadIdx.x >> 6;
@@ -2092,6 +2126,7 @@ __global__ __launch_bounds__(NW * 64) void tri_attn_out_kernel(int* queue, float
     constexpr int KH = P / 2, NB = P / 32, HC = 64;
     __shared__ __attribute__((aligned(16))) float Wl[B3 ? P * HC : P * (HC + 4)];      // B3: fp16 hi | lo planes (rowgemm_h2)
     __shared__ __attribute__((aligned(16))) float bl[P];
+    // (the issue / commit staging of prd_common.h was measured here and gained nothing: two short operands, 16.4 -> 16.5 us in the step)
     if (B3) stage_weight_h2<HC>(reinterpret_cast<u32x4*>(Wl), wo, P, HC, threadIdx.x, NW * 64, H2_WSCALE);
     else stage_weight_cll<HC>(Wl, wo, P, HC, threadIdx.x, NW * 64);
     stage_vec_cll(bl, bo, P, threadIdx.x, NW * 64);

@@ -21,13 +21,14 @@
         slot = blockIdx.x / H;
     }
     const float sc = 0.25f * LOG2E_2;
-    stage_weight_h2_rows<P>(Wb, 64, 0, wk + (long)h * C * P, C, P, tid, NT, H2_WSCALE);
-    stage_weight_h2_rows<P>(Wb, 64, C, wq + (long)h * C * P, C, P, tid, NT, sc * H2_WSCALE);
-    stage_weight_h2_rows<P>(Wb, 64, 2 * C, wg + (long)h * C * P, C, P, tid, NT, NEG_LOG2E * H2_WSCALE);
-    stage_weight_h2_rows<P>(Wb, 64, 3 * C, wv + (long)h * C * P, C, P, tid, NT, H2_WSCALE);
-    if (tid < 16) {
-        const int hh = tid >> 3, e = tid & 7;
-        biasl[tid] = H2_WSCALE * NEG_LOG2E * bg[h * C + 4 * hh + (e & 3) + 8 * (e >> 2)];
+    {                                                   // the four slices and the gate bias requested before the first wait (prd_common.h)
+        StageH2x4<P, C, NT> sw;
+        sw.issue(wk + (long)h * C * P, wq + (long)h * C * P, wg + (long)h * C * P, wv + (long)h * C * P, tid);
+        const int hh = (tid & 15) >> 3, e = tid & 7;    // gate bias in the register order of a lane: [hi][8]
+        const float bgv = stage_base(bg)[h * C + 4 * hh + (e & 3) + 8 * (e >> 2)];
+        stage_issue_fence();
+        sw.commit(Wb, tid, H2_WSCALE, sc * H2_WSCALE, NEG_LOG2E * H2_WSCALE, H2_WSCALE);
+        if (tid < 16) biasl[tid] = H2_WSCALE * NEG_LOG2E * bgv;
     }
     __syncthreads();
     const int nrows = b * N;
