@@ -373,7 +373,7 @@ int prd_pair_bias_bwd(float* dx, float* xn, float* d2, const float* dbias, const
  * db (optional, NULL = skip): the bias gradient db[O] = sum over rows of dy, from the same pass over dy.
  * ws: prd_linear_wgrad_workspace(rows, O, I) bytes of slab partials.
  * arith: PRD_ARITH_FP32 = fp32 MFMA; PRD_ARITH_SPLIT16 (wide form) = fp16 hi | lo operands on the 16-bit matrix pipe, dy scaled by a
- * running power of two per wave (gradients have no fixed magnitude; csrc/prd_bwd.hip linear_wgrad_h2_kernel).  db is summed in
+ * running power of two per wave (gradients have no fixed magnitude; csrc/prd_bwd.hip linear_wgrad_kernel<NBLK, true>).  db is summed in
  * fp32 either way. */
 size_t prd_linear_wgrad_workspace(long long rows, int O, int I);
 int prd_linear_wgrad(float* dw, float* db, const float* dy, const float* x, long long rows, int O, int I, int lddy, int ldx,

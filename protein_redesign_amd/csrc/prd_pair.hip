@@ -5,6 +5,7 @@
 // registers and every pair row is read and written exactly once per operator.
 #include "prd_common.h"
 #include <cstdlib>
+#include <type_traits>
 #include "../../include/prd_hip.h"
 #include "prd_launch.h"
 
@@ -151,101 +152,38 @@ __global__ void time_embed_kernel(float* __restrict__ eb, const int64_t* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
-// pair_init: pair = static + m2 * (W_d rbf(d) + ebeta).  B operand (rbf features) generated in
-// registers, A operand W_d from LDS; never materialises [N,N,dist_dim].
+// Row stages of the pair track's input: each stated ONCE, for both arithmetics, and called by the kernels of their own
+// (pair_init_kernel, opm_pair_kernel, pair_bias_kernel) and by the fused head (pair_head_h2_kernel).  The GEMMs generate their
+// B operand in registers and take the A operand, the weight, from LDS:
+//   B3 = false  fp32 MFMA: the weight as [nout][K + 4] floats (stage_weight_plain); lane half hi walks K / 2 .. of K, four values a step
+//   B3 = true   split-16 (gemm mode 1; K a multiple of 128): the weight as fp16 hi | lo planes [2][nout][K / 8] of 16 bytes
+//               (stage_weight_h2_nat), K in natural order, eight values a step split into fp16 hi + lo (prd_common.h: h2_nat_step)
 // ------------------------------------------------------------------------------------------------
-// LDS bytes: W_dist [P][DK + 4] | centers [DK]
-size_t pair_init_lds_bytes(int P, int DK) { return ((size_t)P * (DK + 4) + DK) * sizeof(float); }
-template <int P>
-__global__ __launch_bounds__(WG) void pair_init_kernel(float* __restrict__ pair, const float* __restrict__ stat,
-                                                       const float* __restrict__ z, const float* __restrict__ mask,
-                                                       const float* __restrict__ centers, const float* __restrict__ wd,
-                                                       const float* __restrict__ ebeta, int b, int N, int DK) {
-    constexpr int NB = P / 32, KH = P / 2;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Wl = smem;                       // [P][DK+4]
-    float* cl = smem + P * (DK + 4);        // [DK]
-    stage_weight_plain(Wl, wd, P, DK, DK, 0, threadIdx.x, WG);
-    for (int k = threadIdx.x; k < DK; k += WG) cl[k] = centers[k];
-    __syncthreads();
-    const float scale = (float)((DK - 1) / 2.0);
-    const float c2 = -scale * 1.4426950408889634f;
-    const int lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5;
-    const long rows = (long)b * N * N;
-    const long ntask = (rows + 31) / 32;
-    for (long task = (long)blockIdx.x * 4 + (threadIdx.x >> 6); task < ntask; task += (long)gridDim.x * 4) {
-        const long pos = task * 32 + r;
-        const bool valid = pos < rows;
-        int bb = 0, i = 0, j = 0;
-        if (valid) decode_pos(pos, N, bb, i, j);
-        const float* zi = z + ((long)bb * N + i) * 3;
-        const float* zj = z + ((long)bb * N + j) * 3;
-        const float dx = zi[0] - zj[0], dy = zi[1] - zj[1], dz = zi[2] - zj[2];
-        const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-        const float m2 = mask[bb * N + i] * mask[bb * N + j];
-        f32x16 acc[NB];
-        zero_acc(acc);
-        const int kb = hi * (DK / 2);
-        for (int m = 0; m < DK / 8; ++m) {
-            const float4 c4 = *reinterpret_cast<const float4*>(cl + kb + 4 * m);
-            float f0 = d - c4.x, f1 = d - c4.y, f2 = d - c4.z, f3 = d - c4.w;
-            // exp(-scale x^2) = 2^(c2 x^2) on v_exp_f32 (~1 ulp): expf() expands to ~15 VALU instructions per value, and on
-            // gfx950 VALU instructions cost matrix-pipe time (67 -> 22 per 8 MFMAs)
-            f0 = __builtin_amdgcn_exp2f(c2 * (f0 * f0)); f1 = __builtin_amdgcn_exp2f(c2 * (f1 * f1));
-            f2 = __builtin_amdgcn_exp2f(c2 * (f2 * f2)); f3 = __builtin_amdgcn_exp2f(c2 * (f3 * f3));
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                const float4 w = *reinterpret_cast<const float4*>(Wl + (nb * 32 + r) * (DK + 4) + kb + 4 * m);
-                acc[nb] = mfma32(w.x, f0, acc[nb]);
-                acc[nb] = mfma32(w.y, f1, acc[nb]);
-                acc[nb] = mfma32(w.z, f2, acc[nb]);
-                acc[nb] = mfma32(w.w, f3, acc[nb]);
-            }
-        }
-        float st[KH], eb[KH];
-        load_row_cll<P>(stat + pos * P, hi, valid, st);
-        load_row_cll<P>(ebeta + bb * P, hi, true, eb);
-        float o[KH];
-#pragma unroll
-        for (int s = 0; s < KH; ++s) o[s] = st[s] + m2 * (acc[s >> 4][s & 15] + eb[s]);
-        store_row_cll<P>(pair + pos * P, hi, valid, o);
-    }
+template <bool B3> using wimg_t = std::conditional_t<B3, u32x4, float>;                  // element of a weight image
+template <bool B3> PRD_DEV int wimg_elems(int nout, int K) { return B3 ? 2 * nout * (K / 8) : nout * (K + 4); }
+template <bool B3>
+PRD_DEV void stage_wimg(wimg_t<B3>* W, const float* __restrict__ w, int nout, int K, int ldw, int tid, int nthreads) {
+    if constexpr (B3) stage_weight_h2_nat(W, w, nout, K, ldw, 0, tid, nthreads, H2_WSCALE);
+    else stage_weight_plain(W, w, nout, K, ldw, 0, tid, nthreads);
 }
+// an accumulator element of such a GEMM as the product it stands for (the split-16 image carries H2_WSCALE)
+template <bool B3> PRD_DEV float acc_out(float a) { if constexpr (B3) return a * H2_INV_WSCALE; else return a; }
 
-// pair_init on the fp16 matrix pipe (gemm mode 1; dist_dim a multiple of 128): the radial-basis features are generated per K
-// step in natural order and split into fp16 hi + lo, W_d sits in LDS as hi | lo planes (prd_common.h: h2_nat_step).
-// LDS bytes: W_dist as fp16 hi | lo planes [2][P][DK / 8] of 16 bytes | centers [DK]
-size_t pair_init_h2_lds_bytes(int P, int DK) { return (size_t)4 * P * DK + (size_t)DK * 4; }
-template <int P>
-__global__ __launch_bounds__(WG) void pair_init_h2_kernel(float* __restrict__ pair, const float* __restrict__ stat,
-                                                          const float* __restrict__ z, const float* __restrict__ mask,
-                                                          const float* __restrict__ centers, const float* __restrict__ wd,
-                                                          const float* __restrict__ ebeta, int b, int N, int DK) {
-    constexpr int NB = P / 32, KH = P / 2;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_pi[];
-    u32x4* Wh = reinterpret_cast<u32x4*>(smem_pi);          // [2][P][DK/8]
-    const int SL = DK / 8;
-    float* cl = reinterpret_cast<float*>(Wh + 2 * P * SL);  // [DK]
-    stage_weight_h2_nat(Wh, wd, P, DK, DK, 0, threadIdx.x, WG, H2_WSCALE);
-    for (int k = threadIdx.x; k < DK; k += WG) cl[k] = centers[k];
-    __syncthreads();
+PRD_DEV float pair_distance(const float* zi, const float* zj) {
+    const float dx = zi[0] - zj[0], dy = zi[1] - zj[1], dz = zi[2] - zj[2];
+    return sqrtf(dx * dx + dy * dy + dz * dz);
+}
+// rbf(d)[k] = exp(-scale (d - c_k)^2) = 2^(c2 (d - c_k)^2) on v_exp_f32 (~1 ulp): expf() expands to ~15 VALU instructions per value,
+// and on gfx950 VALU instructions cost matrix-pipe time (67 -> 22 per 8 MFMAs)
+PRD_DEV float rbf_c2(int DK) {
     const float scale = (float)((DK - 1) / 2.0);
-    const float c2 = -scale * 1.4426950408889634f;
-    const int lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5;
-    const long rows = (long)b * N * N;
-    const long ntask = (rows + 31) / 32;
-    for (long task = (long)blockIdx.x * 4 + (threadIdx.x >> 6); task < ntask; task += (long)gridDim.x * 4) {
-        const long pos = task * 32 + r;
-        const bool valid = pos < rows;
-        int bb = 0, i = 0, j = 0;
-        if (valid) decode_pos(pos, N, bb, i, j);
-        const float* zi = z + ((long)bb * N + i) * 3;
-        const float* zj = z + ((long)bb * N + j) * 3;
-        const float dx = zi[0] - zj[0], dy = zi[1] - zj[1], dz = zi[2] - zj[2];
-        const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-        const float m2 = mask[bb * N + i] * mask[bb * N + j];
-        f32x16 acc[NB];
-        zero_acc(acc);
+    return -scale * 1.4426950408889634f;
+}
+// acc += W_d rbf(d): the radial-basis features of the lane's pair row, never materialised as [N,N,dist_dim]; cl: the centers [DK] in LDS
+template <int P, bool B3>
+PRD_DEV void rbf_rowgemm(const wimg_t<B3>* W, const float* cl, int DK, float c2, float d, f32x16 (&acc)[P / 32], int r, int hi) {
+    constexpr int NB = P / 32;
+    if constexpr (B3) {
         for (int st = 0; st < DK / 16; ++st) {
             const float4 c0 = *reinterpret_cast<const float4*>(cl + 16 * st + 8 * hi);
             const float4 c1 = *reinterpret_cast<const float4*>(cl + 16 * st + 8 * hi + 4);
@@ -254,33 +192,174 @@ __global__ __launch_bounds__(WG) void pair_init_h2_kernel(float* __restrict__ pa
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float t = d - cc[e];
-                f[e] = __builtin_amdgcn_exp2f(c2 * (t * t));       // exp(-scale t^2) on v_exp_f32
+                f[e] = __builtin_amdgcn_exp2f(c2 * (t * t));
             }
-            h2_nat_step<NB>(Wh, P, SL, st, f, acc, r, hi);
+            h2_nat_step<NB>(W, P, DK / 8, st, f, acc, r, hi);
         }
-        float st_[KH], eb[KH];
-        load_row_cll<P>(stat + pos * P, hi, valid, st_);
-        load_row_cll<P>(ebeta + bb * P, hi, true, eb);
-        float o[KH];
+    } else {
+        const int kb = hi * (DK / 2);
+        for (int m = 0; m < DK / 8; ++m) {
+            const float4 c4 = *reinterpret_cast<const float4*>(cl + kb + 4 * m);
+            float f0 = d - c4.x, f1 = d - c4.y, f2 = d - c4.z, f3 = d - c4.w;
+            f0 = __builtin_amdgcn_exp2f(c2 * (f0 * f0)); f1 = __builtin_amdgcn_exp2f(c2 * (f1 * f1));
+            f2 = __builtin_amdgcn_exp2f(c2 * (f2 * f2)); f3 = __builtin_amdgcn_exp2f(c2 * (f3 * f3));
 #pragma unroll
-        for (int s_ = 0; s_ < KH; ++s_) o[s_] = st_[s_] + m2 * (acc[s_ >> 4][s_ & 15] * H2_INV_WSCALE + eb[s_]);
+            for (int nb = 0; nb < NB; ++nb) {
+                const float4 w = *reinterpret_cast<const float4*>(W + (nb * 32 + r) * (DK + 4) + kb + 4 * m);
+                acc[nb] = mfma32(w.x, f0, acc[nb]);
+                acc[nb] = mfma32(w.y, f1, acc[nb]);
+                acc[nb] = mfma32(w.z, f2, acc[nb]);
+                acc[nb] = mfma32(w.w, f3, acc[nb]);
+            }
+        }
+    }
+}
+// x = static + m2 (acc + ebeta): the two rows are requested here, AFTER the GEMM (64 registers the K loop needs; the other waves of
+// the SIMD cover the latency)
+template <int P, bool B3>
+PRD_DEV void pair_init_finish(float (&x)[P / 2], const f32x16 (&acc)[P / 32], const float* stat_row, const float* ebeta_row, float m2,
+                              bool valid, int hi) {
+    constexpr int KH = P / 2;
+    float st[KH], eb[KH];
+    load_row_cll<P>(stat_row, hi, valid, st);
+    load_row_cll<P>(ebeta_row, hi, true, eb);
+#pragma unroll
+    for (int s = 0; s < KH; ++s) x[s] = st[s] + m2 * (acc_out<B3>(acc[s >> 4][s & 15]) + eb[s]);
+}
+// acc += W_o (a_i * b_j) for the rows ai = ab[bb, i], bj = ab[bb, j] + C of the projected single track; the values of K step m + 1
+// are in flight while step m is multiplied (unconditional prefetch, clamped index)
+template <int P, bool B3>
+PRD_DEV void product_rowgemm(const wimg_t<B3>* W, const float* ai, const float* bj, int C, f32x16 (&acc)[P / 32], int r, int hi) {
+    constexpr int NB = P / 32;
+    if constexpr (B3) {
+        ai += 8 * hi;
+        bj += 8 * hi;
+        float4 a0 = *reinterpret_cast<const float4*>(ai), a1 = *reinterpret_cast<const float4*>(ai + 4);
+        float4 b0 = *reinterpret_cast<const float4*>(bj), b1 = *reinterpret_cast<const float4*>(bj + 4);
+        const int nst = C / 16;
+        for (int st = 0; st < nst; ++st) {
+            const int sn = st + 1 < nst ? st + 1 : st;
+            const float4 na0 = *reinterpret_cast<const float4*>(ai + 16 * sn), na1 = *reinterpret_cast<const float4*>(ai + 16 * sn + 4);
+            const float4 nb0 = *reinterpret_cast<const float4*>(bj + 16 * sn), nb1 = *reinterpret_cast<const float4*>(bj + 16 * sn + 4);
+            const float f[8] = {a0.x * b0.x, a0.y * b0.y, a0.z * b0.z, a0.w * b0.w, a1.x * b1.x, a1.y * b1.y, a1.z * b1.z, a1.w * b1.w};
+            h2_nat_step<NB>(W, P, C / 8, st, f, acc, r, hi);
+            a0 = na0; a1 = na1; b0 = nb0; b1 = nb1;
+        }
+    } else {
+        ai += hi * (C / 2);
+        bj += hi * (C / 2);
+        float4 a4 = *reinterpret_cast<const float4*>(ai), b4 = *reinterpret_cast<const float4*>(bj);
+        const int nm = C / 8;
+        for (int m = 0; m < nm; ++m) {
+            const int mn = m + 1 < nm ? m + 1 : m;
+            const float4 an = *reinterpret_cast<const float4*>(ai + 4 * mn);
+            const float4 bn = *reinterpret_cast<const float4*>(bj + 4 * mn);
+            const float f0 = a4.x * b4.x, f1 = a4.y * b4.y, f2 = a4.z * b4.z, f3 = a4.w * b4.w;
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                const float4 w = *reinterpret_cast<const float4*>(W + (nb * 32 + r) * (C + 4) + hi * (C / 2) + 4 * m);
+                acc[nb] = mfma32(w.x, f0, acc[nb]);
+                acc[nb] = mfma32(w.y, f1, acc[nb]);
+                acc[nb] = mfma32(w.z, f2, acc[nb]);
+                acc[nb] = mfma32(w.w, f3, acc[nb]);
+            }
+            a4 = an;
+            b4 = bn;
+        }
+    }
+}
+// x += [m2] (acc + b_o) / (m2 + 1e-3); bl: b_o [P] in LDS, CLL order
+template <int P, bool B3>
+PRD_DEV void opm_finish(float (&x)[P / 2], const f32x16 (&acc)[P / 32], const float* bl, float m2, bool apply_mask, int hi) {
+    constexpr int KH = P / 2;
+    const float norm = m2 + 1e-3f;
+    const float mm = apply_mask ? m2 : 1.f;
+#pragma unroll
+    for (int s = 0; s < KH; ++s) x[s] = x[s] + mm * ((acc_out<B3>(acc[s >> 4][s & 15]) + bl[hi * KH + s]) / norm);
+}
+// The two attention-bias head sets on a normalised row xn: out[bb, h, rem] = W[h] . (gamma ? xn gamma + beta : xn) (+ bvec[h]).  LDS
+// images, CLL order: wl [2][8 P] head rows, gl / sl [2][P] the LayerNorm affine pairs.  out_b == NULL: the first set only.
+template <int P>
+PRD_DEV void bias_heads(const float (&xn)[P / 2], const float* wl, const float* gl, const float* sl,
+                        float* out_a, const float* gamma_a, const float* bvec_a, int Ha,
+                        float* out_b, const float* gamma_b, const float* bvec_b, int Hb, long bb, long rem, long nn, bool valid, int hi) {
+    constexpr int KH = P / 2;
+#pragma unroll
+    for (int set = 0; set < 2; ++set) {
+        if (set == 1 && !out_b) break;
+        const float* ga = set ? gamma_b : gamma_a;
+        const float* bv = set ? bvec_b : bvec_a;
+        float* o = set ? out_b : out_a;
+        const int nh = set ? Hb : Ha;
+        float x[KH];
+#pragma unroll
+        for (int s = 0; s < KH; ++s) x[s] = ga ? xn[s] * gl[set * P + hi * KH + s] + sl[set * P + hi * KH + s] : xn[s];
+        for (int h = 0; h < nh; ++h) {
+            float acc = 0.f;
+#pragma unroll
+            for (int s = 0; s < KH; ++s) acc += x[s] * wl[set * 8 * P + h * P + hi * KH + s];
+            acc = xhalf_sum(acc);
+            if (bv) acc += bv[h];
+            if (valid && hi == 0) o[(bb * nh + h) * nn + rem] = acc;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// pair_init: pair = static + m2 * (W_d rbf(d) + ebeta)
+// ------------------------------------------------------------------------------------------------
+// LDS bytes: W_dist [P][DK + 4] | centers [DK]
+size_t pair_init_lds_bytes(int P, int DK) { return ((size_t)P * (DK + 4) + DK) * sizeof(float); }
+// LDS bytes: W_dist as fp16 hi | lo planes [2][P][DK / 8] of 16 bytes | centers [DK]
+size_t pair_init_h2_lds_bytes(int P, int DK) { return (size_t)4 * P * DK + (size_t)DK * 4; }
+template <int P, bool B3>
+__global__ __launch_bounds__(WG) void pair_init_kernel(float* __restrict__ pair, const float* __restrict__ stat,
+                                                       const float* __restrict__ z, const float* __restrict__ mask,
+                                                       const float* __restrict__ centers, const float* __restrict__ wd,
+                                                       const float* __restrict__ ebeta, int b, int N, int DK) {
+    constexpr int NB = P / 32, KH = P / 2;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_pi[];
+    wimg_t<B3>* W = reinterpret_cast<wimg_t<B3>*>(smem_pi);
+    float* cl = reinterpret_cast<float*>(W + wimg_elems<B3>(P, DK));      // [DK]
+    stage_wimg<B3>(W, wd, P, DK, DK, threadIdx.x, WG);
+    for (int k = threadIdx.x; k < DK; k += WG) cl[k] = centers[k];
+    __syncthreads();
+    const float c2 = rbf_c2(DK);
+    const int lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5;
+    const long rows = (long)b * N * N;
+    const long ntask = (rows + 31) / 32;
+    for (long task = (long)blockIdx.x * 4 + (threadIdx.x >> 6); task < ntask; task += (long)gridDim.x * 4) {
+        const long pos = task * 32 + r;
+        const bool valid = pos < rows;
+        int bb = 0, i = 0, j = 0;
+        if (valid) decode_pos(pos, N, bb, i, j);
+        const float d = pair_distance(z + ((long)bb * N + i) * 3, z + ((long)bb * N + j) * 3);
+        const float m2 = mask[bb * N + i] * mask[bb * N + j];
+        f32x16 acc[NB];
+        zero_acc(acc);
+        rbf_rowgemm<P, B3>(W, cl, DK, c2, d, acc, r, hi);
+        float o[KH];
+        pair_init_finish<P, B3>(o, acc, stat + pos * P, ebeta + bb * P, m2, valid, hi);
         store_row_cll<P>(pair + pos * P, hi, valid, o);
     }
 }
 
-// OPM tail on the fp16 matrix pipe (gemm mode 1; C a multiple of 128): the products a_i * b_j are generated per K step.
+// ------------------------------------------------------------------------------------------------
+// OPM tail: pair[i,j,:] += m2 * (W_o (a_i*b_j) + b_o) / (m2 + 1e-3)
+// ------------------------------------------------------------------------------------------------
+// LDS bytes: W_out [P][C + 4] | bias [P]
+size_t opm_pair_lds_bytes(int P, int C) { return ((size_t)P * (C + 4) + P) * sizeof(float); }
 // LDS bytes: W_out as fp16 hi | lo planes [2][P][C / 8] of 16 bytes | bias [P]
 size_t opm_pair_h2_lds_bytes(int P, int C) { return (size_t)4 * P * C + (size_t)P * 4; }
-template <int P>
-__global__ __launch_bounds__(WG) void opm_pair_h2_kernel(float* out, const float* pair, const float* __restrict__ ab,
-                                                         const float* __restrict__ mask, const float* __restrict__ wo,
-                                                         const float* __restrict__ bo, int b, int N, int C, int flags) {
+template <int P, bool B3>
+__global__ __launch_bounds__(WG) void opm_pair_kernel(float* out, const float* pair, const float* __restrict__ ab,
+                                                      const float* __restrict__ mask, const float* __restrict__ wo,
+                                                      const float* __restrict__ bo, int b, int N, int C, int flags) {
     constexpr int NB = P / 32, KH = P / 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_op[];
-    u32x4* Wh = reinterpret_cast<u32x4*>(smem_op);          // [2][P][C/8]
-    const int SL = C / 8;
-    float* bl = reinterpret_cast<float*>(Wh + 2 * P * SL);  // [P] CLL
-    stage_weight_h2_nat(Wh, wo, P, C, C, 0, threadIdx.x, WG, H2_WSCALE);
+    wimg_t<B3>* W = reinterpret_cast<wimg_t<B3>*>(smem_op);
+    float* bl = reinterpret_cast<float*>(W + wimg_elems<B3>(P, C));       // [P] CLL
+    stage_wimg<B3>(W, wo, P, C, C, threadIdx.x, WG);
     stage_vec_cll(bl, bo, P, threadIdx.x, WG);
     __syncthreads();
     const int lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5;
@@ -293,29 +372,14 @@ __global__ __launch_bounds__(WG) void opm_pair_h2_kernel(float* out, const float
         const int j = vb * 32 + r;
         const bool valid = j < N;
         const int jj = valid ? j : 0;
-        const float* ai = ab + bi * 2 * C + 8 * hi;
-        const float* bj = ab + ((long)bb * N + jj) * 2 * C + C + 8 * hi;
         f32x16 acc[NB];
         zero_acc(acc);
-        float4 a0 = *reinterpret_cast<const float4*>(ai), a1 = *reinterpret_cast<const float4*>(ai + 4);
-        float4 b0 = *reinterpret_cast<const float4*>(bj), b1 = *reinterpret_cast<const float4*>(bj + 4);
-        const int nst = C / 16;
-        for (int st = 0; st < nst; ++st) {
-            const int sn = st + 1 < nst ? st + 1 : st;                   // unconditional prefetch (clamped)
-            const float4 na0 = *reinterpret_cast<const float4*>(ai + 16 * sn), na1 = *reinterpret_cast<const float4*>(ai + 16 * sn + 4);
-            const float4 nb0 = *reinterpret_cast<const float4*>(bj + 16 * sn), nb1 = *reinterpret_cast<const float4*>(bj + 16 * sn + 4);
-            const float f[8] = {a0.x * b0.x, a0.y * b0.y, a0.z * b0.z, a0.w * b0.w, a1.x * b1.x, a1.y * b1.y, a1.z * b1.z, a1.w * b1.w};
-            h2_nat_step<NB>(Wh, P, SL, st, f, acc, r, hi);
-            a0 = na0; a1 = na1; b0 = nb0; b1 = nb1;
-        }
+        product_rowgemm<P, B3>(W, ab + bi * 2 * C, ab + ((long)bb * N + jj) * 2 * C + C, C, acc, r, hi);
         const float m2 = mask[bi] * mask[(long)bb * N + jj];
-        const float norm = m2 + 1e-3f;
         const long off = (bi * N + jj) * P;
         float x[KH];
         load_row_cll<P>(pair + off, hi, valid && (flags & 1), x);
-        const float mm = (flags & 2) ? m2 : 1.f;
-#pragma unroll
-        for (int s_ = 0; s_ < KH; ++s_) x[s_] = x[s_] + mm * ((acc[s_ >> 4][s_ & 15] * H2_INV_WSCALE + bl[hi * KH + s_]) / norm);
+        opm_finish<P, B3>(x, acc, bl, m2, flags & 2, hi);
         store_row_cll<P>(out + off, hi, valid, x);
     }
 }
@@ -355,25 +419,7 @@ __global__ __launch_bounds__(WG) void pair_bias_kernel(float* __restrict__ out, 
         ln_cll<KH>(xn);
         long bb = (task * 32) / nn, rem = task * 32 - bb * nn + r;       // the division on the scalar unit (wave-uniform task), not per lane
         if (rem >= nn) { rem -= nn; ++bb; }
-#pragma unroll
-        for (int set = 0; set < 2; ++set) {
-            if (set == 1 && !out2) break;
-            const float* ga = set ? gamma2 : gamma;
-            const float* bv = set ? bvec2 : bvec;
-            float* o = set ? out2 : out;
-            const int nh = set ? H2 : H;
-            float x[KH];
-#pragma unroll
-            for (int s = 0; s < KH; ++s) x[s] = ga ? xn[s] * gl[set][hi * KH + s] + bl[set][hi * KH + s] : xn[s];
-            for (int h = 0; h < nh; ++h) {
-                float acc = 0.f;
-#pragma unroll
-                for (int s = 0; s < KH; ++s) acc += x[s] * wl[set][h * P + hi * KH + s];
-                acc = xhalf_sum(acc);
-                if (bv) acc += bv[h];
-                if (valid && hi == 0) o[(bb * nh + h) * nn + rem] = acc;
-            }
-        }
+        bias_heads<P>(xn, wl[0], gl[0], bl[0], out, gamma, bvec, H, out2, gamma2, bvec2, H2, bb, rem, nn, valid, hi);
     }
 }
 
@@ -382,8 +428,9 @@ __global__ __launch_bounds__(WG) void pair_bias_kernel(float* __restrict__ out, 
 // (model.py:339-361 + models/AF2_modules.py:532-545 + modules.py:395-397 + AF2_modules.py:454-459 + modules.py:300-304).
 // All three are row-local in (i, j): as separate launches the pair tensor is written, read + written, and read again (4 U =
 // 105 MB at N = 320) and three prologues / tails are paid; here the row stays in registers from the radial-basis GEMM to the
-// bias heads and is written once (1 U + the two [H,N,N] outputs).  The arithmetic of each stage is that of its own kernel
-// (pair_init_h2_kernel, opm_pair_h2_kernel, pair_bias_kernel), in the same order.  A task = (batch row bi = bb N + i, 32 columns j).
+// bias heads and is written once (1 U + the two [H,N,N] outputs).  Each stage is the row-stage function that the kernel of its own
+// calls (pair_init_kernel<P, true>, opm_pair_kernel<P, true>, pair_bias_kernel), in the same order: the outputs are bit-equal to the
+// three launches (tests/test_pair_row_stages.py).  A task = (batch row bi = bb N + i, 32 columns j).
 // LDS bytes: W_dist planes [2][P][DK / 8] | W_out planes [2][P][C / 8] | centers [DK] | bias [P] | bias-head rows [2][8 P] | two vectors per head set [2][P] each
 size_t pair_head_lds_bytes(int P, int DK, int C) { return (size_t)4 * P * DK + (size_t)4 * P * C + ((size_t)DK + P + 16 * P + 4 * P) * 4; }
 template <int P, int NW>
@@ -448,8 +495,7 @@ __global__ __launch_bounds__(NW * 64) void pair_head_h2_kernel(
         }
     }
     __syncthreads();
-    const float scale = (float)((DK - 1) / 2.0);
-    const float c2 = -scale * 1.4426950408889634f;
+    const float c2 = rbf_c2(DK);
     const int lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5;
     const int nvb = (N + 31) / 32;
     const long ntask = (long)b * N * nvb, nn = (long)N * N;
@@ -463,135 +509,20 @@ __global__ __launch_bounds__(NW * 64) void pair_head_h2_kernel(
         const long off = (bi * N + jj) * P;
         const float m2 = mask[bi] * mask[(long)bb * N + jj];
         float x[KH];
-        {   // ---- pair_init: static part + m2 (W_d rbf(|z_i - z_j|) + ebeta) ----
-            const float* zi = z + bi * 3;
-            const float* zj = z + ((long)bb * N + jj) * 3;
-            const float dx = zi[0] - zj[0], dy = zi[1] - zj[1], dz = zi[2] - zj[2];
-            const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-            f32x16 acc[NB];
-            zero_acc(acc);
-            for (int st = 0; st < DK / 16; ++st) {
-                const float4 c0 = *reinterpret_cast<const float4*>(cl + 16 * st + 8 * hi);
-                const float4 c1 = *reinterpret_cast<const float4*>(cl + 16 * st + 8 * hi + 4);
-                const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-                float f[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float t = d - cc[e];
-                    f[e] = __builtin_amdgcn_exp2f(c2 * (t * t));
-                }
-                h2_nat_step<NB>(Wd, P, SLd, st, f, acc, r, hi);
-            }
-            float st_[KH], eb[KH];                                       // (requested after the GEMM: 64 registers the loop needs; the
-            load_row_cll<P>(stat + off, hi, valid, st_);                 // other waves of the SIMD cover the latency)
-            load_row_cll<P>(ebeta + bb * P, hi, true, eb);
-#pragma unroll
-            for (int s_ = 0; s_ < KH; ++s_) x[s_] = st_[s_] + m2 * (acc[s_ >> 4][s_ & 15] * H2_INV_WSCALE + eb[s_]);
-        }
-        {   // ---- OuterProductUpdate tail: x += [m2] (W_o (a_i * b_j) + b_o) / (m2 + 1e-3) ----
-            const float* ai = ab + bi * 2 * C + 8 * hi;
-            const float* bj = ab + ((long)bb * N + jj) * 2 * C + C + 8 * hi;
-            f32x16 acc[NB];
-            zero_acc(acc);
-            float4 a0 = *reinterpret_cast<const float4*>(ai), a1 = *reinterpret_cast<const float4*>(ai + 4);
-            float4 b0 = *reinterpret_cast<const float4*>(bj), b1 = *reinterpret_cast<const float4*>(bj + 4);
-            const int nst = C / 16;
-            for (int st = 0; st < nst; ++st) {
-                const int sn = st + 1 < nst ? st + 1 : st;
-                const float4 na0 = *reinterpret_cast<const float4*>(ai + 16 * sn), na1 = *reinterpret_cast<const float4*>(ai + 16 * sn + 4);
-                const float4 nb0 = *reinterpret_cast<const float4*>(bj + 16 * sn), nb1 = *reinterpret_cast<const float4*>(bj + 16 * sn + 4);
-                const float f[8] = {a0.x * b0.x, a0.y * b0.y, a0.z * b0.z, a0.w * b0.w, a1.x * b1.x, a1.y * b1.y, a1.z * b1.z, a1.w * b1.w};
-                h2_nat_step<NB>(Wo, P, SLo, st, f, acc, r, hi);
-                a0 = na0; a1 = na1; b0 = nb0; b1 = nb1;
-            }
-            const float norm = m2 + 1e-3f;
-            const float mm = apply_mask ? m2 : 1.f;
-#pragma unroll
-            for (int s_ = 0; s_ < KH; ++s_) x[s_] = x[s_] + mm * ((acc[s_ >> 4][s_ & 15] * H2_INV_WSCALE + bl[hi * KH + s_]) / norm);
-        }
+        f32x16 acc[NB];
+        // ---- pair_init: static part + m2 (W_d rbf(|z_i - z_j|) + ebeta) ----
+        zero_acc(acc);
+        rbf_rowgemm<P, true>(Wd, cl, DK, c2, pair_distance(z + bi * 3, z + ((long)bb * N + jj) * 3), acc, r, hi);
+        pair_init_finish<P, true>(x, acc, stat + off, ebeta + bb * P, m2, valid, hi);
+        // ---- OuterProductUpdate tail: x += [m2] (W_o (a_i * b_j) + b_o) / (m2 + 1e-3) ----
+        zero_acc(acc);
+        product_rowgemm<P, true>(Wo, ab + bi * 2 * C, ab + ((long)bb * N + jj) * 2 * C + C, C, acc, r, hi);
+        opm_finish<P, true>(x, acc, bl, m2, apply_mask, hi);
         store_row_cll<P>(pair + off, hi, valid, x);
         // ---- the two bias heads on LN(x) ----
         ln_cll<KH>(x);
-        const long rem = (long)i * N + jj;
-#pragma unroll
-        for (int set = 0; set < 2; ++set) {
-            const float* ga = set ? gamma_b : gamma_a;
-            const float* bv = set ? bvec_b : bvec_a;
-            float* o = set ? out_b : out_a;
-            const int nh = set ? Hb : Ha;
-            float y[KH];
-#pragma unroll
-            for (int s = 0; s < KH; ++s) y[s] = ga ? x[s] * gl[set * P + hi * KH + s] + sl_[set * P + hi * KH + s] : x[s];
-            for (int h = 0; h < nh; ++h) {
-                float acc = 0.f;
-#pragma unroll
-                for (int s = 0; s < KH; ++s) acc += y[s] * wl[set * 8 * P + h * P + hi * KH + s];
-                acc = xhalf_sum(acc);
-                if (bv) acc += bv[h];
-                if (valid && hi == 0) o[((long)bb * nh + h) * nn + rem] = acc;
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// OPM tail: pair[i,j,:] += m2 * (W_o (a_i*b_j) + b_o) / (m2 + 1e-3)
-// ------------------------------------------------------------------------------------------------
-// LDS bytes: W_out [P][C + 4] | bias [P]
-size_t opm_pair_lds_bytes(int P, int C) { return ((size_t)P * (C + 4) + P) * sizeof(float); }
-template <int P>
-__global__ __launch_bounds__(WG) void opm_pair_kernel(float* out, const float* pair, const float* __restrict__ ab,
-                                                      const float* __restrict__ mask, const float* __restrict__ wo,
-                                                      const float* __restrict__ bo, int b, int N, int C, int flags) {
-    constexpr int NB = P / 32, KH = P / 2;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Wl = smem;                    // [P][C+4]
-    float* bl = smem + P * (C + 4);      // [P] CLL
-    stage_weight_plain(Wl, wo, P, C, C, 0, threadIdx.x, WG);
-    stage_vec_cll(bl, bo, P, threadIdx.x, WG);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5;
-    const int nvb = (N + 31) / 32;
-    const long ntask = (long)b * N * nvb;
-    for (long task = (long)blockIdx.x * 4 + (threadIdx.x >> 6); task < ntask; task += (long)gridDim.x * 4) {
-        const int vb = (int)(task % nvb);
-        const long bi = task / nvb;            // bb*N + i
-        const int bb = (int)(bi / N);
-        const int j = vb * 32 + r;
-        const bool valid = j < N;
-        const int jj = valid ? j : 0;
-        const float* ai = ab + bi * 2 * C + hi * (C / 2);
-        const float* bj = ab + ((long)bb * N + jj) * 2 * C + C + hi * (C / 2);
-        f32x16 acc[NB];
-        zero_acc(acc);
-        // the a_i / b_j values of step m+1 are in flight while step m is multiplied (unconditional, clamped index)
-        float4 a4 = *reinterpret_cast<const float4*>(ai), b4 = *reinterpret_cast<const float4*>(bj);
-        const int nm = C / 8;
-        for (int m = 0; m < nm; ++m) {
-            const int mn = m + 1 < nm ? m + 1 : m;
-            const float4 an = *reinterpret_cast<const float4*>(ai + 4 * mn);
-            const float4 bn = *reinterpret_cast<const float4*>(bj + 4 * mn);
-            const float f0 = a4.x * b4.x, f1 = a4.y * b4.y, f2 = a4.z * b4.z, f3 = a4.w * b4.w;
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                const float4 w = *reinterpret_cast<const float4*>(Wl + (nb * 32 + r) * (C + 4) + hi * (C / 2) + 4 * m);
-                acc[nb] = mfma32(w.x, f0, acc[nb]);
-                acc[nb] = mfma32(w.y, f1, acc[nb]);
-                acc[nb] = mfma32(w.z, f2, acc[nb]);
-                acc[nb] = mfma32(w.w, f3, acc[nb]);
-            }
-            a4 = an;
-            b4 = bn;
-        }
-        const float m2 = mask[bi] * mask[(long)bb * N + jj];
-        const float norm = m2 + 1e-3f;
-        const long off = (bi * N + jj) * P;
-        float x[KH];
-        load_row_cll<P>(pair + off, hi, valid && (flags & 1), x);
-        const float mm = (flags & 2) ? m2 : 1.f;
-#pragma unroll
-        for (int s = 0; s < KH; ++s) x[s] = x[s] + mm * ((acc[s >> 4][s & 15] + bl[hi * KH + s]) / norm);
-        store_row_cll<P>(out + off, hi, valid, x);
+        __builtin_assume(out_b != nullptr);                              // (the entry point refuses a call without the second set)
+        bias_heads<P>(x, wl, gl, sl_, out_a, gamma_a, bvec_a, Ha, out_b, gamma_b, bvec_b, Hb, (long)bb, (long)i * N + jj, nn, valid, hi);
     }
 }
 
@@ -666,24 +597,31 @@ __global__ __launch_bounds__(WG) void outer_linear_kernel(float* out, const floa
 size_t outer_linear_res_lds_bytes(int P, int S) { return ((size_t)P * (S + 4) + P) * sizeof(float); }
 // W1 stays resident in LDS up to this size only (beyond: outer_linear_kernel streams it in K chunks)
 constexpr size_t OUTER_LINEAR_RES_LDS_MAX = 150 * 1024;
-template <int P, int NW>
+// B3, the fp16 matrix pipe (gemm mode 1; S a multiple of 128): W1 as fp16 hi | lo planes (the size of the fp32 image, so it stays
+// resident), the generated operand x_i * x_j split per K step, three products per step.  K runs in natural order: K step s of lane
+// (r, hi) covers k = 16 s + 8 hi .. + 7.  Static task assignment: called with queue = nullptr.
+// LDS bytes: W1 as fp16 hi | lo planes [2][P][S / 8] of 16 bytes | bias [P]
+size_t outer_linear_res_h2_lds_bytes(int P, int S) { return (size_t)4 * P * S + 4 * P; }
+template <int P, int NW, bool B3>
 __global__ __launch_bounds__(NW * 64) void outer_linear_res_kernel(int* queue, float* out, const float* pair,
                                                                    const float* __restrict__ x, const float* __restrict__ u,
                                                                    const float* __restrict__ w, const float* __restrict__ bias,
                                                                    int b, int N, int S, int residual, int ldu) {
     constexpr int NB = P / 32, KH = P / 2;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Wl = smem;                      // [P][S+4]
-    float* bl = smem + P * (S + 4);        // [P] CLL
-    stage_weight_plain(Wl, w, P, S, 2 * S, 0, threadIdx.x, NW * 64);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_ol[];
+    wimg_t<B3>* W = reinterpret_cast<wimg_t<B3>*>(smem_ol);
+    float* bl = reinterpret_cast<float*>(W + wimg_elems<B3>(P, S));  // [P] CLL
+    PairPhaseTimer pt;
+    stage_wimg<B3>(W, w, P, S, 2 * S, threadIdx.x, NW * 64);
     stage_vec_cll(bl, bias, P, threadIdx.x, NW * 64);
     __syncthreads();
+    pt.mark(6);                                             // 6: prologue (W1 staging, barrier)
     const int lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5;
     const int nvb = (N + 31) / 32;
     const int npairs = nvb * (nvb + 1) / 2;                // block pairs (ib <= jb)
     const long ntask = (long)b * npairs * 32;              // 32 rows i per block pair
-    const int kb = hi * (S / 2);
-    WaveTasks tasks(queue, ntask, NW);
+    const int kb = B3 ? 8 * hi : hi * (S / 2);             // the lane's first k
+    WaveTasks tasks(B3 ? nullptr : queue, ntask, NW);      // (B3: no queue code is built into the kernel)
     for (long task = tasks.next(); task >= 0; task = tasks.next()) {
         const int ii = (int)(task & 31);
         const long t2 = task >> 5;
@@ -700,44 +638,63 @@ __global__ __launch_bounds__(NW * 64) void outer_linear_res_kernel(int* queue, f
         const int jj = valid ? j : 0;
         const float* xi = x + bi * S + kb;
         const float* xj = x + ((long)bb * N + jj) * S + kb;
-        const float* wl = Wl + r * (S + 4) + kb;
         f32x16 acc[NB];
         zero_acc(acc);
-        // software pipeline: the x_i / x_j operands of K group g+1 (4 x 16 B per lane and operand) are in
-        // flight while the 16*NB MFMAs of group g execute (2048+ cycles >> L2 latency)
-        constexpr int G = 4;                               // 16-byte steps per group
-        float4 ca[G], cb[G], na[G], nb4[G];
-#pragma unroll
-        for (int t = 0; t < G; ++t) {
-            ca[t] = *reinterpret_cast<const float4*>(xi + 4 * t);
-            cb[t] = *reinterpret_cast<const float4*>(xj + 4 * t);
-        }
-        const int ngroups = S / (8 * G);                   // S is a multiple of 64 on this path
-        for (int g = 0; g < ngroups; ++g) {
-            // UNCONDITIONAL prefetch (the last iteration re-reads its own group): with the loads under an `if`
-            // hipcc merges the two paths into `s_waitcnt vmcnt(0)` in front of the MFMAs and the prefetch is lost
-            const int gn = (g + 1 < ngroups) ? g + 1 : g;
-#pragma unroll
-            for (int t = 0; t < G; ++t) {
-                na[t] = *reinterpret_cast<const float4*>(xi + 4 * (G * gn + t));
-                nb4[t] = *reinterpret_cast<const float4*>(xj + 4 * (G * gn + t));
+        pt.mark(0);                                         // 0: task decode
+        if constexpr (B3) {
+            // software pipeline: the operands of K step s+1 are in flight while step s is split and multiplied
+            float4 ca0 = *reinterpret_cast<const float4*>(xi), ca1 = *reinterpret_cast<const float4*>(xi + 4);
+            float4 cb0 = *reinterpret_cast<const float4*>(xj), cb1 = *reinterpret_cast<const float4*>(xj + 4);
+            const int nsteps = S / 16;
+            for (int st = 0; st < nsteps; ++st) {
+                const int sn = (st + 1 < nsteps) ? st + 1 : st;             // unconditional prefetch (clamped)
+                const float4 na0 = *reinterpret_cast<const float4*>(xi + 16 * sn), na1 = *reinterpret_cast<const float4*>(xi + 16 * sn + 4);
+                const float4 nb0 = *reinterpret_cast<const float4*>(xj + 16 * sn), nb1 = *reinterpret_cast<const float4*>(xj + 16 * sn + 4);
+                const float f[8] = {ca0.x * cb0.x, ca0.y * cb0.y, ca0.z * cb0.z, ca0.w * cb0.w,
+                                    ca1.x * cb1.x, ca1.y * cb1.y, ca1.z * cb1.z, ca1.w * cb1.w};
+                h2_nat_step<NB>(W, P, S / 8, st, f, acc, r, hi);
+                __builtin_amdgcn_sched_barrier(0);
+                ca0 = na0; ca1 = na1; cb0 = nb0; cb1 = nb1;
             }
+        } else {
+            const float* wl = W + r * (S + 4) + kb;
+            // software pipeline: the x_i / x_j operands of K group g+1 (4 x 16 B per lane and operand) are in
+            // flight while the 16*NB MFMAs of group g execute (2048+ cycles >> L2 latency)
+            constexpr int G = 4;                               // 16-byte steps per group
+            float4 ca[G], cb[G], na[G], nb4[G];
 #pragma unroll
             for (int t = 0; t < G; ++t) {
-                const float f0 = ca[t].x * cb[t].x, f1 = ca[t].y * cb[t].y, f2 = ca[t].z * cb[t].z, f3 = ca[t].w * cb[t].w;
+                ca[t] = *reinterpret_cast<const float4*>(xi + 4 * t);
+                cb[t] = *reinterpret_cast<const float4*>(xj + 4 * t);
+            }
+            const int ngroups = S / (8 * G);                   // S is a multiple of 64 on this path
+            for (int g = 0; g < ngroups; ++g) {
+                // UNCONDITIONAL prefetch (the last iteration re-reads its own group): with the loads under an `if`
+                // hipcc merges the two paths into `s_waitcnt vmcnt(0)` in front of the MFMAs and the prefetch is lost
+                const int gn = (g + 1 < ngroups) ? g + 1 : g;
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    const float4 wv = *reinterpret_cast<const float4*>(wl + nb * 32 * (S + 4) + 4 * (G * g + t));
-                    acc[nb] = mfma32(wv.x, f0, acc[nb]);
-                    acc[nb] = mfma32(wv.y, f1, acc[nb]);
-                    acc[nb] = mfma32(wv.z, f2, acc[nb]);
-                    acc[nb] = mfma32(wv.w, f3, acc[nb]);
+                for (int t = 0; t < G; ++t) {
+                    na[t] = *reinterpret_cast<const float4*>(xi + 4 * (G * gn + t));
+                    nb4[t] = *reinterpret_cast<const float4*>(xj + 4 * (G * gn + t));
                 }
-            }
-            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int t = 0; t < G; ++t) { ca[t] = na[t]; cb[t] = nb4[t]; }
+                for (int t = 0; t < G; ++t) {
+                    const float f0 = ca[t].x * cb[t].x, f1 = ca[t].y * cb[t].y, f2 = ca[t].z * cb[t].z, f3 = ca[t].w * cb[t].w;
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb) {
+                        const float4 wv = *reinterpret_cast<const float4*>(wl + nb * 32 * (S + 4) + 4 * (G * g + t));
+                        acc[nb] = mfma32(wv.x, f0, acc[nb]);
+                        acc[nb] = mfma32(wv.y, f1, acc[nb]);
+                        acc[nb] = mfma32(wv.z, f2, acc[nb]);
+                        acc[nb] = mfma32(wv.w, f3, acc[nb]);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int t = 0; t < G; ++t) { ca[t] = na[t]; cb[t] = nb4[t]; }
+            }
         }
+        pt.mark(1);                                         // 1: K loop (x_i x_j products, [splits,] MFMAs)
         // epilogue: (i,j) for j >= i ... and the mirrored (j,i) for j > i; positions j < i of the diagonal block belong
         // to the task of row j (which has i in ITS block, i > j)
         float ui[KH], uj[KH], pr[KH];
@@ -747,90 +704,13 @@ __global__ __launch_bounds__(NW * 64) void outer_linear_res_kernel(int* queue, f
         const long off = (bi * N + jj) * P;
         load_row_cll<P>(pair + off, hi, upper && residual, pr);
 #pragma unroll
-        for (int s = 0; s < KH; ++s) pr[s] = pr[s] + (((acc[s >> 4][s & 15] + ui[s]) - uj[s]) + bl[hi * KH + s]);
-        store_row_cll<P>(out + off, hi, upper, pr);
-        const long offm = (((long)bb * N + jj) * N + i) * P;
-        load_row_cll<P>(pair + offm, hi, mirror && residual, pr);
-#pragma unroll
-        for (int s = 0; s < KH; ++s) pr[s] = pr[s] + (((acc[s >> 4][s & 15] + uj[s]) - ui[s]) + bl[hi * KH + s]);
-        store_row_cll<P>(out + offm, hi, mirror, pr);
-    }
-}
-
-// The same on the fp16 matrix pipe (gemm mode 1): W1 as fp16 hi | lo planes (the size of the fp32 image, so it stays resident),
-// the generated operand x_i * x_j split per K step, three products per step (prd_common.h: rowgemm_h2 scheme).  K runs in
-// natural order: K step s of lane (r, hi) covers k = 16 s + 8 hi .. + 7.  S must be a multiple of 128.
-// LDS bytes: W1 as fp16 hi | lo planes [2][P][S / 8] of 16 bytes | bias [P]
-size_t outer_linear_res_h2_lds_bytes(int P, int S) { return (size_t)4 * P * S + 4 * P; }
-template <int P, int NW>
-__global__ __launch_bounds__(NW * 64) void outer_linear_res_h2_kernel(float* out, const float* pair,
-                                                                      const float* __restrict__ x, const float* __restrict__ u,
-                                                                      const float* __restrict__ w, const float* __restrict__ bias,
-                                                                      int b, int N, int S, int residual, int ldu) {
-    constexpr int NB = P / 32, KH = P / 2;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_ol[];
-    u32x4* Wh = reinterpret_cast<u32x4*>(smem_ol);          // [2 planes][P rows][S/8 slots]
-    const int SL = S / 8;
-    float* bl = reinterpret_cast<float*>(Wh + 2 * P * SL);  // [P] CLL
-    PairPhaseTimer pt;
-    stage_weight_h2_nat(Wh, w, P, S, 2 * S, 0, threadIdx.x, NW * 64, H2_WSCALE);
-    stage_vec_cll(bl, bias, P, threadIdx.x, NW * 64);
-    __syncthreads();
-    pt.mark(6);                                             // 6: prologue (W1 staging, barrier)
-    const int lane = threadIdx.x & 63, r = lane & 31, hi = lane >> 5;
-    const int nvb = (N + 31) / 32;
-    const int npairs = nvb * (nvb + 1) / 2;                // block pairs (ib <= jb)
-    const long ntask = (long)b * npairs * 32;              // 32 rows i per block pair
-    WaveTasks tasks(nullptr, ntask, NW);
-    for (long task = tasks.next(); task >= 0; task = tasks.next()) {
-        const int ii = (int)(task & 31);
-        const long t2 = task >> 5;
-        const int bb = (int)(t2 / npairs);
-        int pidx = (int)(t2 - (long)bb * npairs);
-        int ib = 0;
-        while (pidx >= nvb - ib) { pidx -= nvb - ib; ++ib; }
-        const int jb = ib + pidx;
-        const int i = ib * 32 + ii;
-        if (i >= N) continue;                              // wave-uniform
-        const long bi = (long)bb * N + i;
-        const int j = jb * 32 + r;
-        const bool valid = j < N;
-        const int jj = valid ? j : 0;
-        const float* xi = x + bi * S + 8 * hi;
-        const float* xj = x + ((long)bb * N + jj) * S + 8 * hi;
-        f32x16 acc[NB];
-        zero_acc(acc);
-        pt.mark(0);                                         // 0: task decode
-        // software pipeline: the operands of K step s+1 are in flight while step s is split and multiplied
-        float4 ca0 = *reinterpret_cast<const float4*>(xi), ca1 = *reinterpret_cast<const float4*>(xi + 4);
-        float4 cb0 = *reinterpret_cast<const float4*>(xj), cb1 = *reinterpret_cast<const float4*>(xj + 4);
-        const int nsteps = S / 16;
-        for (int st = 0; st < nsteps; ++st) {
-            const int sn = (st + 1 < nsteps) ? st + 1 : st;             // unconditional prefetch (clamped)
-            const float4 na0 = *reinterpret_cast<const float4*>(xi + 16 * sn), na1 = *reinterpret_cast<const float4*>(xi + 16 * sn + 4);
-            const float4 nb0 = *reinterpret_cast<const float4*>(xj + 16 * sn), nb1 = *reinterpret_cast<const float4*>(xj + 16 * sn + 4);
-            const float f[8] = {ca0.x * cb0.x, ca0.y * cb0.y, ca0.z * cb0.z, ca0.w * cb0.w,
-                                ca1.x * cb1.x, ca1.y * cb1.y, ca1.z * cb1.z, ca1.w * cb1.w};
-            h2_nat_step<NB>(Wh, P, SL, st, f, acc, r, hi);
-            __builtin_amdgcn_sched_barrier(0);
-            ca0 = na0; ca1 = na1; cb0 = nb0; cb1 = nb1;
-        }
-        pt.mark(1);                                         // 1: K loop (x_i x_j products, splits, MFMAs)
-        // epilogue: (i,j) for j >= i and the mirrored (j,i) for j > i (see outer_linear_res_kernel)
-        float ui[KH], uj[KH], pr[KH];
-        load_row_cll<P>(u + bi * ldu, hi, true, ui);
-        load_row_cll<P>(u + ((long)bb * N + jj) * ldu, hi, true, uj);
-        const bool upper = valid && j >= i, mirror = valid && j > i;
-        const long off = (bi * N + jj) * P;
-        load_row_cll<P>(pair + off, hi, upper && residual, pr);
-#pragma unroll
-        for (int s_ = 0; s_ < KH; ++s_) pr[s_] = pr[s_] + (((acc[s_ >> 4][s_ & 15] * H2_INV_WSCALE + ui[s_]) - uj[s_]) + bl[hi * KH + s_]);
+        for (int s = 0; s < KH; ++s) pr[s] = pr[s] + (((acc_out<B3>(acc[s >> 4][s & 15]) + ui[s]) - uj[s]) + bl[hi * KH + s]);
         store_row_cll<P>(out + off, hi, upper, pr);
         pt.mark(2);                                         // 2: u / pair rows, first store
         const long offm = (((long)bb * N + jj) * N + i) * P;
         load_row_cll<P>(pair + offm, hi, mirror && residual, pr);
 #pragma unroll
-        for (int s_ = 0; s_ < KH; ++s_) pr[s_] = pr[s_] + (((acc[s_ >> 4][s_ & 15] * H2_INV_WSCALE + uj[s_]) - ui[s_]) + bl[hi * KH + s_]);
+        for (int s = 0; s < KH; ++s) pr[s] = pr[s] + (((acc_out<B3>(acc[s >> 4][s & 15]) + uj[s]) - ui[s]) + bl[hi * KH + s]);
         store_row_cll<P>(out + offm, hi, mirror, pr);
         pt.mark(3);                                         // 3: mirrored pair rows + store
     }
@@ -1588,16 +1468,13 @@ extern "C" int prd_pair_init(float* pair, const float* static_pair, const float*
     if (!pair || !static_pair || !z || !mask || !centers || !w_dist || !ebeta || b <= 0 || N <= 0) return PRD_ERR_ARG;
     PRD_CHECK_P(P);
     if (dist_dim <= 0 || (dist_dim & 7)) return PRD_ERR_UNSUPPORTED;
-    const size_t lds = pair_init_lds_bytes(P, dist_dim);
-    if (lds > PRD_LDS_MAX) return PRD_ERR_UNSUPPORTED;
+    if (pair_init_lds_bytes(P, dist_dim) > PRD_LDS_MAX) return PRD_ERR_UNSUPPORTED;
     const long ntask = ((long)b * N * N + 31) / 32;
     const int grid = grid_for(ntask, 4, 512);
-    if (arith == PRD_ARITH_SPLIT16 && (dist_dim % 128) == 0) {        // fp16 x 2 split operands
-        return PRD_FOR_P(P, PP, prd_launch<pair_init_h2_kernel<PP>>(dim3(grid), dim3(WG), pair_init_h2_lds_bytes(P, dist_dim), stream, pair, static_pair, z, mask, centers, w_dist,
-                                                                    ebeta, b, N, dist_dim));
-    }
-    return PRD_FOR_P(P, PP, prd_launch<pair_init_kernel<PP>>(dim3(grid), dim3(WG), lds, stream, pair, static_pair, z, mask, centers, w_dist, ebeta,
-                                                             b, N, dist_dim));
+    const bool b3 = arith == PRD_ARITH_SPLIT16 && (dist_dim % 128) == 0;      // fp16 x 2 split operands
+    const size_t lds = b3 ? pair_init_h2_lds_bytes(P, dist_dim) : pair_init_lds_bytes(P, dist_dim);
+    return PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3, BB,
+        prd_launch<pair_init_kernel<PP, BB>>(dim3(grid), dim3(WG), lds, stream, pair, static_pair, z, mask, centers, w_dist, ebeta, b, N, dist_dim)));
 }
 
 extern "C" int prd_pair_bias(float* bias_out, const float* pair, const float* gamma, const float* beta,
@@ -1655,22 +1532,20 @@ extern "C" int prd_opm_pair(float* out, const float* pair, const float* ab, cons
     if (!out || !pair || !ab || !mask || !w_out || !b_out || b <= 0 || N <= 0) return PRD_ERR_ARG;
     PRD_CHECK_P(P);
     if (C <= 0 || (C & 7)) return PRD_ERR_UNSUPPORTED;
-    const size_t lds = opm_pair_lds_bytes(P, C);
-    if (lds > PRD_LDS_MAX) return PRD_ERR_UNSUPPORTED;
+    if (opm_pair_lds_bytes(P, C) > PRD_LDS_MAX) return PRD_ERR_UNSUPPORTED;
     const long ntask = (long)b * N * prd_ceil_div(N, 32);
     const int grid = grid_for(ntask, 4, 1024);
-    if (arith == PRD_ARITH_SPLIT16 && (C % 128) == 0) {               // fp16 x 2 split operands
-        return PRD_FOR_P(P, PP, prd_launch<opm_pair_h2_kernel<PP>>(dim3(grid), dim3(WG), opm_pair_h2_lds_bytes(P, C), stream, out, pair, ab, mask, w_out, b_out, b, N, C,
-                                                                   flags));
-    }
-    return PRD_FOR_P(P, PP, prd_launch<opm_pair_kernel<PP>>(dim3(grid), dim3(WG), lds, stream, out, pair, ab, mask, w_out, b_out, b, N, C, flags));
+    const bool b3 = arith == PRD_ARITH_SPLIT16 && (C % 128) == 0;             // fp16 x 2 split operands
+    const size_t lds = b3 ? opm_pair_h2_lds_bytes(P, C) : opm_pair_lds_bytes(P, C);
+    return PRD_FOR_P(P, PP, PRD_FOR_BOOL(b3, BB,
+        prd_launch<opm_pair_kernel<PP, BB>>(dim3(grid), dim3(WG), lds, stream, out, pair, ab, mask, w_out, b_out, b, N, C, flags)));
 }
 
 namespace {
 // OuterLinear with the K axis (single_dim) split over the eight waves of a workgroup (modules.py:283-287, split form
 // out[i,j,:] = W1 (x_i * x_j) + u_i - u_j + bias; symmetric half: the product term of (i, j) and (j, i) is the same).
 //
-// Why: the round-2 kernel (outer_linear_res_h2_kernel) gives one wave a whole (i, 32 j) tile and walks the 512 channels in 32
+// Why: the round-2 kernel (outer_linear_res_kernel<P, NW, true>) gives one wave a whole (i, 32 j) tile and walks the 512 channels in 32
 // dependent K steps.  Its time is neither MFMA (4.4 us of work) nor VALU: every operand / pair-row access is "one row per lane"
 // (16 bytes from each of 32-64 cache lines per instruction), and the texture-address path of a CU serialises a wave instruction
 // by cache line: ~10k cycles of address processing per tile (tools/phase_timing.py), 33 us per launch.  Here
@@ -1908,16 +1783,16 @@ extern "C" int prd_outer_linear(float* out, const float* pair, const float* x, c
     if (arith == PRD_ARITH_SPLIT16 && (S % 128) == 0 && outer_linear_res_h2_lds_bytes(P, S) <= PRD_LDS_MAX) {   // fp16 x 2 split operands
         constexpr int NWL = 8;
         const int grid = grid_for(nsym, 4, 256);
-        return PRD_FOR_P(P, PP, prd_launch<outer_linear_res_h2_kernel<PP, NWL>>(dim3(grid), dim3(NWL * 64), outer_linear_res_h2_lds_bytes(P, S), stream, out, pair, x, u, w, bias,
-                                                                                b, N, S, residual, ldu));
+        return PRD_FOR_P(P, PP, prd_launch<outer_linear_res_kernel<PP, NWL, true>>(dim3(grid), dim3(NWL * 64), outer_linear_res_h2_lds_bytes(P, S), stream, (int*)nullptr, out,
+                                                                                   pair, x, u, w, bias, b, N, S, residual, ldu));
     }
     if (lds <= OUTER_LINEAR_RES_LDS_MAX && (S % 64) == 0) {   // W1 resident in LDS: persistent 8-wave workgroups, queue-fed
         constexpr int NWL = 8;
         const int grid = grid_for(nsym, 4, 256);
         // fewer tasks than resident waves (symmetric half): the static assignment beats the queue (56 vs 74 us at N = 320)
         int* oq = (nsym > (long)grid * NWL) ? queue : nullptr;
-        return PRD_FOR_P(P, PP, prd_launch<outer_linear_res_kernel<PP, NWL>>(dim3(grid), dim3(NWL * 64), lds, stream, oq, out, pair, x, u, w, bias,
-                                                                             b, N, S, residual, ldu));
+        return PRD_FOR_P(P, PP, prd_launch<outer_linear_res_kernel<PP, NWL, false>>(dim3(grid), dim3(NWL * 64), lds, stream, oq, out, pair, x, u, w, bias,
+                                                                                    b, N, S, residual, ldu));
     }
     const int grid = grid_for(ntask, 4, 1024);       // very wide single track: stream W1 through LDS in K chunks
     return PRD_FOR_P(P, PP, prd_launch<outer_linear_kernel<PP>>(dim3(grid), dim3(WG), 0, stream, out, pair, x, u, w, bias, b, N, S, residual, ldu));

@@ -3,8 +3,15 @@ values of the host-only queries, held to a recording.  The trace build of the li
 -DPRD_LAUNCH_TRACE, build.py variant "trace") prints a line per launch instead of launching; tests/native/launch_trace.c walks the
 entry points over a sweep of shapes, arithmetics, switches and head layouts.  tests/golden/launch_trace.txt.xz is that output for the
 commit BEFORE the LDS sizes and the dispatch decisions were gathered into named host functions (only the trace #ifdef applied to it):
-a refactor of the launch sites must reproduce it line for line.  The fixture is still that pre-refactor recording, with one kernel
-renamed in it: tri_attn_core_kernel<P, 12, true, false> became <P, 12> when its two dead template parameters went.  No device is touched."""
+a refactor of the launch sites must reproduce it line for line.  The fixture is still that pre-refactor recording, with kernels
+renamed in it and nothing else: tri_attn_core_kernel<P, 12, true, false> became <P, 12> when its two dead template parameters went;
+and when the fp32 and split-16 forms of four kernels became one body each, with the arithmetic as a template argument,
+    pair_init_kernel<P> -> pair_init_kernel<P, false>                 pair_init_h2_kernel<P> -> pair_init_kernel<P, true>
+    opm_pair_kernel<P> -> opm_pair_kernel<P, false>                   opm_pair_h2_kernel<P> -> opm_pair_kernel<P, true>
+    outer_linear_res_kernel<P, 8> -> outer_linear_res_kernel<P, 8, false>
+    outer_linear_res_h2_kernel<P, 8> -> outer_linear_res_kernel<P, 8, true>, whose lines gained the null `queue` pointer as first argument
+    linear_wgrad_kernel<NBLK> -> linear_wgrad_kernel<NBLK, false>     linear_wgrad_h2_kernel<NBLK> -> linear_wgrad_kernel<NBLK, true>
+No device is touched."""
 import lzma
 import os
 import re

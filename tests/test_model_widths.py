@@ -90,18 +90,18 @@ def ol_form(S, P, split):
     if split and S in (128, 256, 512):
         return "outer_linear_ks_kernel"
     if split and S % 128 == 0 and 4 * P * S + 4 * P <= 160 * 1024:
-        return "outer_linear_res_h2_kernel"
+        return "outer_linear_res_kernel<B3>"
     if (P * (S + 4) + P) * 4 <= 150 * 1024 and S % 64 == 0:
-        return "outer_linear_res_kernel"
+        return "outer_linear_res_kernel<fp32>"
     return "outer_linear_kernel"
 
 
 def opm_form(S, split):
-    return "opm_pair_h2_kernel" if split and (S // 4) % 128 == 0 else "opm_pair_kernel"
+    return "opm_pair_kernel<B3>" if split and (S // 4) % 128 == 0 else "opm_pair_kernel<fp32>"
 
 
 def pair_init_form(D, split):
-    return "pair_init_h2_kernel" if split and D % 128 == 0 else "pair_init_kernel"
+    return "pair_init_kernel<B3>" if split and D % 128 == 0 else "pair_init_kernel<fp32>"
 
 
 def pair_head_form(P, D, S, split):
@@ -176,9 +176,9 @@ def _sid(c):
 def test_mirrors_reach_every_branch():
     """The operator table lands on every branch the issue of these widths named (otherwise a parametrization drifted)."""
     ol = {ol_form(S, P, sp) for S, P, _ in S_CASES for sp in (False, True)}
-    assert ol == {"outer_linear_kernel", "outer_linear_res_h2_kernel", "outer_linear_res_kernel"}, ol
-    assert {opm_form(S, sp) for S, _, _ in S_CASES for sp in (False, True)} == {"opm_pair_kernel", "opm_pair_h2_kernel"}
-    assert {pair_init_form(D, sp) for D in (16, 64, 136, 384) for sp in (False, True)} == {"pair_init_kernel", "pair_init_h2_kernel"}
+    assert ol == {"outer_linear_kernel", "outer_linear_res_kernel<B3>", "outer_linear_res_kernel<fp32>"}, ol
+    assert {opm_form(S, sp) for S, _, _ in S_CASES for sp in (False, True)} == {"opm_pair_kernel<fp32>", "opm_pair_kernel<B3>"}
+    assert {pair_init_form(D, sp) for D in (16, 64, 136, 384) for sp in (False, True)} == {"pair_init_kernel<fp32>", "pair_init_kernel<B3>"}
     assert {spa_form(S, True) for S, _, _ in S_CASES} == {"prd_spa_attn_core", "gemm"}
     assert any(not ops.ln_fusable(S) for S, _, _ in S_CASES) and any(ops.ln_fusable(S) for S, _, _ in S_CASES)
 

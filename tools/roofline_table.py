@@ -26,6 +26,7 @@ def algorithmic(N, P, S, H=4, c=16):
     """kernel -> (flops, bytes) per launch at b = 1 (U = N^2 P 4 bytes)."""
     U = N * N * P * 4
     Hc = H * c
+    # (keys: kernel names without their template arguments -- pair_init / opm_pair / outer_linear_res are one kernel for both arithmetics)
     return {
         "tri_attn_core_v2_kernel": (8 * N * N * P * Hc + 4 * Hc * N ** 3, 2 * U),
         "tri_attn_core_v2l_kernel": (8 * N * N * P * Hc + 4 * Hc * N ** 3, 2 * U),
@@ -38,12 +39,12 @@ def algorithmic(N, P, S, H=4, c=16):
         "tri_mul_contract_split_kernel": (2 * P * N ** 3, 3 * U),
         "tri_mul_out_kernel": (4 * N * N * P * P, 3 * U),
         "tri_mul_out_proj_kernel": (12 * N * N * P * P, 5 * U),
-        "outer_linear_res_h2_kernel": (N * N * S * P + 4 * N * S * P, 2 * U),       # symmetric half of 2 N^2 S P
+        "outer_linear_res_kernel": (N * N * S * P + 4 * N * S * P, 2 * U),       # symmetric half of 2 N^2 S P
         "outer_linear_ks_kernel": (N * N * S * P + 4 * N * S * P, 2 * U),
-        "pair_init_h2_kernel": (2 * N * N * 256 * P, 2 * U),
+        "pair_init_kernel": (2 * N * N * 256 * P, 2 * U),
         # pair_init + OPM tail + the two first bias heads in one row pass: static pair in, pair out (+ 2 x [H,N,N] outputs)
         "pair_head_h2_kernel": (2 * N * N * 256 * P + 2 * N * N * (S // 4) * P + 2 * 2 * N * N * P * H, 2 * U + 2 * H * N * N * 4),
-        "opm_pair_h2_kernel": (2 * N * N * (S // 4) * P, 2 * U),
+        "opm_pair_kernel": (2 * N * N * (S // 4) * P, 2 * U),
         "coord_head_kernel": (2 * N * N * P * P + 2 * N * N * P, 2 * U),
         "pair_bias_kernel": (2 * 2 * N * N * P * H, U),
     }
