@@ -45,6 +45,14 @@ LIB_TMALIGN, TMALIGN_SOURCES = SIDE_LIBS["tmalign"].lib, SIDE_LIBS["tmalign"].so
 LIB_QUALITY, QUALITY_SOURCES = SIDE_LIBS["quality"].lib, SIDE_LIBS["quality"].sources
 LIB_CONDITION, CONDITION_SOURCES = SIDE_LIBS["condition"].lib, SIDE_LIBS["condition"].sources
 LIB_SEQUENCE, SEQUENCE_SOURCES = SIDE_LIBS["sequence"].lib, SIDE_LIBS["sequence"].sources
+# The loop libraries: the same SideLib tuples, the same flags and compile routine (build_side serves both maps), for what runs INSIDE the
+# sampling loop without being part of the denoiser ABI.  They are kept apart from SIDE_LIBS because that map is what the side-library
+# launch trace (build_trace_side, tests/native/side_launch_trace.c) walks; each source sits in a directory of its own under csrc/.
+#   solver   libprd_solver.so (include/prd_solver.h): the step boundary of few-step sampling (solver.py) -- strided ancestral and DDIM
+#            loops over K visited levels; called by the sampling loop only when a solver is given
+LOOP_LIBS = {"solver": SideLib([os.path.join("solver", "prd_solver.hip")], [os.path.join(_INCLUDE, "prd_solver.h"), PRD_LAUNCH_H],
+                               os.path.join(HERE, "libprd_solver.so"), "--solver")}
+LIB_SOLVER, SOLVER_SOURCES = LOOP_LIBS["solver"].lib, LOOP_LIBS["solver"].sources
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -109,7 +117,7 @@ def _hipcc():
 
 def _headers(src):
     """the headers an object of ``src`` depends on"""
-    return next((s.headers for s in SIDE_LIBS.values() if src in s.sources), HEADERS)
+    return next((s.headers for s in list(SIDE_LIBS.values()) + list(LOOP_LIBS.values()) if src in s.sources), HEADERS)
 
 
 def _stamp(src):
@@ -185,6 +193,7 @@ def _build(v: Variant, sources, force: bool = False, verbose: bool = True) -> st
         objs.append(obj)
         if not (force or _stale(obj, [spath] + _headers(src))):
             continue
+        os.makedirs(os.path.dirname(obj), exist_ok=True)        # a source in a directory of its own keeps its object there
         cmd = [_hipcc()] + FLAGS + EXTRA_FLAGS.get(src, []) + v.cflags + ["-c", spath, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
@@ -208,10 +217,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
 
 def build_side(name: str, force: bool = False, verbose: bool = True, variant: str = "shipped") -> str:
-    """The side library ``name`` of SIDE_LIBS: its sources with the committed FLAGS and the shipped variant's extras, objects beside
+    """The side library ``name`` of SIDE_LIBS (or the loop library ``name`` of LOOP_LIBS): its sources with the committed FLAGS and the shipped variant's extras, objects beside
     the denoiser's.  Not a variant of libprd_hip.so: ``build()`` compiles none of it, and no side library compiles another.
     ``variant="trace"``: the trace variant's flags and object directory, the library libprd_<name>_trace.so."""
-    s, v = SIDE_LIBS[name], VARIANTS[variant]
+    s, v = (SIDE_LIBS[name] if name in SIDE_LIBS else LOOP_LIBS[name]), VARIANTS[variant]
     lib = s.lib if variant == "shipped" else s.lib.replace(".so", f"_{variant}.so")
     return _build(Variant(v.cflags, v.ldflags, v.objdir, lib, None), s.sources, force, verbose)
 
@@ -239,6 +248,11 @@ def build_condition(force: bool = False, verbose: bool = True) -> str:
 def build_sequence(force: bool = False, verbose: bool = True) -> str:
     """libprd_sequence.so (include/prd_sequence.h, protein_redesign_amd/sequence.py)"""
     return build_side("sequence", force, verbose)
+
+
+def build_solver(force: bool = False, verbose: bool = True) -> str:
+    """libprd_solver.so (include/prd_solver.h, protein_redesign_amd/solver.py)"""
+    return build_side("solver", force, verbose)
 
 
 def build_asan(verbose: bool = True) -> str:
@@ -305,12 +319,12 @@ if __name__ == "__main__":
         sys.exit(subprocess.call([build_trace()]))
     if "--trace-side" in sys.argv:
         sys.exit(subprocess.call([build_trace_side()]))
-    for side, s in SIDE_LIBS.items():
+    for side, s in list(SIDE_LIBS.items()) + list(LOOP_LIBS.items()):
         if s.flag in sys.argv:
             print(build_side(side, force="--force" in sys.argv))
             sys.exit(0)
-    if "--resources" in sys.argv:                   # the denoiser's kernels, then those of each side library
-        for sources in [SOURCES] + [s.sources for s in SIDE_LIBS.values()]:
+    if "--resources" in sys.argv:                   # the denoiser's kernels, then those of each side and loop library
+        for sources in [SOURCES] + [s.sources for s in list(SIDE_LIBS.values()) + list(LOOP_LIBS.values())]:
             for name, u in sorted(resource_usage(verbose=True, sources=sources).items()):
                 print(f"{u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}")
         sys.exit(0)

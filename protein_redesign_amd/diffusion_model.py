@@ -30,6 +30,7 @@ from .schedule import reverse_coefficients, schedule_tables
 from .conditioning import BATCH_KEY as SCAFFOLD_KEY, Scaffold, condition_rows_, level_table
 from .masking import MaskDraws, Redesign
 from .sequence import BATCH_KEY as RULES_KEY, SequenceRules, constrain_rows_
+from .solver import Solver, check_time_dim, solver_boundary_
 from .synthetic import NoiseSource
 from .trunk import Denoiser, Linear
 
@@ -423,10 +424,12 @@ class ProteinReDiffModel(_Base):
                                      "or nonfinite_policy = 'fp32'" if cur == 1 else ": the weights / inputs themselves produce inf or NaN"))
 
     def predict_step(self, batch, batch_idx, redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None,
-                     sequence_rules: Optional[SequenceRules] = None):
+                     sequence_rules: Optional[SequenceRules] = None, solver: Optional[Solver] = None):
         kw = {} if scaffold is None else {"scaffold": scaffold}
         if sequence_rules is not None:
             kw["sequence_rules"] = sequence_rules
+        if solver is not None:
+            kw["solver"] = solver
         with self.ema.average_parameters(self.parameters()):
             return self.sample(batch, batch_idx=batch_idx, redesign=redesign, **kw)
 
@@ -532,6 +535,21 @@ class ProteinReDiffModel(_Base):
         if self.training_mode:
             raise ValueError("sequence rules constrain what inference designs; under training_mode=True they are refused")
         return rules
+
+    def _solver_spec(self, solver: Optional[Solver], scaffold: Optional[Scaffold] = None) -> Optional[Solver]:
+        """The solver of a call: the keyword or None -- there is no attribute.  A solver chooses the levels inference visits; the
+        training recipe draws its own: a solver under ``training_mode=True`` is an error.  Everything host data decides is decided
+        here, before any library call: the time embedding the boundary kernel holds, and that the levels fit this model's schedule
+        and the scaffold's starting level."""
+        if solver is None:
+            return None
+        if not isinstance(solver, Solver):
+            raise TypeError(f"solver must be a solver.Solver, got {type(solver).__name__}")
+        if self.training_mode:
+            raise ValueError("a solver chooses the levels inference visits; under training_mode=True it is refused")
+        check_time_dim(self.time_dim)
+        solver.levels(self.num_steps, scaffold.start if scaffold is not None else None)
+        return solver
 
     def _redesign_mask(self, batch, spec: Redesign):
         """(extra, inv) of a design region, built on the device without a host synchronisation.  ``within`` / ``nearest``: ONE
@@ -678,8 +696,11 @@ class ProteinReDiffModel(_Base):
     # ------------------------------------------------------------------ reverse diffusion (model.py:377-422)
     @torch.inference_mode()
     def sample(self, batch, sources: Optional[Sequence] = None, batch_idx: Optional[int] = None, mask_draws: Optional[MaskDraws] = None,
-               redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None, sequence_rules: Optional[SequenceRules] = None):
-        """``scaffold`` (conditioning.Scaffold, keyword only): keep rows of the complex where the input structure has them and / or
+               redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None, sequence_rules: Optional[SequenceRules] = None,
+               solver: Optional[Solver] = None):
+        """``solver`` (solver.Solver, keyword only): visit K chosen levels instead of all ``num_steps`` -- strided ancestral sampling or
+        DDIM, K network evaluations per sample (``ReverseDiffusion``); a repeat under fp32 runs the same solver.
+        ``scaffold`` (conditioning.Scaffold, keyword only): keep rows of the complex where the input structure has them and / or
         start from the noised input (``ReverseDiffusion``); the positions then come back in the INPUT's frame.  ``sequence_rules``
         (sequence.SequenceRules, keyword only): the classes the ruled residues may take and the bias on their logits, applied to the
         sequence state after every step and to the returned logits (``ReverseDiffusion``)."""
@@ -688,6 +709,8 @@ class ProteinReDiffModel(_Base):
         cond = {} if self._scaffold_spec(scaffold) is None else {"scaffold": scaffold}
         if self._rules_spec(sequence_rules) is not None:         # deterministic too: the repeat prepares the same tables
             cond["sequence_rules"] = sequence_rules
+        if self._solver_spec(solver, scaffold) is not None:     # an immutable value: the repeat computes the same tables
+            cond["solver"] = solver
         if sources is None:
             sources = self._sources(batch["atom_mask"].shape[0], batch_idx)
         if self.training_mode and mask_draws is None:
@@ -723,6 +746,35 @@ class ProteinReDiffModel(_Base):
                                      "or nonfinite_policy = 'fp32'" if cur == 1 else ": the weights / inputs themselves produce inf or NaN"))
 
 
+def update_noise_rows(solver: Optional[Solver], T: int) -> int:
+    """Update-noise tensors [N,3] a loop draws per source after z_T and seq_T: T - 1 without a solver, K - 1 under a stochastic one,
+    none under a deterministic one."""
+    if solver is None:
+        return T - 1
+    return solver.K - 1 if solver.stochastic else 0
+
+
+def conditioning_noise_rows(solver: Optional[Solver], T: int, start: Optional[int]) -> int:
+    """Conditioning-noise tensors [N,3] a scaffold adds per source, after every other draw: one per level the loop visits"""
+    if solver is not None:
+        return solver.K
+    return (T - 1 if start is None else start) + 1
+
+
+def draw_loop_noise(sources, N: int, rows: int):
+    """(z_T [b,N,3], seq_T [b,N,21], update noise [rows,b,N,3] or None for rows = 0) from each sample's keyed source, in the
+    reference's per-sample order: z_T, seq_T, then the update tensors in the order the loop consumes them.  Host only."""
+    z0 = torch.stack([s.randn(N, 3) for s in sources])
+    s0 = torch.stack([s.randn(N, NUM_RESIDUE_CLASSES) for s in sources])
+    noise = torch.stack([torch.stack([s.randn(N, 3) for _ in range(rows)]) for s in sources], dim=1) if rows > 0 else None
+    return z0, s0, noise
+
+
+def draw_conditioning_noise(sources, N: int, rows: int) -> torch.Tensor:
+    """[rows,b,N,3]: per source ``rows`` tensors for the visited levels, highest level first.  Host only."""
+    return torch.stack([torch.stack([s.randn(N, 3) for _ in range(rows)]) for s in sources], dim=1)
+
+
 class ReverseDiffusion:
     """State and driver of one ``sample()`` call (reference model.py:377-422) on one GPU.
 
@@ -752,13 +804,28 @@ class ReverseDiffusion:
     rebuilds the coming step's single input.  With ``Scaffold(sequence=True)`` as well the order is constrain, hold, one
     prd_single_init: a held row wins.  A spec without any ban or bias (``inert``) rules no row by construction and launches nothing.
     The initial ``seq_t`` is noise on the design rows, as the reference initialises it, and stays as it is.  ``result()`` returns the
-    logits with the rules applied on the ruled rows."""
+    logits with the rules applied on the ruled rows.
+
+    ``solver`` (solver.Solver; beyond the reference): the loop visits the K levels ``tau_{K-1} > ... > tau_0`` the
+    spec chooses instead of all T.  A device counter ``k`` runs from K - 1 down to 0 beside ``t``, which holds the level itself;
+    ``steps_done``, ``run()``, ``reset()`` and ``restart(step, ...)`` count solver steps in [0, K).  The boundary of every step is ONE
+    launch of prd_solver_boundary (include/prd_solver.h), which indexes the level table [K] and the coefficient table [K,8]
+    (``Solver.tables``: float64 on the host, rounded once) by the counter; it has no un-fused form, so PRD_FUSED_BOUNDARY does not
+    apply.  One captured graph serves every step, and a replayed step has the launches it had.  A stochastic solver draws K - 1 update
+    tensors per source where the T - 1 of the full loop sit (the table is [K-1, b, N, 3], row K - 1 - k consumed at counter k > 0); a
+    deterministic one (``Solver.ddim(K)``) draws none and uploads no table.  ``x0_hat`` [b,N,3] holds the clean-structure estimate of
+    the last step, centred and in nanometres.  With a scaffold the kept rows are noised to the level that comes NEXT: the level and
+    conditioning-noise tables are compressed to the visited levels ([K,2], [K,b,N,3]: K conditioning draws per source) and
+    prd_condition_rows is handed the counter; ``start = L`` spreads the K levels over [L .. 0].  ``Solver.ancestral(T)`` is the loop
+    without a solver, bit for bit."""
 
     def __init__(self, model: "ProteinReDiffModel", batch, sources: Optional[Sequence] = None, mask_draws: Optional[MaskDraws] = None,
-                 redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None, sequence_rules: Optional[SequenceRules] = None):
+                 redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None, sequence_rules: Optional[SequenceRules] = None,
+                 solver: Optional[Solver] = None):
         m = self.model = model
         self.scaffold = scaffold = m._scaffold_spec(scaffold)
         self.sequence_rules = sequence_rules = m._rules_spec(sequence_rules)
+        self.solver = solver = m._solver_spec(solver, scaffold)
         if not m.setup_schedule:
             m.run_setup_schedule()
             m.setup_schedule = True
@@ -770,17 +837,21 @@ class ReverseDiffusion:
         self.mask = batch["residue_and_atom_mask"].contiguous()
         self.rm = batch["residue_mask"].contiguous()
         self.T = T = m.num_steps
-        z0 = torch.stack([s.randn(N, 3) for s in sources])
-        s0 = torch.stack([s.randn(N, NUM_RESIDUE_CLASSES) for s in sources])
-        if T > 1:
-            noise = torch.stack([torch.stack([s.randn(N, 3) for _ in range(T - 1)]) for s in sources], dim=1)
-        else:
+        self.K = T                              # steps_done of a finished loop: T, or the K of a solver
+        if solver is not None:
+            # host arithmetic only: the full-length special case recomputes the rows of m._coef as run_setup_schedule does (equal bits)
+            # instead of reading them back from the device
+            levels, coef = solver.tables(T, m.diffusion_schedule, scaffold.start if scaffold is not None else None)
+            self._levels = levels.tolist()      # host copy: restart() and reset() look levels up without reading the device
+            self.K = len(self._levels)
+        z0, s0, noise = draw_loop_noise(sources, N, update_noise_rows(solver, T))
+        if noise is None and solver is None:
             noise = torch.zeros(1, b, N, 3)
-        # with a scaffold or sequence rules the tables go up from pinned staging, ordered on the current stream, so that such a loop is
-        # set up without a host synchronisation; without either the uploads are the pageable copies they were
-        pinned = (scaffold is not None or sequence_rules is not None) and dev.type == "cuda"
+        # with a scaffold, sequence rules or a solver the tables go up from pinned staging, ordered on the current stream, so that such
+        # a loop is set up without a host synchronisation; without any of them the uploads are the pageable copies they were
+        pinned = (scaffold is not None or sequence_rules is not None or solver is not None) and dev.type == "cuda"
         up = self._upload = (lambda x: x.pin_memory().to(dev, non_blocking=True)) if pinned else (lambda x: x.to(dev))
-        self.noise = up(noise).contiguous()                          # [T-1, b, N, 3]
+        self.noise = up(noise).contiguous() if noise is not None else None      # [T-1, b, N, 3]; a solver: [K-1, b, N, 3] or None
         self.z = ops.remove_mean(up(z0).contiguous(), self.mask)
         seq_t = ops.remove_mean(up(s0).contiguous(), self.rm)
         self.seq_t = (batch["residue_extra_mask"].unsqueeze(-1) * batch["residue_one_hot"]
@@ -794,6 +865,13 @@ class ReverseDiffusion:
                 self.rules = (sequence_rules.table(batch), sequence_rules.rows(batch))
             batch[RULES_KEY] = self.rules[1] if self.rules is not None else torch.zeros_like(self.rm)
         self.t = torch.full((b,), T - 1, dtype=torch.int64, device=dev)
+        self.k = self.x0_hat = None
+        if solver is not None:                  # the counter beside the level, the two tables, the estimate of the last step
+            self._first = (self.K - 1, 0)
+            self.t.fill_(self._levels[-1])
+            self.k = torch.full((b,), self.K - 1, dtype=torch.int64, device=dev)
+            self.levels, self.coef = up(levels), up(coef)
+            self.x0_hat = torch.zeros(b, N, 3, dtype=torch.float32, device=dev)
         if scaffold is not None:
             self._condition(scaffold, sources, b, N, dev)
         self._init = (self.z.clone(), self.seq_t.clone())
@@ -802,8 +880,9 @@ class ReverseDiffusion:
         self.seq_pred = None
         # inputs of the coming step that the previous step's boundary kernel prepares (single, time embedding)
         import os
-        # time_dim > 512: the fused boundary has no room for the time features; the separate launches serve any width
-        self.fused_boundary = os.environ.get("PRD_FUSED_BOUNDARY", "1") != "0" and ops.step_boundary_fusable(m.time_dim)
+        # time_dim > 512: the fused boundary has no room for the time features; the separate launches serve any width.  Under a solver
+        # the boundary is always the one launch of prd_solver_boundary (no un-fused form; _solver_spec refused a wider time_dim)
+        self.fused_boundary = solver is not None or os.environ.get("PRD_FUSED_BOUNDARY", "1") != "0" and ops.step_boundary_fusable(m.time_dim)
         self.sync = torch.zeros(2, dtype=torch.int32, device=dev)     # [0] arrival counter, [1] sticky non-finite flag (prd_step_boundary)
         self._seq_pred_buf = None               # logits of the last step (written by the step-boundary kernel)
         self.single_in, self.eb_in = m._step_inputs(self.static, self.seq_t, self.rm, self.t)
@@ -821,20 +900,31 @@ class ReverseDiffusion:
         self.keep = scaffold.rows(batch)                                                           # K [b,N] or None
         batch[SCAFFOLD_KEY] = self.keep if self.keep is not None else torch.zeros_like(self.mask)
         self.level = level_table({k: getattr(m, k) for k in ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod")})
-        draws = torch.stack([torch.stack([s.randn(N, 3) for _ in range(L + 1)]) for s in sources], dim=1)     # [L+1,b,N,3]: levels L .. 0
-        table = self._upload(draws.flip(0).contiguous())                                               # indexed by level
-        self.cond_noise = ops.remove_mean(table.view((L + 1) * b, N, 3), self.mask.repeat(L + 1, 1)).view(L + 1, b, N, 3)
+        # one conditioning draw per level the loop visits, highest first: L + 1 without a solver, K with one -- whose tables are
+        # compressed to the visited levels and indexed by the counter (row k: level tau_k; rows picked, no arithmetic)
+        rows = conditioning_noise_rows(self.solver, T, scaffold.start)
+        if self.solver is not None:
+            self.level = self.level[self.levels].contiguous()
+        draws = draw_conditioning_noise(sources, N, rows)                                              # [rows,b,N,3]: levels L .. 0
+        table = self._upload(draws.flip(0).contiguous())                                               # indexed by level / by counter
+        self.cond_noise = ops.remove_mean(table.view(rows * b, N, 3), self.mask.repeat(rows, 1)).view(rows, b, N, 3)
         seq = dict(seq0=batch["residue_one_hot"].to(torch.float32).contiguous(),
                    keep_seq=batch["residue_extra_mask"].to(torch.float32).contiguous()) if scaffold.sequence else {}
         held = dict(x0c=self.x0c, noise=self.cond_noise, level=self.level)
-        self.t.fill_(L)
-        self._first = (L, T - 1 - L)
+        if self.solver is None:
+            self.t.fill_(L)
+            self._first = (L, T - 1 - L)
         # the initial state: with ``start`` every valid row is the noised input, otherwise the kept ones
         first = self.mask if scaffold.start is not None else self.keep
         if first is not None or seq:
-            condition_rows_(self.z, self.seq_t, self.t, keep_z=first, **(held if first is not None else {}), **seq)
+            condition_rows_(self.z, self.seq_t, self._counter, keep_z=first, **(held if first is not None else {}), **seq)
         if self.keep is not None or seq:
             self.cond = dict(keep_z=self.keep, **(held if self.keep is not None else {}), **seq)
+
+    @property
+    def _counter(self):
+        """what indexes the tables of prd_condition_rows: the level itself, or under a solver the counter over the visited levels"""
+        return self.k if self.solver is not None else self.t
 
     def _hold_rows(self, seq_pred):
         """After a boundary: the ruled rows of seq_t retaken under the sequence rules from the step's logits ``seq_pred``
@@ -845,7 +935,7 @@ class ReverseDiffusion:
         if self.rules is not None:
             constrain_rows_(self.seq_t, seq_pred, *self.rules)
         if self.cond is not None:
-            condition_rows_(self.z, self.seq_t, self.t, **self.cond)
+            condition_rows_(self.z, self.seq_t, self._counter, **self.cond)
         if self.fused_boundary and (clamp or self.rules is not None):
             ops.single_init(self.static["single"], self.seq_t, self.rm, self.model.embed_residue_type[1].weight, out=self.single_in)
 
@@ -854,11 +944,19 @@ class ReverseDiffusion:
         self.single_in.copy_(single)
         self.eb_in.copy_(eb)
 
+    def _set_counter(self, counter: int):
+        """every sample at ``counter``: the level itself, or under a solver the counter and the level it stands for (host values)"""
+        if self.solver is None:
+            self.t.fill_(counter)
+        else:
+            self.k.fill_(counter)
+            self.t.fill_(self._levels[counter])
+
     def reset(self):
         """Back to step T-1 with the same initial noise (bench / repeated runs)."""
         self.z.copy_(self._init[0])
         self.seq_t.copy_(self._init[1])
-        self.t.fill_(self._first[0])
+        self._set_counter(self._first[0])
         self.steps_done = self._first[1]
         self._refresh_step_inputs()
 
@@ -866,20 +964,32 @@ class ReverseDiffusion:
         """Continue from a given state: ``z`` / ``seq_t`` are the tensors ENTERING denoising step number ``step`` (0 = the
         first, t = T-1).  The pre-drawn noise table is indexed by the step counter, so the continuation consumes exactly the
         noise the uninterrupted loop would (checkpointed sampling; segment-wise parity tests)."""
-        if not 0 <= step < self.T:
-            raise ValueError(f"step must be in [0, {self.T}), got {step}")
+        if not 0 <= step < self.K:
+            raise ValueError(f"step must be in [0, {self.K}), got {step}")
         self.z.copy_(z.to(self.z.device))
         self.seq_t.copy_(seq_t.to(self.seq_t.device))
-        self.t.fill_(self.T - 1 - step)
+        self._set_counter(self.K - 1 - step)
         self.steps_done = step
         if self.cond is not None:               # the kept rows of the given state, at its level
-            condition_rows_(self.z, self.seq_t, self.t, **self.cond)
+            condition_rows_(self.z, self.seq_t, self._counter, **self.cond)
         self._refresh_step_inputs()
 
     def _enqueue_step(self):
         """Network forward on the inputs the previous boundary prepared, then ONE step-boundary launch: remove_mean, reverse
         update, t <- t - 1 and the next step's single / time-embedding inputs (ops.step_boundary_)."""
         m = self.model
+        if self.solver is not None:             # the same step with prd_solver_boundary as its one boundary launch
+            eps_raw, seq_h = m._network(self.batch, self.z, self.seq_t, self.mask, self.t, static=self.static,
+                                        step_inputs=(self.single_in, self.eb_in), raw_noise=True, defer_seq_head=True)
+            if self._seq_pred_buf is None:
+                self._seq_pred_buf = torch.empty(*self.seq_t.shape, device=self.seq_t.device, dtype=torch.float32)
+            solver_boundary_(self.z, self.seq_t, self.k, self.t, eps_raw, self._seq_pred_buf, self.noise, self.mask, self.levels, self.coef,
+                             self.T, self.single_in, self.static["single"], self.rm, m.embed_residue_type[1].weight,
+                             self.eb_in, m.embed_beta[0].weight, m.embed_beta[1].weight, self.sync, x0_out=self.x0_hat,
+                             seq_h=seq_h, w_seq=m.seq_mlp[3].weight)
+            if self.cond is not None or self.rules is not None:
+                self._hold_rows(self._seq_pred_buf)
+            return self._seq_pred_buf
         if not self.fused_boundary:             # the four separate launches (kept for A/B measurements: PRD_FUSED_BOUNDARY=0)
             noise_pred, seq_pred = m._network(self.batch, self.z, self.seq_t, self.mask, self.t, static=self.static)
             ops.reverse_update_(self.z, self.seq_t, self.t, noise_pred, seq_pred, self.noise, self.mask, m._coef, self.T)
@@ -901,8 +1011,9 @@ class ReverseDiffusion:
     @torch.inference_mode()
     def step(self):
         """One denoising step: network forward + reverse update (asynchronous)."""
-        if self.steps_done >= self.T:
-            raise RuntimeError("all num_steps denoising steps already done; call reset()")
+        if self.steps_done >= self.K:
+            raise RuntimeError("all num_steps denoising steps already done; call reset()" if self.solver is None else
+                               f"all {self.K} solver steps already done; call reset()")
         if self.graph is not None:
             self.graph.replay()
         elif self.model.use_hip_graph and self.steps_done >= 1 + self._first[1]:
@@ -915,7 +1026,7 @@ class ReverseDiffusion:
         self.steps_done += 1
 
     def run(self):
-        while self.steps_done < self.T:
+        while self.steps_done < self.K:
             self.step()
 
     def finite(self) -> bool:

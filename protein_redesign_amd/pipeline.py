@@ -549,9 +549,10 @@ def _references(model, data, redesign, align_to, correspondence, assess, scaffol
     return struct_ref, align_ref, quality_ref, spec
 
 
-def _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device, scaffold=None, sequence_rules=None, keep_logits=False):
-    """Stage (b): the sampling loop, with no synchronisation beyond its copies to the host; ``scaffold`` and ``sequence_rules`` reach
-    ``model.sample`` only when given.  Returns (positions per batch -- left on the
+def _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device, scaffold=None, sequence_rules=None, keep_logits=False,
+          solver=None):
+    """Stage (b): the sampling loop, with no synchronisation beyond its copies to the host; ``scaffold``, ``sequence_rules`` and
+    ``solver`` reach ``model.sample`` only when given.  Returns (positions per batch -- left on the
     device if ``keep_on_device``, for the stages that score them there --, logits per batch on the host -- on the device if
     ``keep_logits``, for the decoding there --, the first prepared batch, the keyed noise source of every sample as sample() left it)."""
     from .synthetic import NoiseSource, batch_to
@@ -559,6 +560,8 @@ def _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_devi
     cond = {} if scaffold is None else {"scaffold": scaffold}
     if sequence_rules is not None:
         cond["sequence_rules"] = sequence_rules
+    if solver is not None:
+        cond["solver"] = solver
     for start in range(0, num_samples, batch_size):
         idx = list(range(start, min(start + batch_size, num_samples)))
         batch = collate_fn([data] * len(idx))
@@ -709,7 +712,7 @@ def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffol
 @torch.inference_mode()
 def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_size: int = 1, seed: int = 0,
                      output_dir: Optional[Union[str, Path]] = None, redesign=None, align_to=None, mirror: bool = True,
-                     correspondence: str = "index", assess=None, scaffold=None, sequence_rules=None, decode=None):
+                     correspondence: str = "index", assess=None, scaffold=None, sequence_rules=None, decode=None, solver=None):
     """Draw ``num_samples`` samples of one featurised complex ``data`` (the dict of ligand_to_data ∪ protein_to_data).
 
     Returns (positions [S,N,3] in Angstrom, logits [S,N,21], proteins, ligand_positions).  With ``output_dir`` the CA
@@ -790,7 +793,16 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     (the fraction of the input's known residues a sample reproduces) and ``recovery_design`` [S] (the same over the redesigned residues
     only); ``against="input"`` is refused, before anything is uploaded, for an input whose ``residue_type`` is all unknown.
     ``output_dir`` also receives ``sample_sequences.fasta`` (one record per sample, the header carrying the mean ``logp`` and the
-    recovery) and ``sample_sequences.npz`` (the dict)."""
+    recovery) and ``sample_sequences.npz`` (the dict).
+
+    ``solver`` (solver.Solver, keyword only, default None: nothing changes): the levels the loop visits and the update between them --
+    ``Solver.ddim(50)``, ``Solver.ancestral(100)``, explicit ``timesteps`` -- handed to ``model.sample`` unchanged
+    (``diffusion_model.ReverseDiffusion``): K network evaluations per sample instead of ``num_steps``.  Refused, before the model is
+    touched, if it is no ``Solver``.  The return value gains no element and ``output_dir`` no file for it."""
+    if solver is not None:
+        from .solver import Solver
+        if not isinstance(solver, Solver):
+            raise TypeError(f"solver must be a solver.Solver, got {type(solver).__name__}")
     struct_ref, align_ref, quality_ref, spec = _references(model, data, redesign, align_to, correspondence, assess, scaffold,
                                                            sequence_rules, decode)
     device = model.device
@@ -803,7 +815,8 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     na, nr = int(data["num_atoms"]), int(data["num_residues"])
     scored = align_to is not None or assess is not None         # then the samples stay on the device until they are scored
     drawn, logits, first_batch, sources = _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device=scored,
-                                                scaffold=scaffold, sequence_rules=sequence_rules, keep_logits=decode is not None)
+                                                scaffold=scaffold, sequence_rules=sequence_rules, keep_logits=decode is not None,
+                                                solver=solver)
     # every sample of the complex shares the mask: read from the first prepared batch, after the loop (no synchronisation inside it)
     used_mask = first_batch["residue_inv_extra_mask"][0].cpu().numpy() if spec is not None and first_batch is not None else None
     kept = None
