@@ -53,6 +53,19 @@ LIB_SEQUENCE, SEQUENCE_SOURCES = SIDE_LIBS["sequence"].lib, SIDE_LIBS["sequence"
 LOOP_LIBS = {"solver": SideLib([os.path.join("solver", "prd_solver.hip")], [os.path.join(_INCLUDE, "prd_solver.h"), PRD_LAUNCH_H],
                                os.path.join(HERE, "libprd_solver.so"), "--solver")}
 LIB_SOLVER, SOLVER_SOURCES = LOOP_LIBS["solver"].lib, LOOP_LIBS["solver"].sources
+# The step libraries: again the same SideLib tuples, flags and compile routine, for what runs inside a sampling STEP, between the network
+# and the boundary, when the caller asks for it.  They are kept apart from both maps above: SIDE_LIBS is what the side-library launch trace
+# walks, and LOOP_LIBS is the set of step boundaries (a loop has exactly one of them; its tests pin the map to the solver's).
+#   guide    libprd_guide.so (include/prd_guide.h): guided sampling (guidance.py) -- the gradient of a clash and restraint energy on the
+#            step's clean-structure estimate, added to the predicted noise; called by the sampling loop only when guidance is given
+STEP_LIBS = {"guide": SideLib([os.path.join("guide", "prd_guide.hip")], [os.path.join(_INCLUDE, "prd_guide.h"), PRD_LAUNCH_H],
+                              os.path.join(HERE, "libprd_guide.so"), "--guide")}
+LIB_GUIDE, GUIDE_SOURCES = STEP_LIBS["guide"].lib, STEP_LIBS["guide"].sources
+
+
+def _own_libs():
+    """every library with a header of its own: the side libraries, then the loop libraries, then the step libraries"""
+    return list(SIDE_LIBS.items()) + list(LOOP_LIBS.items()) + list(STEP_LIBS.items())
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -117,7 +130,7 @@ def _hipcc():
 
 def _headers(src):
     """the headers an object of ``src`` depends on"""
-    return next((s.headers for s in list(SIDE_LIBS.values()) + list(LOOP_LIBS.values()) if src in s.sources), HEADERS)
+    return next((s.headers for _, s in _own_libs() if src in s.sources), HEADERS)
 
 
 def _stamp(src):
@@ -217,10 +230,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
 
 def build_side(name: str, force: bool = False, verbose: bool = True, variant: str = "shipped") -> str:
-    """The side library ``name`` of SIDE_LIBS (or the loop library ``name`` of LOOP_LIBS): its sources with the committed FLAGS and the shipped variant's extras, objects beside
+    """The side library ``name`` of SIDE_LIBS (or the loop library ``name`` of LOOP_LIBS, or the step library ``name`` of STEP_LIBS): its sources with the committed FLAGS and the shipped variant's extras, objects beside
     the denoiser's.  Not a variant of libprd_hip.so: ``build()`` compiles none of it, and no side library compiles another.
     ``variant="trace"``: the trace variant's flags and object directory, the library libprd_<name>_trace.so."""
-    s, v = (SIDE_LIBS[name] if name in SIDE_LIBS else LOOP_LIBS[name]), VARIANTS[variant]
+    s, v = dict(_own_libs())[name], VARIANTS[variant]
     lib = s.lib if variant == "shipped" else s.lib.replace(".so", f"_{variant}.so")
     return _build(Variant(v.cflags, v.ldflags, v.objdir, lib, None), s.sources, force, verbose)
 
@@ -253,6 +266,11 @@ def build_sequence(force: bool = False, verbose: bool = True) -> str:
 def build_solver(force: bool = False, verbose: bool = True) -> str:
     """libprd_solver.so (include/prd_solver.h, protein_redesign_amd/solver.py)"""
     return build_side("solver", force, verbose)
+
+
+def build_guide(force: bool = False, verbose: bool = True) -> str:
+    """libprd_guide.so (include/prd_guide.h, protein_redesign_amd/guidance.py)"""
+    return build_side("guide", force, verbose)
 
 
 def build_asan(verbose: bool = True) -> str:
@@ -319,12 +337,12 @@ if __name__ == "__main__":
         sys.exit(subprocess.call([build_trace()]))
     if "--trace-side" in sys.argv:
         sys.exit(subprocess.call([build_trace_side()]))
-    for side, s in list(SIDE_LIBS.items()) + list(LOOP_LIBS.items()):
+    for side, s in _own_libs():
         if s.flag in sys.argv:
             print(build_side(side, force="--force" in sys.argv))
             sys.exit(0)
-    if "--resources" in sys.argv:                   # the denoiser's kernels, then those of each side and loop library
-        for sources in [SOURCES] + [s.sources for s in list(SIDE_LIBS.values()) + list(LOOP_LIBS.values())]:
+    if "--resources" in sys.argv:                   # the denoiser's kernels, then those of each side, loop and step library
+        for sources in [SOURCES] + [s.sources for _, s in _own_libs()]:
             for name, u in sorted(resource_usage(verbose=True, sources=sources).items()):
                 print(f"{u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}")
         sys.exit(0)

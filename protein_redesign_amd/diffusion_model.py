@@ -28,6 +28,7 @@ from . import _lib, ops
 from .constants import ATOM_FEATURE_CARDS, BOND_FEATURE_CARDS, NUM_RESIDUE_CLASSES
 from .schedule import reverse_coefficients, schedule_tables
 from .conditioning import BATCH_KEY as SCAFFOLD_KEY, Scaffold, condition_rows_, level_table
+from .guidance import MAX_N as GUIDE_MAX_N, Guidance, guide_eps_
 from .masking import MaskDraws, Redesign
 from .sequence import BATCH_KEY as RULES_KEY, SequenceRules, constrain_rows_
 from .solver import Solver, check_time_dim, solver_boundary_
@@ -424,12 +425,15 @@ class ProteinReDiffModel(_Base):
                                      "or nonfinite_policy = 'fp32'" if cur == 1 else ": the weights / inputs themselves produce inf or NaN"))
 
     def predict_step(self, batch, batch_idx, redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None,
-                     sequence_rules: Optional[SequenceRules] = None, solver: Optional[Solver] = None):
+                     sequence_rules: Optional[SequenceRules] = None, solver: Optional[Solver] = None,
+                     guidance: Optional[Guidance] = None):
         kw = {} if scaffold is None else {"scaffold": scaffold}
         if sequence_rules is not None:
             kw["sequence_rules"] = sequence_rules
         if solver is not None:
             kw["solver"] = solver
+        if guidance is not None:
+            kw["guidance"] = guidance
         with self.ema.average_parameters(self.parameters()):
             return self.sample(batch, batch_idx=batch_idx, redesign=redesign, **kw)
 
@@ -550,6 +554,25 @@ class ProteinReDiffModel(_Base):
         check_time_dim(self.time_dim)
         solver.levels(self.num_steps, scaffold.start if scaffold is not None else None)
         return solver
+
+    def _guidance_spec(self, guidance: Optional[Guidance], solver: Optional[Solver] = None) -> Optional[Guidance]:
+        """The guidance of a call: the keyword or None -- there is no attribute.  Guidance steers inference; the training recipe noises
+        and denoises the data as it is: guidance under ``training_mode=True`` is an error.  prd_guide_eps sits between the network and a
+        boundary that takes the raw output of the coordinate head, which only the fused boundaries do: the un-fused form
+        (PRD_FUSED_BOUNDARY=0, or a time_dim above 512 without a solver) is refused.  Host data only: no library call."""
+        if guidance is None:
+            return None
+        if not isinstance(guidance, Guidance):
+            raise TypeError(f"guidance must be a guidance.Guidance, got {type(guidance).__name__}")
+        if self.training_mode:
+            raise ValueError("guidance steers the coordinates of inference; under training_mode=True it is refused")
+        import os
+        if solver is None and (os.environ.get("PRD_FUSED_BOUNDARY", "1") == "0" or not ops.step_boundary_fusable(self.time_dim)):
+            raise ValueError("guidance needs the fused step boundary, which takes the coordinate head's raw output: it is refused under "
+                             f"PRD_FUSED_BOUNDARY=0 and, without a solver, for a time_dim above 512 (this model has time_dim = "
+                             f"{self.time_dim}, PRD_FUSED_BOUNDARY={os.environ.get('PRD_FUSED_BOUNDARY', '1')})")
+        guidance.check_rows(GUIDE_MAX_N, "the library's rows")      # the batch's own N is checked when the loop knows it
+        return guidance
 
     def _redesign_mask(self, batch, spec: Redesign):
         """(extra, inv) of a design region, built on the device without a host synchronisation.  ``within`` / ``nearest``: ONE
@@ -697,8 +720,10 @@ class ProteinReDiffModel(_Base):
     @torch.inference_mode()
     def sample(self, batch, sources: Optional[Sequence] = None, batch_idx: Optional[int] = None, mask_draws: Optional[MaskDraws] = None,
                redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None, sequence_rules: Optional[SequenceRules] = None,
-               solver: Optional[Solver] = None):
-        """``solver`` (solver.Solver, keyword only): visit K chosen levels instead of all ``num_steps`` -- strided ancestral sampling or
+               solver: Optional[Solver] = None, guidance: Optional[Guidance] = None):
+        """``guidance`` (guidance.Guidance, keyword only): distance restraints and clash repulsion, evaluated on every step's
+        clean-structure estimate and added to the predicted noise (``ReverseDiffusion``).
+        ``solver`` (solver.Solver, keyword only): visit K chosen levels instead of all ``num_steps`` -- strided ancestral sampling or
         DDIM, K network evaluations per sample (``ReverseDiffusion``); a repeat under fp32 runs the same solver.
         ``scaffold`` (conditioning.Scaffold, keyword only): keep rows of the complex where the input structure has them and / or
         start from the noised input (``ReverseDiffusion``); the positions then come back in the INPUT's frame.  ``sequence_rules``
@@ -711,6 +736,8 @@ class ProteinReDiffModel(_Base):
             cond["sequence_rules"] = sequence_rules
         if self._solver_spec(solver, scaffold) is not None:     # an immutable value: the repeat computes the same tables
             cond["solver"] = solver
+        if self._guidance_spec(guidance, solver) is not None:   # an immutable value too
+            cond["guidance"] = guidance
         if sources is None:
             sources = self._sources(batch["atom_mask"].shape[0], batch_idx)
         if self.training_mode and mask_draws is None:
@@ -817,15 +844,30 @@ class ReverseDiffusion:
     the last step, centred and in nanometres.  With a scaffold the kept rows are noised to the level that comes NEXT: the level and
     conditioning-noise tables are compressed to the visited levels ([K,2], [K,b,N,3]: K conditioning draws per source) and
     prd_condition_rows is handed the counter; ``start = L`` spreads the K levels over [L .. 0].  ``Solver.ancestral(T)`` is the loop
-    without a solver, bit for bit."""
+    without a solver, bit for bit.
+
+    ``guidance`` (guidance.Guidance; beyond the reference): between the network and the boundary of every step ONE
+    launch of prd_guide_eps (include/prd_guide.h) evaluates the clash and restraint energy on the step's clean-structure estimate and
+    writes ``eps_raw + lam dE/dx0`` (capped per position) into a loop-owned buffer, which the boundary then receives in place of the
+    coordinate head's output.  The table {q, r, lam, cap} per counter (``Guidance.tables``: float64 on the host, rounded once; the rows
+    of the visited levels under a solver), the restraint lists and the clash floors go up once; the classes and the bond exclusions are
+    built on the device.  ``guidance_energy`` [b,N,2] holds every row's share of the clash and restraint energy at the last step's
+    estimate.  A replayed step has one launch more.  With a scaffold the kept rows are overwritten after the boundary as before: forces
+    on them are harmless and are not special-cased.  An ``inert`` spec launches nothing and uploads nothing.  A restraint must name rows
+    of the batch; rows beyond a sample's valid ones hold no structure, and ``pipeline.generate_samples`` refuses them on the host data."""
 
     def __init__(self, model: "ProteinReDiffModel", batch, sources: Optional[Sequence] = None, mask_draws: Optional[MaskDraws] = None,
                  redesign: Optional[Redesign] = None, scaffold: Optional[Scaffold] = None, sequence_rules: Optional[SequenceRules] = None,
-                 solver: Optional[Solver] = None):
+                 solver: Optional[Solver] = None, guidance: Optional[Guidance] = None):
         m = self.model = model
         self.scaffold = scaffold = m._scaffold_spec(scaffold)
         self.sequence_rules = sequence_rules = m._rules_spec(sequence_rules)
         self.solver = solver = m._solver_spec(solver, scaffold)
+        self.guidance = guidance = m._guidance_spec(guidance, solver)
+        if guidance is not None:
+            guidance.check_rows(batch["atom_mask"].shape[1], "the batch's rows")
+            if guidance.inert:
+                guidance = None                 # nothing can ever be added: nothing is uploaded, nothing is launched
         if not m.setup_schedule:
             m.run_setup_schedule()
             m.setup_schedule = True
@@ -847,9 +889,9 @@ class ReverseDiffusion:
         z0, s0, noise = draw_loop_noise(sources, N, update_noise_rows(solver, T))
         if noise is None and solver is None:
             noise = torch.zeros(1, b, N, 3)
-        # with a scaffold, sequence rules or a solver the tables go up from pinned staging, ordered on the current stream, so that such
+        # with a scaffold, sequence rules, a solver or guidance the tables go up from pinned staging, ordered on the current stream, so that such
         # a loop is set up without a host synchronisation; without any of them the uploads are the pageable copies they were
-        pinned = (scaffold is not None or sequence_rules is not None or solver is not None) and dev.type == "cuda"
+        pinned = (scaffold is not None or sequence_rules is not None or solver is not None or guidance is not None) and dev.type == "cuda"
         up = self._upload = (lambda x: x.pin_memory().to(dev, non_blocking=True)) if pinned else (lambda x: x.to(dev))
         self.noise = up(noise).contiguous() if noise is not None else None      # [T-1, b, N, 3]; a solver: [K-1, b, N, 3] or None
         self.z = ops.remove_mean(up(z0).contiguous(), self.mask)
@@ -872,6 +914,12 @@ class ReverseDiffusion:
             self.k = torch.full((b,), self.K - 1, dtype=torch.int64, device=dev)
             self.levels, self.coef = up(levels), up(coef)
             self.x0_hat = torch.zeros(b, N, 3, dtype=torch.float32, device=dev)
+        self.guide = self.guidance_energy = None        # the step-invariant arguments of guide_eps_ (None: no launch), its e_out
+        if guidance is not None:
+            self.guide = guidance.terms(batch, up)
+            self.guide["table"] = up(guidance.tables(T, m.diffusion_schedule, self._levels if solver is not None else None))
+            self._eps_guided = torch.empty(b, N, 3, dtype=torch.float32, device=dev)
+            self.guidance_energy = torch.zeros(b, N, 2, dtype=torch.float32, device=dev)
         if scaffold is not None:
             self._condition(scaffold, sources, b, N, dev)
         self._init = (self.z.clone(), self.seq_t.clone())
@@ -939,6 +987,16 @@ class ReverseDiffusion:
         if self.fused_boundary and (clamp or self.rules is not None):
             ops.single_init(self.static["single"], self.seq_t, self.rm, self.model.embed_residue_type[1].weight, out=self.single_in)
 
+    def _guide(self, eps_raw):
+        """Between the network and the boundary: the guided predicted noise in the loop's own buffer (prd_guide_eps, indexed by the
+        counter the boundary is about to consume), or ``eps_raw`` itself without guidance"""
+        if self.guide is None:
+            return eps_raw
+        g = self.guide
+        guide_eps_(self.z, eps_raw.contiguous(), self._eps_guided, self.mask, self._counter, g["table"], g["cls"], g["floors"], g["wclash"],
+                   g["exclude"], g["csr"], self.guidance_energy)
+        return self._eps_guided
+
     def _refresh_step_inputs(self):
         single, eb = self.model._step_inputs(self.static, self.seq_t, self.rm, self.t)
         self.single_in.copy_(single)
@@ -983,6 +1041,7 @@ class ReverseDiffusion:
                                         step_inputs=(self.single_in, self.eb_in), raw_noise=True, defer_seq_head=True)
             if self._seq_pred_buf is None:
                 self._seq_pred_buf = torch.empty(*self.seq_t.shape, device=self.seq_t.device, dtype=torch.float32)
+            eps_raw = self._guide(eps_raw)
             solver_boundary_(self.z, self.seq_t, self.k, self.t, eps_raw, self._seq_pred_buf, self.noise, self.mask, self.levels, self.coef,
                              self.T, self.single_in, self.static["single"], self.rm, m.embed_residue_type[1].weight,
                              self.eb_in, m.embed_beta[0].weight, m.embed_beta[1].weight, self.sync, x0_out=self.x0_hat,
@@ -1000,6 +1059,7 @@ class ReverseDiffusion:
                                     step_inputs=(self.single_in, self.eb_in), raw_noise=True, defer_seq_head=True)
         if self._seq_pred_buf is None:
             self._seq_pred_buf = torch.empty(*self.seq_t.shape, device=self.seq_t.device, dtype=torch.float32)
+        eps_raw = self._guide(eps_raw)
         ops.step_boundary_(self.z, self.seq_t, self.t, eps_raw, self._seq_pred_buf, self.noise, self.mask, m._coef, self.T,
                            self.single_in, self.static["single"], self.rm, m.embed_residue_type[1].weight,
                            self.eb_in, m.embed_beta[0].weight, m.embed_beta[1].weight, self.sync,

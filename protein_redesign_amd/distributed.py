@@ -58,14 +58,15 @@ def gather_samples(pos: torch.Tensor, logits: torch.Tensor, num_samples: int,
 def sample_sharded(sampler: Callable[[Dict[str, torch.Tensor], Sequence[NoiseSource]], Tuple[torch.Tensor, torch.Tensor]],
                    complex_batch: Dict[str, torch.Tensor], num_samples: int, seed: int = 0, batch_size: int = 1,
                    group: Optional[dist.ProcessGroup] = None, redesign=None, scaffold=None,
-                   sequence_rules=None, solver=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                   sequence_rules=None, solver=None, guidance=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Draw ``num_samples`` samples of ONE complex (a batch dict with leading dim 1).
 
     ``sampler(batch, sources) -> (pos [b,N,3], logits [b,N,21])`` is ``ProteinReDiffModel.sample`` on a
     GPU rank (tests inject a CPU stand-in).  Works without an initialised process group (world size 1).
     ``redesign`` (masking.Redesign), when given, is passed to the sampler unchanged as ``redesign=``: the spec is deterministic, so
     every rank redesigns the same residues.  ``scaffold`` (conditioning.Scaffold), when given, likewise as ``scaffold=``, and
-    ``sequence_rules`` (sequence.SequenceRules) as ``sequence_rules=``, and ``solver`` (solver.Solver) as ``solver=``.  Returns all samples, ordered by global index, on every rank."""
+    ``sequence_rules`` (sequence.SequenceRules) as ``sequence_rules=``, and ``solver`` (solver.Solver) as ``solver=``, and
+    ``guidance`` (guidance.Guidance) as ``guidance=``.  Returns all samples, ordered by global index, on every rank."""
     distributed = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if distributed else 1
     rank = dist.get_rank(group) if distributed else 0
@@ -82,6 +83,8 @@ def sample_sharded(sampler: Callable[[Dict[str, torch.Tensor], Sequence[NoiseSou
             kw["sequence_rules"] = sequence_rules
         if solver is not None:
             kw["solver"] = solver
+        if guidance is not None:
+            kw["guidance"] = guidance
         pos, logits = sampler(repeat_batch(clone_batch(complex_batch), len(idx)), sources, **kw)
         pos_l.append(pos)
         log_l.append(logits)

@@ -550,9 +550,9 @@ def _references(model, data, redesign, align_to, correspondence, assess, scaffol
 
 
 def _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device, scaffold=None, sequence_rules=None, keep_logits=False,
-          solver=None):
-    """Stage (b): the sampling loop, with no synchronisation beyond its copies to the host; ``scaffold``, ``sequence_rules`` and
-    ``solver`` reach ``model.sample`` only when given.  Returns (positions per batch -- left on the
+          solver=None, guidance=None):
+    """Stage (b): the sampling loop, with no synchronisation beyond its copies to the host; ``scaffold``, ``sequence_rules``,
+    ``solver`` and ``guidance`` reach ``model.sample`` only when given.  Returns (positions per batch -- left on the
     device if ``keep_on_device``, for the stages that score them there --, logits per batch on the host -- on the device if
     ``keep_logits``, for the decoding there --, the first prepared batch, the keyed noise source of every sample as sample() left it)."""
     from .synthetic import NoiseSource, batch_to
@@ -562,6 +562,8 @@ def _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_devi
         cond["sequence_rules"] = sequence_rules
     if solver is not None:
         cond["solver"] = solver
+    if guidance is not None:
+        cond["guidance"] = guidance
     for start in range(0, num_samples, batch_size):
         idx = list(range(start, min(start + batch_size, num_samples)))
         batch = collate_fn([data] * len(idx))
@@ -677,7 +679,24 @@ def _decode(data, positions, logits, na, nr, tokens=None):
     return proteins, ligands
 
 
-def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffold=None, sequences=None):
+def _guidance_report(guidance, data, pos, first_batch, na, nr):
+    """Stage (c'), ``guidance=``: the spec's terms, the clash and restraint energy [S,2] of the samples as model.sample returned them
+    (``guidance.energy``: one launch, distances only) and, when the input has coordinates, the same energy of the input structure --
+    what an unguided evaluation of it gives.  Returns the dict of numpy values."""
+    from . import guidance as GD
+    out = guidance.describe()
+    one = {k: (v[:1] if torch.is_tensor(v) else v) for k, v in first_batch.items()}     # every sample is the same complex
+    out["energy"] = GD.energy(pos.float(), one, guidance).cpu().numpy()
+    if _ca_trace_problem(data) is None and (na == 0 or "atom_pos" in data):
+        given = torch.zeros(1, pos.shape[1], 3)
+        given[0, na: na + nr] = torch.as_tensor(data["residue_atom_pos"], dtype=torch.float32)[:, 1]
+        if na > 0:
+            given[0, :na] = torch.as_tensor(data["atom_pos"], dtype=torch.float32)
+        out["input_energy"] = GD.energy(given.to(pos.device), one, guidance).cpu().numpy()[0]
+    return out
+
+
+def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffold=None, sequences=None, guided=None):
     """Stage (f): the files of ``output_dir``"""
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
@@ -701,6 +720,8 @@ def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffol
     if scaffold is not None:
         np.savez(out / "sample_scaffold.npz", keep=scaffold["keep"], ligand=scaffold["ligand"], sequence=scaffold["sequence"],
                  start=-1 if scaffold["start"] is None else scaffold["start"])
+    if guided is not None:
+        np.savez(out / "sample_guidance.npz", **guided)
     if sequences is not None:
         np.savez(out / "sample_sequences.npz", **{k: (np.array(v) if k == "sequences" else v) for k, v in sequences.items()})
         with open(out / "sample_sequences.fasta", "w") as f:
@@ -712,7 +733,8 @@ def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffol
 @torch.inference_mode()
 def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_size: int = 1, seed: int = 0,
                      output_dir: Optional[Union[str, Path]] = None, redesign=None, align_to=None, mirror: bool = True,
-                     correspondence: str = "index", assess=None, scaffold=None, sequence_rules=None, decode=None, solver=None):
+                     correspondence: str = "index", assess=None, scaffold=None, sequence_rules=None, decode=None, solver=None,
+                     guidance=None):
     """Draw ``num_samples`` samples of one featurised complex ``data`` (the dict of ligand_to_data ∪ protein_to_data).
 
     Returns (positions [S,N,3] in Angstrom, logits [S,N,21], proteins, ligand_positions).  With ``output_dir`` the CA
@@ -798,7 +820,20 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     ``solver`` (solver.Solver, keyword only, default None: nothing changes): the levels the loop visits and the update between them --
     ``Solver.ddim(50)``, ``Solver.ancestral(100)``, explicit ``timesteps`` -- handed to ``model.sample`` unchanged
     (``diffusion_model.ReverseDiffusion``): K network evaluations per sample instead of ``num_steps``.  Refused, before the model is
-    touched, if it is no ``Solver``.  The return value gains no element and ``output_dir`` no file for it."""
+    touched, if it is no ``Solver``.  The return value gains no element and ``output_dir`` no file for it.
+
+    ``guidance`` (guidance.Guidance, keyword only, default None: nothing below happens, every return value and file is what it was):
+    distance restraints between rows of the complex and clash repulsion, evaluated on every step's clean-structure estimate and added to
+    the predicted noise (``diffusion_model.ReverseDiffusion``).  Refused, before the model is touched, if it is no ``Guidance`` or a
+    restraint names a row outside the complex's ``num_atoms + num_residues``.  The return value gains one more trailing ``dict``, after
+    all of the above: the spec's terms (``restraints`` [R,2], ``restraint_bounds`` [R,3] = lo, hi, weight in Angstrom, ``clash`` = the
+    three floors and the weight, ``scale``, ``cap``, ``from_level`` (-1 for None), ``schedule``), ``energy`` [S,2] -- the clash and the
+    restraint energy of the samples as the model returned them, from ``guidance.energy`` -- and, when the input has coordinates,
+    ``input_energy`` [2], the same of the input structure.  ``output_dir`` also receives ``sample_guidance.npz`` (the dict)."""
+    if guidance is not None:
+        from .guidance import check_guidance
+        check_guidance(guidance)
+        guidance.check_rows(int(data["num_atoms"]) + int(data["num_residues"]), "the complex's num_atoms + num_residues rows")
     if solver is not None:
         from .solver import Solver
         if not isinstance(solver, Solver):
@@ -813,10 +848,10 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     if spec is not None:
         spec = spec.to(device)                  # a positions mask is uploaded once, not per batch
     na, nr = int(data["num_atoms"]), int(data["num_residues"])
-    scored = align_to is not None or assess is not None         # then the samples stay on the device until they are scored
+    scored = align_to is not None or assess is not None or guidance is not None     # then the samples stay on the device until they are scored
     drawn, logits, first_batch, sources = _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device=scored,
                                                 scaffold=scaffold, sequence_rules=sequence_rules, keep_logits=decode is not None,
-                                                solver=solver)
+                                                solver=solver, guidance=guidance)
     # every sample of the complex shares the mask: read from the first prepared batch, after the loop (no synchronisation inside it)
     used_mask = first_batch["residue_inv_extra_mask"][0].cpu().numpy() if spec is not None and first_batch is not None else None
     kept = None
@@ -826,6 +861,7 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
                 "start": scaffold.start}
     pos = torch.cat(drawn)
     quality = _assess(pos, first_batch, quality_ref, na, nr) if assess is not None else None
+    guided = _guidance_report(guidance, data, pos, first_batch, na, nr) if guidance is not None else None
     pos, alignment = _superpose(pos, data, struct_ref, align_ref, mirror, na, nr) if align_to is not None else (pos, None)
     sequences = None
     if decode is not None:
@@ -839,7 +875,8 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         alignment = {k: float(v.cpu()) if k == "diversity" else v.cpu().numpy() for k, v in alignment.items()}
     proteins, ligands = _decode(data, positions, logits, na, nr, sequences["tokens"] if sequences is not None else None)
     if output_dir is not None:
-        _write(output_dir, proteins, ligands, used_mask, alignment, quality, kept, sequences)
+        _write(output_dir, proteins, ligands, used_mask, alignment, quality, kept, sequences, guided)
     result = (positions, logits, proteins, ligands) + ((used_mask,) if spec is not None else ())
     result = result + ((alignment,) if alignment is not None else ()) + ((quality,) if quality is not None else ())
-    return result + ((kept,) if kept is not None else ()) + ((sequences,) if sequences is not None else ())
+    result = result + ((kept,) if kept is not None else ()) + ((sequences,) if sequences is not None else ())
+    return result + ((guided,) if guided is not None else ())

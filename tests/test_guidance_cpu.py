@@ -1,0 +1,428 @@
+"""CPU: guided sampling as far as it goes without a GPU -- the header / build of libprd_guide.so and its host refusals, the ``Restraint``
+and ``Guidance`` specs, their tables against a direct float64 computation, the restraint lists, the restatement of the launch against
+float64 autograd of its own energy and its invariances, every host refusal of the loop, and the ``guidance=`` keyword through
+pipeline.generate_samples and distributed.sample_sharded."""
+import ctypes
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import guidance_ref as GR
+import solver_ref as R
+from conftest import ROOT
+from protein_redesign_amd import _lib, build
+from protein_redesign_amd import guidance as GD
+from protein_redesign_amd import pipeline as PL
+from protein_redesign_amd.constants import make_args
+from protein_redesign_amd.guidance import Guidance, Restraint
+from protein_redesign_amd.solver import Solver
+from protein_redesign_amd.synthetic import NoiseSource, synthetic_batch
+from sample_stubs import _NoDevice, _Stub, header_entries
+from test_binding_cpu import Recorder, exported
+from test_conditioning_cpu import _generate
+from test_generate_samples_combinations_cpu import NA, NR
+
+HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
+SOURCE = os.path.join(ROOT, "protein_redesign_amd", "csrc", "guide", "prd_guide.hip")
+
+
+# ---- header, build, host refusals of the library ----------------------------------------------------------------------------------------
+
+def test_header_parses_with_the_derived_binding():
+    e = header_entries("guide")
+    assert sorted(e) == ["prd_guide_eps", "prd_guide_version"]
+    assert all(x.inject is None and x.restype is _lib.ci for x in e.values())
+    assert e["prd_guide_eps"].argtypes == [_lib.vp] * 14 + [_lib.ci] * 4 + [_lib.vp] and e["prd_guide_version"].argtypes == []
+    assert GD.ENTRIES == e and not set(e) & set(_lib.ENTRIES)
+    D = GD._DEFINES
+    assert GD.ABI_VERSION == D["VERSION"] == 100 and (D["ERR_ARG"], D["ERR_ALIGN"], D["ERR_UNSUPPORTED"]) == (-1, -2, -3)
+    assert D["MAX_B"] == 4096 and D["MAX_N"] == GD.MAX_N == 8192 and D["MAX_R"] == GD.MAX_R >= 2 * 8192 and D["TABLE_STRIDE"] == 4
+    with open(SOURCE) as f:
+        text = f.read()
+    assert '#include "../prd_launch.h"' in text and "hipLaunchKernelGGL" not in text and "<<<" not in text and "asm" not in text
+    assert "atomic" not in text and "getenv" not in text and "hipMalloc" not in text
+    assert text.count("prd_launch<") == 1                       # one kernel per call
+
+
+def test_one_compile_one_link_and_neither_a_side_nor_a_loop_library(monkeypatch):
+    assert "guide" not in build.SIDE_LIBS and "guide" not in build.LOOP_LIBS and list(build.STEP_LIBS) == ["guide"]
+    s = build.STEP_LIBS["guide"]
+    assert s.sources == [os.path.join("guide", "prd_guide.hip")] == build.GUIDE_SOURCES and s.flag == "--guide"
+    assert s.lib == build.LIB_GUIDE == os.path.join(ROOT, "protein_redesign_amd", "libprd_guide.so")
+    assert s.headers == [os.path.join(ROOT, "include", "prd_guide.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
+    assert build._headers(s.sources[0]) == s.headers
+    monkeypatch.delenv("HIPCC", raising=False)
+    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
+    rec = Recorder(execute=False)
+    rec.install(monkeypatch)
+    build.build_condition(verbose=False)
+    condition_cmds, rec.cmds = rec.cmds, []
+    build.build_guide(verbose=False)
+    src, obj = "{ROOT}/protein_redesign_amd/csrc/guide/prd_guide.hip", "{ROOT}/protein_redesign_amd/csrc/guide/prd_guide.o"
+    assert len(rec.cmds) == 2 and rec.cmds[0][-4:] == ["-c", src, "-o", obj] and "-ffp-contract=off" in rec.cmds[0]
+    assert rec.cmds[1] == rec.cmds[0][:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_guide.so", obj]
+    # the same flags and routine as a side library's: only source, object and library differ
+    swap = lambda t: t.replace("csrc/prd_condition", "csrc/guide/prd_guide").replace("condition", "guide")      # noqa: E731
+    assert rec.cmds == [[swap(t) for t in c] for c in condition_cmds]
+    # the other builds compile none of it
+    rec.cmds = []
+    build.build(verbose=False)
+    for name in list(build.SIDE_LIBS) + list(build.LOOP_LIBS):
+        build.build_side(name, verbose=False)
+    assert rec.cmds and not any("guide" in t for c in rec.cmds for t in c)
+
+
+@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
+def test_forced_cross_compile_exports_the_header_and_a_second_build_is_incremental(monkeypatch):
+    lib = build.build_guide(force=True, verbose=False)
+    assert lib == build.LIB_GUIDE and os.path.exists(lib)
+    assert exported(lib) == set(header_entries("guide"))
+    rec = Recorder(execute=True)
+    rec.install(monkeypatch)
+    assert build.build_guide(verbose=False) == lib
+    assert rec.cmds == []
+
+
+@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
+def test_resources_of_the_one_kernel():
+    mine = build.resource_usage(sources=build.GUIDE_SOURCES)
+    assert sorted(mine) == ["guide_eps_kernel"]
+    u = mine["guide_eps_kernel"]
+    assert u["scratch"] == 0 and u["agprs"] == 0 and u["vgprs"] <= 64 and 4096 <= u["lds"] <= 4096 + 256     # the tile and two small arrays
+    assert not set(mine) & set(build.resource_usage())
+
+
+@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
+def test_the_library_refuses_on_the_host_before_any_device_call():
+    """every refusal of prd_guide.h is host code that runs before the first HIP call: reachable without a GPU, with pointers that are
+    never followed"""
+    build.build_guide(verbose=False)
+    L, D = GD.lib(), GD._DEFINES
+    assert L.prd_guide_version() == 100
+    p, far = ctypes.c_void_p(1 << 20), ctypes.c_void_p(1 << 30)
+    names = ["z", "eps_raw", "eps_out", "mask", "counter", "table", "cls", "floors", "wclash", "exclude", "rs_ptr", "rs_j", "rs_par", "e_out"]
+
+    def call(b=2, N=5, rows=16, R=6, **ptrs):
+        args = [ptrs.get(n, far if n == "eps_out" else p) for n in names]
+        return L.prd_guide_eps(*args, b, N, rows, R, None)
+    for n in ("z", "eps_raw", "eps_out", "mask", "table", "cls", "floors", "wclash"):
+        assert call(**{n: None}) == D["ERR_ARG"], n
+    for kw in (dict(b=0), dict(N=0), dict(rows=0), dict(b=-1), dict(N=-3), dict(R=0), dict(R=-2), dict(rs_ptr=None), dict(rs_j=None),
+               dict(rs_par=None), dict(rs_ptr=None, rs_j=None), dict(eps_out=p), dict(eps_out=ctypes.c_void_p((1 << 20) + 2 * 5 * 12 - 4)),
+               dict(eps_out=ctypes.c_void_p((1 << 20) - 2 * 5 * 12 + 4))):
+        assert call(**kw) == D["ERR_ARG"], kw
+    for kw in (dict(b=D["MAX_B"] + 1), dict(N=D["MAX_N"] + 1), dict(rows=D["MAX_ROWS"] + 1), dict(R=D["MAX_R"] + 1)):
+        assert call(**kw) == D["ERR_UNSUPPORTED"], kw
+    for kw in (dict(table=ctypes.c_void_p((1 << 20) + 4)), dict(rs_par=ctypes.c_void_p((1 << 20) + 8))):
+        assert call(**kw) == D["ERR_ALIGN"], kw
+    # the launch geometry the bounds promise: the grid and every int index of the kernel stay below 2^31
+    assert D["MAX_B"] * (D["MAX_N"] // 64 + 1) < 2 ** 31 and D["MAX_B"] * (D["MAX_N"] + 1) < 2 ** 31 and D["MAX_N"] * 3 < 2 ** 31
+
+
+# ---- the specs ------------------------------------------------------------------------------------------------------------------------
+
+def test_restraint_is_validated_and_immutable():
+    r = Restraint(3, 9, hi=6)
+    assert (r.i, r.j, r.lo, r.hi, r.weight) == (3, 9, None, 6.0, 1.0) and isinstance(r.hi, float)
+    assert Restraint(np.int64(2), torch.tensor(4).item(), lo=1.5).j == 4
+    with pytest.raises(Exception):
+        r.hi = 2.0
+    for kw, what in ((dict(i=-1, j=2, hi=1), "i must"), (dict(i=1, j=1.5, hi=1), "j must"), (dict(i=True, j=2, hi=1), "i must"),
+                     (dict(i=2, j=2, hi=1), "must differ"), (dict(i=0, j=1), "lo, hi or both"), (dict(i=0, j=1, lo=3, hi=2), "must not exceed"),
+                     (dict(i=0, j=1, lo=-1), "lo must"), (dict(i=0, j=1, hi=float("inf")), "hi must"), (dict(i=0, j=1, hi=2, weight=0), "weight"),
+                     (dict(i=0, j=1, hi=2, weight=float("nan")), "weight")):
+        with pytest.raises(ValueError, match=what):
+            Restraint(**kw)
+
+
+def test_guidance_is_validated_converted_once_and_knows_when_it_is_inert():
+    g = Guidance()
+    assert g.clash == dict(rr=3.0, rl=2.5, ll=2.0, weight=1.0) and g.restraints == () and not g.inert
+    assert (g.scale, g.cap, g.from_level, g.schedule) == (1.0, 0.5, None, "sigma")
+    assert g.floors_nm == (3.0 * 0.1, 2.5 * 0.1, 2.0 * 0.1) and g.clash_weights == (1.0, 1.0, 1.0)
+    h = Guidance(restraints=[Restraint(0, 1, lo=2, hi=4, weight=3)], clash=dict(rl=4.0, weight=2.0), scale=2, cap=1, from_level=5, schedule="constant")
+    assert h.clash == dict(rr=3.0, rl=4.0, ll=2.0, weight=2.0) and h.floors_nm[1] == 4.0 * 0.1 and h.clash_weights == (2.0,) * 3
+    assert isinstance(h.restraints, tuple) and Guidance(restraints=Restraint(0, 1, hi=1)).restraints[0].hi == 1.0
+    with pytest.raises(Exception):
+        g.scale = 2.0
+    # inert: no term at all, or no strength
+    assert Guidance(clash=False).inert and Guidance(clash=dict(weight=0)).inert and Guidance(clash=dict(rr=0, rl=0, ll=0)).inert
+    assert Guidance(scale=0).inert and Guidance(restraints=[Restraint(0, 1, hi=1)], scale=0.0).inert
+    assert not Guidance(restraints=[Restraint(0, 1, hi=1)], clash=False).inert
+    assert Guidance(clash=False).floors_nm == (0.0, 0.0, 0.0) and Guidance(clash=False).clash_weights == (0.0, 0.0, 0.0)
+    for kw, what in ((dict(clash="yes"), "clash must"), (dict(clash=dict(rx=1.0)), "clash takes"), (dict(clash=dict(rr=-1)), r"clash\['rr'\]"),
+                     (dict(scale=-1), "scale"), (dict(scale=float("nan")), "scale"), (dict(cap=0), "cap"), (dict(cap=-0.1), "cap"),
+                     (dict(schedule="linear"), "schedule"), (dict(from_level=-1), "from_level"), (dict(from_level=1.5), "from_level"),
+                     (dict(from_level=True), "from_level"), (dict(restraints=[(0, 1)]), "sequence of guidance.Restraint")):
+        with pytest.raises(ValueError, match=what):
+            Guidance(**kw)
+    # the unit conversion happens once: the lists hold nanometres, an open side is 0 / inf
+    ptr, js, par = h.csr({"atom_mask": torch.zeros(1, 3)})
+    assert par.dtype == torch.float32 and par.tolist() == [[np.float32(0.2).item(), np.float32(0.4).item(), 3.0, 0.0]] * 2
+    _, _, par = Guidance(restraints=[Restraint(0, 1, hi=5), Restraint(1, 2, lo=5)], clash=False).csr({"atom_mask": torch.zeros(1, 3)})
+    assert par[0].tolist() == [0.0, 0.5, 1.0, 0.0] and par[1].tolist() == [0.0, 0.5, 1.0, 0.0] and par[2].tolist() == [0.5, math.inf, 1.0, 0.0]
+    assert "1 restraints" in repr(h) and "hi=6.0" in repr(Restraint(3, 9, hi=6))
+
+
+@pytest.mark.parametrize("kind", ["linear", "cosine"])
+def test_tables_against_a_direct_float64_computation(kind):
+    ab = R.abar(16, kind)
+    g = Guidance(scale=0.7, cap=0.25, from_level=9)
+    tab = g.tables(16, kind)
+    assert tab.shape == (16, 4) and tab.dtype == torch.float32 and tab.is_contiguous()
+    for t in range(16):
+        q, r = 1.0 / math.sqrt(ab[t]), math.sqrt(1.0 - ab[t])
+        want = torch.tensor([q, r, 0.7 * q * r if t <= 9 else 0.0, 0.25], dtype=torch.float64).float()
+        assert torch.equal(tab[t], want), (t, tab[t], want)     # float64, rounded once
+    assert float(tab[10:, 2].abs().max()) == 0.0 and bool((tab[:10, 2] > 0).all())
+    const = Guidance(scale=0.7, schedule="constant").tables(16, kind)
+    assert torch.equal(const[:, 2], torch.full((16,), 0.7)) and torch.equal(const[:, :2], tab[:, :2])
+    # under a solver: the rows of the visited levels, picked
+    lv = Solver.ddim(5).levels(16)
+    assert lv == [0, 4, 8, 11, 15] and torch.equal(g.tables(16, kind, lv), tab[lv]) and torch.equal(GR.guide_table(g, lv, kind), tab[lv])
+    # q and r are the solver's own columns: the estimate the kernel evaluates is the boundary's
+    assert torch.equal(g.tables(16, kind, lv)[:, :2], Solver.ddim(5).tables(16, kind)[1][:, [4, 3]])
+
+
+def test_csr_lists_every_restraint_under_both_ends_in_a_deterministic_order():
+    rs = [Restraint(4, 1, hi=3), Restraint(1, 2, lo=1, weight=2), Restraint(4, 2, lo=1, hi=2), Restraint(1, 4, hi=9)]
+    g = Guidance(restraints=rs, clash=False)
+    ptr, js, par = g.csr({"atom_mask": torch.zeros(2, 6)})
+    assert ptr.dtype == js.dtype == torch.int32 and ptr.shape == (2, 7) and js.shape == (8,) and par.shape == (8, 4)
+    assert ptr[0].tolist() == ptr[1].tolist() == [0, 0, 3, 5, 5, 8, 8]          # rows 0, 3 and 5 are empty
+    assert js.tolist() == [4, 2, 4, 1, 4, 1, 2, 1]                              # a row's entries in the order of ``restraints``
+    assert par[:, 2].tolist() == [1, 2, 1, 2, 1, 1, 1, 1] and par[0].tolist() == par[5].tolist() and par[2].tolist() == par[7].tolist()
+    again = Guidance(restraints=rs, clash=False).csr({"atom_mask": torch.zeros(2, 6)})
+    assert all(torch.equal(a, b) for a, b in zip((ptr, js, par), again))
+    assert Guidance().csr({"atom_mask": torch.zeros(2, 6)}) is None
+    with pytest.raises(ValueError, match=r"outside the batch's rows \[0, 4\)"):
+        g.csr({"atom_mask": torch.zeros(1, 4)})
+
+
+def test_chain_and_bond_helpers_follow_the_rows_quality_counts():
+    batch = synthetic_batch([(8, 40)], esm_dim=16, seed=0)
+    ch = GD.chain(batch)
+    assert len(ch) == 38 and all(r.j == r.i + 1 and (r.lo, r.hi) == (3.8 - 0.5, 3.8 + 0.5) for r in ch)        # two chains of 20
+    assert {r.i for r in ch} == set(range(8, 47)) - {8 + 19} and GD.chain(batch, tol=0.1)[0].hi == 3.8 + 0.1
+    bd = batch["bond_distance"][0]
+    bo = GD.bonds(batch)
+    assert len(bo) == int((bd[:8, :8] == 1).triu(1).sum()) and all(r.i < r.j < 8 and (r.lo, r.hi) == (0.9, 2.1) for r in bo)
+
+
+# ---- the restatement ------------------------------------------------------------------------------------------------------------------
+
+def _case(N=37, seed=3):
+    c = GR.kernel_case(N, seed)
+    return c, GR.table16()
+
+
+def test_restated_gradient_is_the_float64_autograd_of_its_own_energy():
+    """pins the sign and the factor of a half: g = dE/dx with E the sum of the rows' shares"""
+    c, _ = _case()
+    for s in range(3):
+        x = (c["z"][s].double() * 1.0).requires_grad_(True)
+        args = (c["mask"][s].double(), c["cls"][s], c["floors"].double(), c["wclash"].double(), c["exclude"][s],
+                (c["csr"][0][s], c["csr"][1], c["csr"][2].double()))
+        e, g = GD.restate_rows(x, *args)
+        total = e.sum()
+        (auto,) = torch.autograd.grad(total, x)
+        assert float(e.detach()[:, 0].sum()) > 0 and float(e.detach()[:, 1].sum()) > 0
+        assert GR.rel(g.detach(), auto) <= 1e-10, GR.rel(g.detach(), auto)
+        # the energy itself, pair by pair
+        xs, E = x.detach(), 0.0
+        cl = torch.where(c["mask"][s] > 0.5, c["cls"][s], torch.zeros_like(c["cls"][s])).tolist()
+        for i in range(len(cl)):
+            for j in range(i + 1, len(cl)):
+                if cl[i] and cl[j] and not c["exclude"][s, i, j]:
+                    k = cl[i] + cl[j] - 2
+                    E += float(c["wclash"][k]) / 2 * max(0.0, float(c["floors"][k]) - float((xs[i] - xs[j]).norm())) ** 2
+        assert abs(float(e.detach()[:, 0].sum()) - E) <= 1e-12 * max(E, 1.0)
+
+
+def test_lam_zero_is_the_identity_and_dead_counters_are_left_alone():
+    c, tab = _case()
+    tab = tab.clone()
+    tab[5, 2] = 0.0
+    c["eps_raw"][0, 0, 0] = -0.0
+    out = GD.restate_guide(c["z"], c["eps_raw"], c["mask"], torch.tensor([5, -1, 16]), tab, c["cls"], c["floors"], c["wclash"], c["exclude"],
+                           c["csr"], dtype=torch.float32)
+    assert out["live"].tolist() == [True, False, False]
+    assert torch.equal(out["eps_out"][0], c["eps_raw"][0]) and math.copysign(1.0, float(out["eps_out"][0, 0, 0])) == -1.0
+    assert float(out["e_out"][0].sum()) > 0 and float(out["e_out"][1:].abs().sum()) == 0.0
+    on = GR.restate(c, [4, 4, 4], GR.table16())
+    assert bool(((on["eps_out"] - c["eps_raw"].double()).abs().amax(-1) > 0)[c["mask"] > 0.5].float().mean() > 0.5)
+
+
+def test_the_cap_is_continuous_where_it_starts_to_bind():
+    c, tab = _case()
+    base = GR.restate(c, [4, 4, 4], tab)
+    d = (tab[4, 2].double() * base["g"]).norm(dim=-1)
+    row = int(torch.argmax(d[0]))
+    at = float(d[0, row])
+    outs = []
+    for cap in (at * (1 + 1e-9), at, at * (1 - 1e-9)):
+        t = tab.double().clone()
+        t[4, 3] = cap
+        outs.append(GD.restate_guide(c["z"], c["eps_raw"], c["mask"], torch.tensor([4, 4, 4]), t, c["cls"], c["floors"], c["wclash"],
+                                     c["exclude"], c["csr"])["eps_out"][0, row])
+    assert float((outs[0] - outs[1]).abs().max()) <= 1e-12 and float((outs[1] - outs[2]).abs().max()) <= 1e-8 * at
+    # and it binds: with a small cap no row moves by more than it
+    t = tab.double().clone()
+    t[4, 3] = at / 10
+    moved = (GD.restate_guide(c["z"], c["eps_raw"], c["mask"], torch.tensor([4, 4, 4]), t, c["cls"], c["floors"], c["wclash"], c["exclude"],
+                              c["csr"])["eps_out"] - c["eps_raw"].double()).norm(dim=-1)
+    assert float(moved.max()) <= at / 10 * (1 + 1e-12) and int((moved > at / 10 * (1 - 1e-9)).sum()) >= 1
+
+
+def test_a_coincident_pair_contributes_nothing_and_stays_finite():
+    c, tab = _case(N=9)
+    plain = GR.restate(c, [0, 0, 0], tab)           # counter 0: q = 1 up to rounding, r small
+    c["z"][:, 1], c["eps_raw"][:, 1], c["mask"][:, :2], c["cls"][:, :2] = c["z"][:, 0], c["eps_raw"][:, 0], 1.0, 1
+    c["exclude"][:, 0, 1] = c["exclude"][:, 1, 0] = 0
+    out = GR.restate(c, [0, 0, 0], tab)
+    assert bool(torch.isfinite(out["eps_out"]).all()) and bool(torch.isfinite(out["e_out"]).all())
+    assert float((out["x"][:, 0] - out["x"][:, 1]).abs().max()) == 0.0
+    far = GD.restate_guide(c["z"] + torch.tensor([0.0, 0.0, 50.0]) * torch.eye(9)[1][None, :, None], c["eps_raw"], c["mask"],
+                           torch.tensor([0, 0, 0]), tab, c["cls"], c["floors"], c["wclash"], c["exclude"], None)
+    nolist = GD.restate_guide(c["z"], c["eps_raw"], c["mask"], torch.tensor([0, 0, 0]), tab, c["cls"], c["floors"], c["wclash"],
+                              c["exclude"], None)
+    # row 0 feels nothing from its twin: what it feels is what it feels with the twin moved out of every floor
+    assert float((nolist["g"][:, 0] - far["g"][:, 0]).abs().max()) <= 1e-12 and plain["live"].all()
+
+
+def test_energy_is_invariant_and_forces_are_covariant_under_rotation_and_reflection():
+    c, tab = _case()
+    g = torch.Generator().manual_seed(1)
+    Q, _ = torch.linalg.qr(torch.randn(3, 3, generator=g, dtype=torch.float64))
+    for M in (Q, Q @ torch.diag(torch.tensor([1.0, 1.0, -1.0], dtype=torch.float64))):
+        assert abs(abs(float(torch.det(M))) - 1.0) <= 1e-12
+        a = GR.restate(c, [3, 7, 12], tab)
+        moved = dict(c, z=(c["z"].double() @ M), eps_raw=(c["eps_raw"].double() @ M))
+        b = GR.restate(moved, [3, 7, 12], tab)
+        assert float((a["e_out"] - b["e_out"]).abs().max()) <= 1e-12 * float(a["e_out"].abs().max())
+        want = (a["eps_out"] - c["eps_raw"].double()) @ M
+        assert GR.rel(b["eps_out"] - moved["eps_raw"], want) <= 1e-10
+
+
+# ---- the refusals of the loop, all on the host ------------------------------------------------------------------------------------------
+
+def test_the_model_refuses_guidance_it_cannot_serve(monkeypatch):
+    """decided before any device work or library call"""
+    from protein_redesign_amd.diffusion_model import ProteinReDiffModel, ReverseDiffusion
+    model = ProteinReDiffModel(make_args(single_dim=128, pair_dim=64, num_blocks=1, esm_dim=64, num_steps=4))
+    spec = Guidance(restraints=[Restraint(0, 5, hi=4)])
+    assert model._guidance_spec(None) is None and model._guidance_spec(spec) is spec and not hasattr(model, "guidance")
+    with pytest.raises(TypeError, match="Guidance"):
+        model._guidance_spec("clash")
+    with pytest.raises(TypeError, match="Guidance"):
+        model.sample({}, sources=[], guidance=dict(clash=True))
+    monkeypatch.setenv("PRD_FUSED_BOUNDARY", "0")
+    with pytest.raises(ValueError, match=r"PRD_FUSED_BOUNDARY=0.*time_dim above 512"):
+        model.sample({}, sources=[], guidance=spec)
+    assert model._guidance_spec(spec, Solver.ddim(2)) is spec           # a solver's boundary has no un-fused form
+    monkeypatch.delenv("PRD_FUSED_BOUNDARY")
+    wide = ProteinReDiffModel(make_args(single_dim=128, pair_dim=64, num_blocks=1, esm_dim=64, num_steps=4, time_dim=1024))
+    with pytest.raises(ValueError, match=r"PRD_FUSED_BOUNDARY=0.*time_dim above 512.*time_dim = 1024"):
+        wide.sample({}, sources=[], guidance=spec)
+    with pytest.raises(ValueError, match="solver"):                     # ... and with one the solver's own refusal of that width
+        wide.sample({}, sources=[], guidance=spec, solver=Solver.ddim(2))
+    # a restraint outside the rows: the library's, then the batch's (the loop knows N before it touches the device)
+    with pytest.raises(ValueError, match=r"outside the library's rows \[0, 8192\)"):
+        model.sample({}, sources=[], guidance=Guidance(restraints=[Restraint(0, 8192, hi=4)]))
+    batch = synthetic_batch([(4, 6)], esm_dim=64, seed=0)
+    with pytest.raises(ValueError, match=r"outside the batch's rows \[0, 10\)"):
+        ReverseDiffusion(_Spy(model), batch, [NoiseSource(0, 0)], guidance=Guidance(restraints=[Restraint(0, 10, hi=4)]))
+    monkeypatch.setattr(GD, "MAX_R", 4)
+    with pytest.raises(ValueError, match=r"3 restraints make 6 list entries, at most 4"):
+        model.sample({}, sources=[], guidance=Guidance(restraints=[Restraint(0, k, hi=4) for k in (1, 2, 3)]))
+    model.training_mode = True
+    with pytest.raises(ValueError, match="training_mode"):
+        model.sample({}, sources=[], guidance=spec)
+
+
+class _Spy:
+    """the model's spec checks and nothing else: any further use of the model fails"""
+
+    def __init__(self, model):
+        self._model = model
+
+    def __getattr__(self, name):
+        if name in ("_scaffold_spec", "_rules_spec", "_solver_spec", "_guidance_spec"):
+            return getattr(self._model, name)
+        raise AssertionError(f"the model was touched ({name}) before the restraints were checked")
+
+
+# ---- plumbing -------------------------------------------------------------------------------------------------------------------------
+
+class _GuidedStub(_Stub):
+    def __init__(self):
+        self.seen = []
+
+    def sample(self, batch, sources, redesign=None, guidance=None):
+        self.seen.append(guidance)
+        return super().sample(batch, sources, redesign=redesign)
+
+
+def _host_energy(x, batch, spec):
+    """guidance.energy restated on the host for the stub path (the real one is a launch)"""
+    t = spec.terms(batch)
+    S, N, _ = x.shape
+    grow = lambda v: v.expand(S, *v.shape[1:])     # noqa: E731
+    tab = torch.tensor([[1.0, 0.0, 0.0, spec.cap]])
+    csr = (grow(t["csr"][0]),) + t["csr"][1:] if t["csr"] is not None else None
+    out = GD.restate_guide(0.1 * x, torch.zeros_like(x), grow(batch["atom_mask"] + batch["residue_mask"]), None, tab, grow(t["cls"]), t["floors"],
+                           t["wclash"], grow(t["exclude"]), csr)
+    return out["e_out"].sum(1)
+
+
+def test_generate_samples_returns_the_trailing_dict_and_writes_the_file(tmp_path, monkeypatch):
+    monkeypatch.setattr(GD, "energy", _host_energy)
+    spec = Guidance(restraints=[Restraint(1, NA + 3, hi=6.0), Restraint(NA, NA + 8, lo=4.0, hi=30.0, weight=2.0)], scale=0.5, from_level=7)
+    model = _GuidedStub()
+    out = _generate(model, tmp_path / "with", guidance=spec)
+    assert len(out) == 5 and model.seen == [spec, spec] and all(s is spec for s in model.seen)
+    d = out[-1]
+    assert sorted(d) == ["cap", "clash", "energy", "from_level", "input_energy", "restraint_bounds", "restraints", "scale", "schedule"]
+    assert d["restraints"].tolist() == [[1, NA + 3], [NA, NA + 8]] and d["restraint_bounds"].tolist() == [[0.0, 6.0, 1.0], [4.0, 30.0, 2.0]]
+    assert d["clash"].tolist() == [3.0, 2.5, 2.0, 1.0] and (d["scale"], d["cap"], d["from_level"], d["schedule"]) == (0.5, 0.5, 7, "sigma")
+    assert d["energy"].shape == (3, 2) and d["energy"].dtype == np.float64 and d["input_energy"].shape == (2,)
+    assert np.isfinite(d["energy"]).all() and (d["energy"] >= 0).all() and d["energy"][:, 1].min() > 0      # random rows: the restraints are violated
+    assert sorted(os.listdir(tmp_path / "with")) == ["sample_guidance.npz", "sample_ligand_pos.npy", "sample_protein.pdb"]
+    with np.load(tmp_path / "with" / "sample_guidance.npz") as f:
+        assert sorted(f.files) == sorted(d) and np.array_equal(f["energy"], d["energy"]) and str(f["schedule"]) == "sigma"
+    # without the keyword the arity and the files are what they were, and the keyword does not reach the model
+    want = torch.stack([torch.randn(NA + NR, 3, generator=NoiseSource(1, k).g) for k in range(3)]).numpy()
+    for kw in ({}, dict(guidance=None)):
+        plain = _generate(_Stub(), tmp_path / "plain", **kw)
+        assert len(plain) == 4 and np.array_equal(plain[0], want) and np.array_equal(plain[0], out[0]) and np.array_equal(plain[1], out[1])
+    assert sorted(os.listdir(tmp_path / "plain")) == ["sample_ligand_pos.npy", "sample_protein.pdb"]
+    with pytest.raises(TypeError, match="guidance"):
+        _generate(_Stub(), tmp_path / "c", guidance=spec)
+    with pytest.raises(TypeError, match="guidance.Guidance"):
+        PL.generate_samples(_NoDevice(), {}, num_samples=2, guidance="clash")
+    with pytest.raises(ValueError, match=rf"outside the complex's num_atoms \+ num_residues rows \[0, {NA + NR}\)"):
+        PL.generate_samples(_NoDevice(), dict(num_atoms=NA, num_residues=NR), num_samples=2, guidance=Guidance(restraints=[Restraint(0, NA + NR, hi=3)]))
+
+
+def test_sample_sharded_and_predict_step_pass_the_keyword_only_when_given():
+    from protein_redesign_amd.distributed import sample_sharded
+    batch = synthetic_batch([(NA, NR)], esm_dim=16, seed=8)
+    seen = []
+
+    def sampler(bt, sources, **kw):
+        seen.append(kw)
+        n = bt["atom_mask"].shape[1]
+        return torch.zeros(len(sources), n, 3), torch.zeros(len(sources), n, 21)
+    spec = Guidance()
+    sample_sharded(sampler, batch, 2)
+    sample_sharded(sampler, batch, 2, guidance=spec)
+    sample_sharded(sampler, batch, 1, solver=Solver.ddim(3), guidance=spec)
+    assert seen[:2] == [{}, {}] and seen[2:4] == [{"guidance": spec}] * 2 and seen[2]["guidance"] is spec
+    assert sorted(seen[4]) == ["guidance", "solver"]
+    import inspect
+    from protein_redesign_amd.diffusion_model import ProteinReDiffModel, ReverseDiffusion
+    for fn in (ProteinReDiffModel.predict_step, ProteinReDiffModel.sample, ReverseDiffusion.__init__, PL.generate_samples, sample_sharded):
+        assert inspect.signature(fn).parameters["guidance"].default is None, fn
