@@ -61,11 +61,19 @@ LIB_SOLVER, SOLVER_SOURCES = LOOP_LIBS["solver"].lib, LOOP_LIBS["solver"].source
 STEP_LIBS = {"guide": SideLib([os.path.join("guide", "prd_guide.hip")], [os.path.join(_INCLUDE, "prd_guide.h"), PRD_LAUNCH_H],
                               os.path.join(HERE, "libprd_guide.so"), "--guide")}
 LIB_GUIDE, GUIDE_SOURCES = STEP_LIBS["guide"].lib, STEP_LIBS["guide"].sources
+# The sample libraries: once more the same SideLib tuples, flags and compile routine, for post-processing of samples that was added after
+# the side-library launch trace was recorded.  They are kept apart from SIDE_LIBS because that map is what the trace and its recorded
+# output walk, and from the two maps above because nothing here runs inside the sampling loop.
+#   chirality  libprd_chirality.so (include/prd_chirality.h): the handedness census of samples (chirality.py) -- C-alpha virtual
+#            dihedrals and the signed volumes of the ligand's stereocentres, a verdict per sample, the reflection of mirrored samples
+SAMPLE_LIBS = {"chirality": SideLib([os.path.join("chirality", "prd_chirality.hip")], [os.path.join(_INCLUDE, "prd_chirality.h"), PRD_LAUNCH_H],
+                                    os.path.join(HERE, "libprd_chirality.so"), "--chirality")}
+LIB_CHIRALITY, CHIRALITY_SOURCES = SAMPLE_LIBS["chirality"].lib, SAMPLE_LIBS["chirality"].sources
 
 
 def _own_libs():
-    """every library with a header of its own: the side libraries, then the loop libraries, then the step libraries"""
-    return list(SIDE_LIBS.items()) + list(LOOP_LIBS.items()) + list(STEP_LIBS.items())
+    """every library with a header of its own: the side libraries, then the loop libraries, the step libraries and the sample libraries"""
+    return list(SIDE_LIBS.items()) + list(LOOP_LIBS.items()) + list(STEP_LIBS.items()) + list(SAMPLE_LIBS.items())
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -230,7 +238,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
 
 def build_side(name: str, force: bool = False, verbose: bool = True, variant: str = "shipped") -> str:
-    """The side library ``name`` of SIDE_LIBS (or the loop library ``name`` of LOOP_LIBS, or the step library ``name`` of STEP_LIBS): its sources with the committed FLAGS and the shipped variant's extras, objects beside
+    """The side library ``name`` of SIDE_LIBS (or the loop library ``name`` of LOOP_LIBS, or the step library ``name`` of STEP_LIBS, or the sample library ``name`` of SAMPLE_LIBS): its sources with the committed FLAGS and the shipped variant's extras, objects beside
     the denoiser's.  Not a variant of libprd_hip.so: ``build()`` compiles none of it, and no side library compiles another.
     ``variant="trace"``: the trace variant's flags and object directory, the library libprd_<name>_trace.so."""
     s, v = dict(_own_libs())[name], VARIANTS[variant]
@@ -273,6 +281,11 @@ def build_guide(force: bool = False, verbose: bool = True) -> str:
     return build_side("guide", force, verbose)
 
 
+def build_chirality(force: bool = False, verbose: bool = True) -> str:
+    """libprd_chirality.so (include/prd_chirality.h, protein_redesign_amd/chirality.py)"""
+    return build_side("chirality", force, verbose)
+
+
 def build_asan(verbose: bool = True) -> str:
     """Host-side AddressSanitizer build: libprd_hip_asan.so with the HOST code of every source instrumented
     (-fsanitize=address; device code is compiled as usual: -fno-gpu-sanitize) and the argument-validation driver
@@ -282,6 +295,18 @@ def build_asan(verbose: bool = True) -> str:
     exe = os.path.join(VARIANTS["asan"].objdir, "host_abi_check")
     driver = os.path.join(os.path.dirname(HERE), "tests", "native", "host_abi_check.c")
     if _stale(exe, [driver, lib, PRD_HIP_H]):
+        _run([_hipcc(), "-x", "c", driver, "-x", "none", "-g"] + _ASAN + ["-o", exe, lib, "-Wl,-rpath," + HERE], verbose)
+    return exe
+
+
+def build_chirality_check(verbose: bool = True) -> str:
+    """Host-side AddressSanitizer build of libprd_chirality.so (the asan variant's flags: host code instrumented, device code as usual)
+    and the argument-validation driver tests/native/chirality_abi_check.c linked against it.  Runs on a machine without a GPU: every
+    call of the driver is refused before any HIP API is used.  Returns the path of the driver binary."""
+    lib = build_side("chirality", verbose=verbose, variant="asan")
+    exe = os.path.join(VARIANTS["asan"].objdir, "chirality_abi_check")
+    driver = os.path.join(os.path.dirname(HERE), "tests", "native", "chirality_abi_check.c")
+    if _stale(exe, [driver, lib, SAMPLE_LIBS["chirality"].headers[0]]):
         _run([_hipcc(), "-x", "c", driver, "-x", "none", "-g"] + _ASAN + ["-o", exe, lib, "-Wl,-rpath," + HERE], verbose)
     return exe
 

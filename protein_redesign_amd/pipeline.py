@@ -524,10 +524,15 @@ def check_sequence_options(data: Mapping[str, Any], sequence_rules, decode) -> N
                              "unknown (a protein without a sequence?)")
 
 
-def _references(model, data, redesign, align_to, correspondence, assess, scaffold=None, sequence_rules=None, decode=None):
+def _references(model, data, redesign, align_to, correspondence, assess, scaffold=None, sequence_rules=None, decode=None, handedness=None):
     """Stage (a) of generate_samples: every refusal that host data alone decides, in the order callers rely on, before ``model.device``
     is read; those of ``scaffold`` come after the references' and before the model's own design region is looked up.  Returns (structural reference or None, index-wise alignment reference or None, quality
     reference or None, redesign spec)."""
+    if handedness is not None:                  # the type first, then what it may not be combined with
+        from .chirality import Handedness
+        if Handedness.of(handedness).fix and scaffold is not None:
+            raise ValueError("handedness='fix' cannot be combined with a scaffold: the kept rows pin the frame and the hand of a sample, and a "
+                             "reflection would move them off the input; use handedness='report' with a scaffold")
     if correspondence not in ("index", "structure"):
         raise ValueError(f"correspondence must be 'index' or 'structure', got {correspondence!r}")
     struct_ref = _structural_reference(align_to) if correspondence == "structure" else None
@@ -696,7 +701,46 @@ def _guidance_report(guidance, data, pos, first_batch, na, nr):
     return out
 
 
-def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffold=None, sequences=None, guided=None):
+def _handedness_report(spec, data, pos, first_batch, na, nr):
+    """Stage (b'), ``handedness=``: one census over all samples as model.sample returned them (``chirality.census``: one launch), under
+    ``spec.fix`` the reflection of the samples judged mirrored, in place and with the verdict still on the device, and, when the input
+    has C-alpha coordinates, the same census of the input structure.  The ligand's centres are compared with the input's own when the
+    input has ligand coordinates.  Returns the dict of numpy values; ``pos`` [S,N,3] fp32 is changed in place under ``fix``."""
+    from . import chirality as CH
+    device, n = pos.device, pos.shape[1]
+    one = {k: (v[:1] if torch.is_tensor(v) else v) for k, v in first_batch.items()}     # every sample is the same complex
+    mask, link = (t[:n].contiguous() for t in CH.trace_links(one, 0, na, nr))
+    centres, atoms = CH.ligand_centres(collate_fn([{k: v for k, v in data.items() if k in ("num_atoms", "num_residues", "atom_feats", "bond_distance")}]))
+    has_ligand = na > 0 and "atom_pos" in data and bool((torch.as_tensor(data["atom_pos"]) != 0).any())
+    ref = None
+    if has_ligand and len(centres):
+        centres, ref = CH.centre_reference(torch.as_tensor(data["atom_pos"], dtype=torch.float32), centres, spec.vmin)
+        atoms = centres[:, 0].to(torch.int64)
+    listed = CH.upload(centres, device) if len(centres) else None
+    ref = ref.to(device) if ref is not None and len(centres) else None
+    got = CH.census(pos, mask, link, centres=listed, centre_ref=ref, **spec.thresholds())
+    flipped = (got.verdict < 0) if spec.fix else torch.zeros_like(got.verdict, dtype=torch.bool)
+    if spec.fix:
+        CH.reflect(pos, flipped)
+    out = {"verdict": got.verdict, "basis": got.basis, "flipped": flipped, "helix_fraction": got.helix_fraction,
+           "extended_fraction": got.extended_fraction, "tau": got.tau[:, na: na + nr], "classes": got.classes[:, na: na + nr],
+           "ligand_volume": got.volume}
+    for k, name in enumerate(CH.COUNT_COLUMNS):
+        out[CH.RESULT_NAMES.get(name, name)] = got.counts[:, k]
+    if _ca_trace_problem(data) is None:
+        given = torch.zeros(1, n, 3)
+        given[0, na: na + nr] = torch.as_tensor(data["residue_atom_pos"], dtype=torch.float32)[:, 1]
+        if has_ligand:
+            given[0, :na] = torch.as_tensor(data["atom_pos"], dtype=torch.float32)
+        own = CH.census(given.to(device), mask, link, centres=listed if has_ligand else None, centre_ref=ref if has_ligand else None,
+                        **spec.thresholds())
+        out.update(input_verdict=own.verdict[0], input_basis=own.basis[0], input_counts=own.counts[0])
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    out["ligand_centres"] = atoms.numpy()
+    return out
+
+
+def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffold=None, sequences=None, guided=None, handed=None):
     """Stage (f): the files of ``output_dir``"""
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
@@ -722,6 +766,13 @@ def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffol
                  start=-1 if scaffold["start"] is None else scaffold["start"])
     if guided is not None:
         np.savez(out / "sample_guidance.npz", **guided)
+    if handed is not None:
+        from .chirality import RESULT_NAMES, TEXT_COLUMNS
+        np.savez(out / "sample_handedness.npz", **handed)
+        with open(out / "sample_handedness.txt", "w") as f:
+            f.write("# " + " ".join(TEXT_COLUMNS) + "\n")
+            for k in range(len(proteins)):
+                f.write(" ".join(str(int(handed[RESULT_NAMES.get(c, c)][k])) for c in TEXT_COLUMNS) + "\n")
     if sequences is not None:
         np.savez(out / "sample_sequences.npz", **{k: (np.array(v) if k == "sequences" else v) for k, v in sequences.items()})
         with open(out / "sample_sequences.fasta", "w") as f:
@@ -734,7 +785,7 @@ def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffol
 def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_size: int = 1, seed: int = 0,
                      output_dir: Optional[Union[str, Path]] = None, redesign=None, align_to=None, mirror: bool = True,
                      correspondence: str = "index", assess=None, scaffold=None, sequence_rules=None, decode=None, solver=None,
-                     guidance=None):
+                     guidance=None, handedness=None):
     """Draw ``num_samples`` samples of one featurised complex ``data`` (the dict of ligand_to_data ∪ protein_to_data).
 
     Returns (positions [S,N,3] in Angstrom, logits [S,N,21], proteins, ligand_positions).  With ``output_dir`` the CA
@@ -783,8 +834,8 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     for an input without coordinates such as ``protein_from_sequence``.  A ``Protein`` of the same length: ``lddt_ca`` and
     ``lddt_ca_per_residue`` against it.  The samples are scored as ``model.sample`` returned them; every metric is built from distances,
     which the transform of ``align_to`` leaves as they are (up to its fp32 rounding), so the order of the two does not matter -- and for
-    the same reason a mirror image scores like the original.  The return value gains one more trailing ``dict`` of numpy arrays, after
-    the alignment dict when both are requested.  ``output_dir`` also receives ``sample_quality.npz`` (the dict) and
+    the same reason a mirror image scores like the original (``handedness`` below tells the two apart).  The return value gains one more
+    trailing ``dict`` of numpy arrays, after the alignment dict when both are requested.  ``output_dir`` also receives ``sample_quality.npz`` (the dict) and
     ``sample_quality.txt``: a ``#`` line naming the columns, then one line per sample holding the scalar metrics in the order of
     ``quality.SCALAR_COLUMNS`` (those present).
 
@@ -829,7 +880,27 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     all of the above: the spec's terms (``restraints`` [R,2], ``restraint_bounds`` [R,3] = lo, hi, weight in Angstrom, ``clash`` = the
     three floors and the weight, ``scale``, ``cap``, ``from_level`` (-1 for None), ``schedule``), ``energy`` [S,2] -- the clash and the
     restraint energy of the samples as the model returned them, from ``guidance.energy`` -- and, when the input has coordinates,
-    ``input_energy`` [2], the same of the input structure.  ``output_dir`` also receives ``sample_guidance.npz`` (the dict)."""
+    ``input_energy`` [2], the same of the input structure.  ``output_dir`` also receives ``sample_guidance.npz`` (the dict).
+
+    ``handedness`` (``"report"``, ``"fix"`` or a chirality.Handedness, keyword only, default None: nothing below happens, every launch,
+    draw, return value and file is what it was): tell mirror-image samples from their natural hand WITHOUT a reference, with
+    ``protein_redesign_amd.chirality`` on the device -- a census of the C-alpha trace's virtual dihedrals (right- against left-handed
+    helical turns, the twist of extended stretches) and of the signed volumes at the ligand's tagged stereocentres, compared with the
+    input's own when the input has ligand coordinates -- and a verdict per sample.  The census runs once over all samples as
+    ``model.sample`` returned them, before they are copied to the host.  Under ``"fix"`` the samples judged mirrored (verdict -1) are
+    reflected in place, exactly (the x coordinate negated): the network is reflection-equivariant, so the mirror image of a sample is an
+    equally valid sample.  ``assess``, the guidance report, ``align_to`` and the decoding then see the result: distance metrics do not
+    change, and ``alignment["mirrored"]`` reports on the fixed sample.  Refused, before the model is touched: any other value, and
+    ``"fix"`` together with a ``scaffold`` (the kept rows pin the hand; ``"report"`` is allowed).  The return value gains one more
+    trailing ``dict`` of numpy values, after all of the above: ``verdict`` (+1 natural, -1 mirrored, 0 undecided), ``basis`` (the rule
+    that decided: 1 helices, 2 ligand centres, 3 extended stretches, 0 none) and ``flipped``, each [S]; ``helix_right``, ``helix_left``,
+    ``extended_native``, ``extended_mirror``, ``quads``, ``ligand_kept``, ``ligand_inverted``, ``ligand_flat`` [S]; ``helix_fraction``,
+    ``extended_fraction`` [S]; ``tau`` (radians, NaN where a residue starts no quad) and ``classes`` [S,nr]; ``ligand_centres`` [C] (atom
+    indices) and ``ligand_volume`` [S,C]; and, when the input has C-alpha coordinates, ``input_verdict``, ``input_basis`` and
+    ``input_counts`` [8] of the input structure.  The census values describe the samples AS DRAWN; ``flipped`` says which were
+    reflected, and by the exact symmetry a flipped sample's counts are the swapped ones.  ``output_dir`` also receives
+    ``sample_handedness.npz`` (the dict) and ``sample_handedness.txt``: a ``#`` line naming the columns, then one line per sample holding
+    verdict, basis, flipped and the eight counts.  Nothing is claimed about how often a real sample is decided."""
     if guidance is not None:
         from .guidance import check_guidance
         check_guidance(guidance)
@@ -839,8 +910,11 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         if not isinstance(solver, Solver):
             raise TypeError(f"solver must be a solver.Solver, got {type(solver).__name__}")
     struct_ref, align_ref, quality_ref, spec = _references(model, data, redesign, align_to, correspondence, assess, scaffold,
-                                                           sequence_rules, decode)
+                                                           sequence_rules, decode, handedness)
     device = model.device
+    if handedness is not None:
+        from .chirality import Handedness
+        handedness = Handedness.of(handedness)
     if sequence_rules is not None:
         sequence_rules = sequence_rules.to(device)      # the table is uploaded once, not per batch
     if scaffold is not None:
@@ -848,7 +922,7 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     if spec is not None:
         spec = spec.to(device)                  # a positions mask is uploaded once, not per batch
     na, nr = int(data["num_atoms"]), int(data["num_residues"])
-    scored = align_to is not None or assess is not None or guidance is not None     # then the samples stay on the device until they are scored
+    scored = align_to is not None or assess is not None or guidance is not None or handedness is not None     # then the samples stay on the device until they are scored
     drawn, logits, first_batch, sources = _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device=scored,
                                                 scaffold=scaffold, sequence_rules=sequence_rules, keep_logits=decode is not None,
                                                 solver=solver, guidance=guidance)
@@ -860,6 +934,10 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         kept = {"keep": first_batch[BATCH_KEY][0].cpu().numpy(), "ligand": scaffold.ligand, "sequence": scaffold.sequence,
                 "start": scaffold.start}
     pos = torch.cat(drawn)
+    handed = None
+    if handedness is not None:
+        pos = pos.float().contiguous()          # what torch.cat made already, said once: the reflection works in place
+        handed = _handedness_report(handedness, data, pos, first_batch, na, nr)
     quality = _assess(pos, first_batch, quality_ref, na, nr) if assess is not None else None
     guided = _guidance_report(guidance, data, pos, first_batch, na, nr) if guidance is not None else None
     pos, alignment = _superpose(pos, data, struct_ref, align_ref, mirror, na, nr) if align_to is not None else (pos, None)
@@ -875,8 +953,8 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         alignment = {k: float(v.cpu()) if k == "diversity" else v.cpu().numpy() for k, v in alignment.items()}
     proteins, ligands = _decode(data, positions, logits, na, nr, sequences["tokens"] if sequences is not None else None)
     if output_dir is not None:
-        _write(output_dir, proteins, ligands, used_mask, alignment, quality, kept, sequences, guided)
+        _write(output_dir, proteins, ligands, used_mask, alignment, quality, kept, sequences, guided, handed)
     result = (positions, logits, proteins, ligands) + ((used_mask,) if spec is not None else ())
     result = result + ((alignment,) if alignment is not None else ()) + ((quality,) if quality is not None else ())
     result = result + ((kept,) if kept is not None else ()) + ((sequences,) if sequences is not None else ())
-    return result + ((guided,) if guided is not None else ())
+    return result + ((guided,) if guided is not None else ()) + ((handed,) if handed is not None else ())

@@ -5,7 +5,8 @@ from the two).  ``align.py`` answers "how close is the fold after a global fit";
 preserved, is the ligand pose physically possible, is the chain a chain, which residues line the pocket.
 
 EVERY metric here is built from distances alone, so a mirror image scores exactly like the original.  Chirality is what
-``alignment["mirrored"]`` of ``pipeline.generate_samples(align_to=...)`` reports, not this module.
+``protein_redesign_amd.chirality`` reads off the sample itself (``pipeline.generate_samples(handedness=...)``) and what
+``alignment["mirrored"]`` of ``pipeline.generate_samples(align_to=...)`` reports against a reference, not this module.
 
 Everything runs on the current stream with no host synchronisation.  HIP only: a missing library or a CPU tensor raises."""
 from __future__ import annotations

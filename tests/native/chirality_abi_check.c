@@ -1,0 +1,107 @@
+/* Host-side check of the argument validation of libprd_chirality.so (include/prd_chirality.h), meant to run under AddressSanitizer on a
+ * machine WITHOUT a GPU: every call below must be refused (a negative PRD_CHIRALITY_ERR_* code) before any HIP API is touched, with no
+ * out-of-bounds access on the host side -- the walk over the caller's host copy of the centre list is the one loop over caller memory.
+ * Build + run: protein_redesign_amd.build.build_chirality_check()   (tests/test_chirality_cpu.py) */
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "../../include/prd_chirality.h"
+
+static int failures = 0;
+#define EXPECT(call, code)                                                                 \
+    do {                                                                                   \
+        const int got_ = (call);                                                           \
+        if (got_ != (code)) { printf("FAIL %s -> %d (want %d)\n", #call, got_, (code)); ++failures; } \
+    } while (0)
+
+/* the arguments of a call that would be accepted; a test changes one of them */
+struct args {
+    int *counts, *verdict, *basis; float* tau; int* cls; float* volume;
+    const float* x; long long xs; int xr; const float *mask, *link;
+    const int *centres, *centres_host; const float* cref; int C;
+    float w[8], lo, hi, vmin; int mh, me, S, N;
+};
+
+static int census(const struct args* a) {
+    return prd_chirality_census(a->counts, a->verdict, a->basis, a->tau, a->cls, a->volume, a->x, a->xs, a->xr, a->mask, a->link, a->centres,
+                                a->centres_host, a->cref, a->C, a->w[0], a->w[1], a->w[2], a->w[3], a->w[4], a->w[5], a->w[6], a->w[7], a->lo, a->hi,
+                                a->vmin, a->mh, a->me, a->S, a->N, 0);
+}
+
+int main(void) {
+    static float fbuf[16];                           /* host memory standing in for device pointers: never followed by the checks */
+    static int ibuf[16];
+    int* host = (int*)malloc(8 * sizeof(int));       /* exactly C = 2 centres: a walk past 4 * C ints is an ASan report */
+    const int rows[8] = {1, 0, 2, 3, 4, 3, 2, 1};
+    for (int k = 0; k < 8; ++k) host[k] = rows[k];
+    const struct args ok = {ibuf, ibuf, ibuf, fbuf, ibuf, fbuf, fbuf, 30, 3, fbuf, fbuf, ibuf, host, fbuf, 2,
+                            {-0.342020154f, 0.258819044f, 0.523598790f, 1.39626336f, -0.866025388f, -0.258819044f, 2.09439516f, 3.14159274f},
+                            3.3f, 4.3f, 0.5f, 4, 12, 2, 5};
+    struct args a;
+    EXPECT(prd_chirality_version(), PRD_CHIRALITY_VERSION);
+#define WITH(change, code) do { a = ok; change; EXPECT(census(&a), code); } while (0)
+    WITH(a.counts = 0, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.verdict = 0, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.basis = 0, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.x = 0, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.mask = 0, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.link = 0, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.S = 0, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.N = 0, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.S = -1, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.N = -7, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.C = -1, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.xr = 2, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.xs = -1, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.centres = 0, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.centres_host = 0, PRD_CHIRALITY_ERR_ARG);
+    for (int k = 0; k < 8; ++k) {                    /* every window edge: not finite; then lo >= hi of every pair */
+        WITH(a.w[k] = NAN, PRD_CHIRALITY_ERR_ARG);
+        WITH(a.w[k] = (k & 1) ? INFINITY : -INFINITY, PRD_CHIRALITY_ERR_ARG);
+    }
+    for (int k = 0; k < 8; k += 2) {
+        WITH(a.w[k] = ok.w[k + 1], PRD_CHIRALITY_ERR_ARG);
+        WITH((a.w[k] = ok.w[k + 1], a.w[k + 1] = ok.w[k]), PRD_CHIRALITY_ERR_ARG);
+    }
+    WITH(a.w[0] = -1.5f, PRD_CHIRALITY_ERR_ARG);     /* a cosine outside [-1, 1], a dihedral outside [0, pi] */
+    WITH(a.w[5] = 1.5f, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.w[2] = -0.1f, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.w[7] = 3.2f, PRD_CHIRALITY_ERR_ARG);
+    WITH((a.lo = 4.3f, a.hi = 3.3f), PRD_CHIRALITY_ERR_ARG);
+    WITH(a.lo = a.hi, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.lo = 0.f, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.lo = NAN, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.hi = INFINITY, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.vmin = 0.f, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.vmin = -0.5f, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.vmin = NAN, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.vmin = INFINITY, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.mh = -1, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.me = -1, PRD_CHIRALITY_ERR_ARG);
+    WITH(a.N = PRD_CHIRALITY_MAX_N + 1, PRD_CHIRALITY_ERR_UNSUPPORTED);
+    WITH(a.S = PRD_CHIRALITY_MAX_S + 1, PRD_CHIRALITY_ERR_UNSUPPORTED);
+    WITH(a.C = PRD_CHIRALITY_MAX_C + 1, PRD_CHIRALITY_ERR_UNSUPPORTED);          /* refused before the host copy is walked */
+    /* a centre row outside [0, N): the library's own walk over the host copy, to its last element and no further */
+    WITH(a.N = 4, PRD_CHIRALITY_ERR_ARG);            /* row 4 of the second centre */
+    host[7] = 5;
+    WITH((void)0, PRD_CHIRALITY_ERR_ARG);
+    host[7] = 1, host[2] = -1;
+    WITH((void)0, PRD_CHIRALITY_ERR_ARG);
+    host[2] = 2;
+    EXPECT(prd_chirality_reflect(0, 30, 3, ibuf, 2, 5, 0), PRD_CHIRALITY_ERR_ARG);
+    EXPECT(prd_chirality_reflect(fbuf, 30, 3, 0, 2, 5, 0), PRD_CHIRALITY_ERR_ARG);
+    EXPECT(prd_chirality_reflect(fbuf, 30, 3, ibuf, 0, 5, 0), PRD_CHIRALITY_ERR_ARG);
+    EXPECT(prd_chirality_reflect(fbuf, 30, 3, ibuf, 2, 0, 0), PRD_CHIRALITY_ERR_ARG);
+    EXPECT(prd_chirality_reflect(fbuf, 30, 2, ibuf, 2, 5, 0), PRD_CHIRALITY_ERR_ARG);
+    EXPECT(prd_chirality_reflect(fbuf, -1, 3, ibuf, 2, 5, 0), PRD_CHIRALITY_ERR_ARG);
+    EXPECT(prd_chirality_reflect(fbuf, 30, 3, ibuf, 2, PRD_CHIRALITY_MAX_N + 1, 0), PRD_CHIRALITY_ERR_UNSUPPORTED);
+    EXPECT(prd_chirality_reflect(fbuf, 30, 3, ibuf, PRD_CHIRALITY_MAX_S + 1, 5, 0), PRD_CHIRALITY_ERR_UNSUPPORTED);
+    free(host);
+    if (failures) {
+        printf("%d FAILED\n", failures);
+        return 1;
+    }
+    printf("chirality_abi_check OK\n");
+    return 0;
+}
