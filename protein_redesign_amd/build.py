@@ -69,11 +69,26 @@ LIB_GUIDE, GUIDE_SOURCES = STEP_LIBS["guide"].lib, STEP_LIBS["guide"].sources
 SAMPLE_LIBS = {"chirality": SideLib([os.path.join("chirality", "prd_chirality.hip")], [os.path.join(_INCLUDE, "prd_chirality.h"), PRD_LAUNCH_H],
                                     os.path.join(HERE, "libprd_chirality.so"), "--chirality")}
 LIB_CHIRALITY, CHIRALITY_SOURCES = SAMPLE_LIBS["chirality"].lib, SAMPLE_LIBS["chirality"].sources
+# The history libraries: the same SideLib tuples, flags and compile routine a fifth time, for what runs inside a sampling step AFTER its
+# boundary and keeps a history across steps.  They are kept apart from LOOP_LIBS (the step boundaries: a loop has exactly one) and from
+# STEP_LIBS (what runs before the boundary), each of which its tests pin to its present contents.
+#   multistep  libprd_multistep.so (include/prd_multistep.h): the second- and third-order correction of multistep few-step sampling
+#            (solver.py) and the history of clean-structure estimates it reads; called by the sampling loop only under a multistep
+#            solver of order 2 or 3
+HISTORY_LIBS = {"multistep": SideLib([os.path.join("multistep", "prd_multistep.hip")], [os.path.join(_INCLUDE, "prd_multistep.h"), PRD_LAUNCH_H],
+                                     os.path.join(HERE, "libprd_multistep.so"), "--multistep")}
+LIB_MULTISTEP, MULTISTEP_SOURCES = HISTORY_LIBS["multistep"].lib, HISTORY_LIBS["multistep"].sources
 
 
 def _own_libs():
     """every library with a header of its own: the side libraries, then the loop libraries, the step libraries and the sample libraries"""
     return list(SIDE_LIBS.items()) + list(LOOP_LIBS.items()) + list(STEP_LIBS.items()) + list(SAMPLE_LIBS.items())
+
+
+def _all_libs():
+    """``_own_libs()`` and the history libraries after them: what build_side, the header lookup and the command line serve.  (The
+    first four maps keep a function of their own because tests of theirs hold its value to exactly those four.)"""
+    return _own_libs() + list(HISTORY_LIBS.items())
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -138,7 +153,7 @@ def _hipcc():
 
 def _headers(src):
     """the headers an object of ``src`` depends on"""
-    return next((s.headers for _, s in _own_libs() if src in s.sources), HEADERS)
+    return next((s.headers for _, s in _all_libs() if src in s.sources), HEADERS)
 
 
 def _stamp(src):
@@ -238,10 +253,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
 
 def build_side(name: str, force: bool = False, verbose: bool = True, variant: str = "shipped") -> str:
-    """The side library ``name`` of SIDE_LIBS (or the loop library ``name`` of LOOP_LIBS, or the step library ``name`` of STEP_LIBS, or the sample library ``name`` of SAMPLE_LIBS): its sources with the committed FLAGS and the shipped variant's extras, objects beside
+    """The side library ``name`` of SIDE_LIBS (or the loop library ``name`` of LOOP_LIBS, or the step library ``name`` of STEP_LIBS, or the sample library ``name`` of SAMPLE_LIBS, or the history library ``name`` of HISTORY_LIBS): its sources with the committed FLAGS and the shipped variant's extras, objects beside
     the denoiser's.  Not a variant of libprd_hip.so: ``build()`` compiles none of it, and no side library compiles another.
     ``variant="trace"``: the trace variant's flags and object directory, the library libprd_<name>_trace.so."""
-    s, v = dict(_own_libs())[name], VARIANTS[variant]
+    s, v = dict(_all_libs())[name], VARIANTS[variant]
     lib = s.lib if variant == "shipped" else s.lib.replace(".so", f"_{variant}.so")
     return _build(Variant(v.cflags, v.ldflags, v.objdir, lib, None), s.sources, force, verbose)
 
@@ -284,6 +299,11 @@ def build_guide(force: bool = False, verbose: bool = True) -> str:
 def build_chirality(force: bool = False, verbose: bool = True) -> str:
     """libprd_chirality.so (include/prd_chirality.h, protein_redesign_amd/chirality.py)"""
     return build_side("chirality", force, verbose)
+
+
+def build_multistep(force: bool = False, verbose: bool = True) -> str:
+    """libprd_multistep.so (include/prd_multistep.h, protein_redesign_amd/solver.py)"""
+    return build_side("multistep", force, verbose)
 
 
 def build_asan(verbose: bool = True) -> str:
@@ -362,12 +382,12 @@ if __name__ == "__main__":
         sys.exit(subprocess.call([build_trace()]))
     if "--trace-side" in sys.argv:
         sys.exit(subprocess.call([build_trace_side()]))
-    for side, s in _own_libs():
+    for side, s in _all_libs():
         if s.flag in sys.argv:
             print(build_side(side, force="--force" in sys.argv))
             sys.exit(0)
     if "--resources" in sys.argv:                   # the denoiser's kernels, then those of each side, loop and step library
-        for sources in [SOURCES] + [s.sources for _, s in _own_libs()]:
+        for sources in [SOURCES] + [s.sources for _, s in _all_libs()]:
             for name, u in sorted(resource_usage(verbose=True, sources=sources).items()):
                 print(f"{u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}")
         sys.exit(0)

@@ -31,7 +31,7 @@ from .conditioning import BATCH_KEY as SCAFFOLD_KEY, Scaffold, condition_rows_, 
 from .guidance import MAX_N as GUIDE_MAX_N, Guidance, guide_eps_
 from .masking import MaskDraws, Redesign
 from .sequence import BATCH_KEY as RULES_KEY, SequenceRules, constrain_rows_
-from .solver import Solver, check_time_dim, solver_boundary_
+from .solver import Solver, check_time_dim, multistep_correct_, solver_boundary_
 from .synthetic import NoiseSource
 from .trunk import Denoiser, Linear
 
@@ -552,7 +552,7 @@ class ProteinReDiffModel(_Base):
         if self.training_mode:
             raise ValueError("a solver chooses the levels inference visits; under training_mode=True it is refused")
         check_time_dim(self.time_dim)
-        solver.levels(self.num_steps, scaffold.start if scaffold is not None else None)
+        solver.levels(self.num_steps, scaffold.start if scaffold is not None else None, self.diffusion_schedule)
         return solver
 
     def _guidance_spec(self, guidance: Optional[Guidance], solver: Optional[Solver] = None) -> Optional[Guidance]:
@@ -846,6 +846,15 @@ class ReverseDiffusion:
     prd_condition_rows is handed the counter; ``start = L`` spreads the K levels over [L .. 0].  ``Solver.ancestral(T)`` is the loop
     without a solver, bit for bit.
 
+    A multistep solver of order 2 or 3 (``Solver.multistep``, ``Solver.dpmpp_2m``) is the deterministic ddim loop on its
+    levels plus ONE launch of prd_multistep_correct (include/prd_multistep.h) directly after every boundary, inside the captured graph:
+    it adds the step's gains (``Solver.gain_table`` [K,4]: float64 on the host, rounded once) times the differences between ``x0_hat``
+    and the estimates of the previous one or two steps to ``z``, then pushes ``x0_hat`` onto the history ``x0_hist`` [2,b,N,3].  ``first``
+    [b] holds the counter of the first step run since ``reset()`` / ``restart()``, which both set with a ``fill_``: the history of another
+    trajectory is never used, and the order builds up again over two steps.  A replayed step has one launch more than under
+    ``Solver.ddim``; the kept rows of a scaffold are overwritten after the correction.  With guidance the history holds the guided
+    estimate, which is what the boundary writes.  Order 1 allocates, uploads and launches nothing: it is the ddim loop, bit for bit.
+
     ``guidance`` (guidance.Guidance; beyond the reference): between the network and the boundary of every step ONE
     launch of prd_guide_eps (include/prd_guide.h) evaluates the clash and restraint energy on the step's clean-structure estimate and
     writes ``eps_raw + lam dE/dx0`` (capped per position) into a loop-owned buffer, which the boundary then receives in place of the
@@ -914,6 +923,11 @@ class ReverseDiffusion:
             self.k = torch.full((b,), self.K - 1, dtype=torch.int64, device=dev)
             self.levels, self.coef = up(levels), up(coef)
             self.x0_hat = torch.zeros(b, N, 3, dtype=torch.float32, device=dev)
+        self.gain = self.x0_hist = self.first = None    # a multistep solver of order 2 or 3: the gains, the last two estimates, the first counter
+        if solver is not None and solver.corrected:
+            self.gain = up(solver.gain_table(T, m.diffusion_schedule, scaffold.start if scaffold is not None else None))
+            self.x0_hist = torch.zeros(2, b, N, 3, dtype=torch.float32, device=dev)
+            self.first = torch.full((b,), self.K - 1, dtype=torch.int64, device=dev)
         self.guide = self.guidance_energy = None        # the step-invariant arguments of guide_eps_ (None: no launch), its e_out
         if guidance is not None:
             self.guide = guidance.terms(batch, up)
@@ -1009,6 +1023,8 @@ class ReverseDiffusion:
         else:
             self.k.fill_(counter)
             self.t.fill_(self._levels[counter])
+            if self.first is not None:          # the history belongs to the trajectory that ends here: the order builds up again
+                self.first.fill_(counter)
 
     def reset(self):
         """Back to step T-1 with the same initial noise (bench / repeated runs)."""
@@ -1046,6 +1062,8 @@ class ReverseDiffusion:
                              self.T, self.single_in, self.static["single"], self.rm, m.embed_residue_type[1].weight,
                              self.eb_in, m.embed_beta[0].weight, m.embed_beta[1].weight, self.sync, x0_out=self.x0_hat,
                              seq_h=seq_h, w_seq=m.seq_mlp[3].weight)
+            if self.gain is not None:           # the higher-order correction on the counter the boundary left, and the push of x0_hat
+                multistep_correct_(self.z, self.x0_hat, self.x0_hist, self.k, self.first, self.gain)
             if self.cond is not None or self.rules is not None:
                 self._hold_rows(self._seq_pred_buf)
             return self._seq_pred_buf
