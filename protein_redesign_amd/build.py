@@ -78,6 +78,14 @@ LIB_CHIRALITY, CHIRALITY_SOURCES = SAMPLE_LIBS["chirality"].lib, SAMPLE_LIBS["ch
 HISTORY_LIBS = {"multistep": SideLib([os.path.join("multistep", "prd_multistep.hip")], [os.path.join(_INCLUDE, "prd_multistep.h"), PRD_LAUNCH_H],
                                      os.path.join(HERE, "libprd_multistep.so"), "--multistep")}
 LIB_MULTISTEP, MULTISTEP_SOURCES = HISTORY_LIBS["multistep"].lib, HISTORY_LIBS["multistep"].sources
+# The output libraries: the same SideLib tuples, flags and compile routine a sixth time, for what turns finished samples into what
+# leaves the project.  They are kept apart from SAMPLE_LIBS and from every map above because each of those is held to its present
+# contents by its own tests.
+#   backbone  libprd_backbone.so (include/prd_backbone.h): N, C, O and CB of every residue from the C-alpha trace (backbone.py) --
+#            the last device stage of generate_samples(backbone=...)
+OUTPUT_LIBS = {"backbone": SideLib([os.path.join("backbone", "prd_backbone.hip")], [os.path.join(_INCLUDE, "prd_backbone.h"), PRD_LAUNCH_H],
+                                  os.path.join(HERE, "libprd_backbone.so"), "--backbone")}
+LIB_BACKBONE, BACKBONE_SOURCES = OUTPUT_LIBS["backbone"].lib, OUTPUT_LIBS["backbone"].sources
 
 
 def _own_libs():
@@ -86,9 +94,15 @@ def _own_libs():
 
 
 def _all_libs():
-    """``_own_libs()`` and the history libraries after them: what build_side, the header lookup and the command line serve.  (The
-    first four maps keep a function of their own because tests of theirs hold its value to exactly those four.)"""
+    """``_own_libs()`` and the history libraries after them.  (The first four maps keep a function of their own because tests of
+    theirs hold its value to exactly those four; this one is held to its five in the same way, see ``_every_lib``.)"""
     return _own_libs() + list(HISTORY_LIBS.items())
+
+
+def _every_lib():
+    """``_all_libs()`` and the output libraries after them: what build_side, the header lookup and the command line serve.  (The
+    two functions above keep their values because tests hold each to exactly its maps.)"""
+    return _all_libs() + list(OUTPUT_LIBS.items())
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -153,7 +167,7 @@ def _hipcc():
 
 def _headers(src):
     """the headers an object of ``src`` depends on"""
-    return next((s.headers for _, s in _all_libs() if src in s.sources), HEADERS)
+    return next((s.headers for _, s in _every_lib() if src in s.sources), HEADERS)
 
 
 def _stamp(src):
@@ -253,10 +267,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
 
 def build_side(name: str, force: bool = False, verbose: bool = True, variant: str = "shipped") -> str:
-    """The side library ``name`` of SIDE_LIBS (or the loop library ``name`` of LOOP_LIBS, or the step library ``name`` of STEP_LIBS, or the sample library ``name`` of SAMPLE_LIBS, or the history library ``name`` of HISTORY_LIBS): its sources with the committed FLAGS and the shipped variant's extras, objects beside
+    """The side library ``name`` of SIDE_LIBS (or the loop library ``name`` of LOOP_LIBS, or the step library ``name`` of STEP_LIBS, or the sample library ``name`` of SAMPLE_LIBS, or the history library ``name`` of HISTORY_LIBS, or the output library ``name`` of OUTPUT_LIBS): its sources with the committed FLAGS and the shipped variant's extras, objects beside
     the denoiser's.  Not a variant of libprd_hip.so: ``build()`` compiles none of it, and no side library compiles another.
     ``variant="trace"``: the trace variant's flags and object directory, the library libprd_<name>_trace.so."""
-    s, v = dict(_all_libs())[name], VARIANTS[variant]
+    s, v = dict(_every_lib())[name], VARIANTS[variant]
     lib = s.lib if variant == "shipped" else s.lib.replace(".so", f"_{variant}.so")
     return _build(Variant(v.cflags, v.ldflags, v.objdir, lib, None), s.sources, force, verbose)
 
@@ -306,6 +320,11 @@ def build_multistep(force: bool = False, verbose: bool = True) -> str:
     return build_side("multistep", force, verbose)
 
 
+def build_backbone(force: bool = False, verbose: bool = True) -> str:
+    """libprd_backbone.so (include/prd_backbone.h, protein_redesign_amd/backbone.py)"""
+    return build_side("backbone", force, verbose)
+
+
 def build_asan(verbose: bool = True) -> str:
     """Host-side AddressSanitizer build: libprd_hip_asan.so with the HOST code of every source instrumented
     (-fsanitize=address; device code is compiled as usual: -fno-gpu-sanitize) and the argument-validation driver
@@ -327,6 +346,18 @@ def build_chirality_check(verbose: bool = True) -> str:
     exe = os.path.join(VARIANTS["asan"].objdir, "chirality_abi_check")
     driver = os.path.join(os.path.dirname(HERE), "tests", "native", "chirality_abi_check.c")
     if _stale(exe, [driver, lib, SAMPLE_LIBS["chirality"].headers[0]]):
+        _run([_hipcc(), "-x", "c", driver, "-x", "none", "-g"] + _ASAN + ["-o", exe, lib, "-Wl,-rpath," + HERE], verbose)
+    return exe
+
+
+def build_backbone_check(verbose: bool = True) -> str:
+    """Host-side AddressSanitizer build of libprd_backbone.so (the asan variant's flags: host code instrumented, device code as usual)
+    and the argument-validation driver tests/native/backbone_abi_check.c linked against it.  Runs on a machine without a GPU: every
+    call of the driver is refused before any HIP API is used.  Returns the path of the driver binary."""
+    lib = build_side("backbone", verbose=verbose, variant="asan")
+    exe = os.path.join(VARIANTS["asan"].objdir, "backbone_abi_check")
+    driver = os.path.join(os.path.dirname(HERE), "tests", "native", "backbone_abi_check.c")
+    if _stale(exe, [driver, lib, OUTPUT_LIBS["backbone"].headers[0]]):
         _run([_hipcc(), "-x", "c", driver, "-x", "none", "-g"] + _ASAN + ["-o", exe, lib, "-Wl,-rpath," + HERE], verbose)
     return exe
 
@@ -382,12 +413,12 @@ if __name__ == "__main__":
         sys.exit(subprocess.call([build_trace()]))
     if "--trace-side" in sys.argv:
         sys.exit(subprocess.call([build_trace_side()]))
-    for side, s in _all_libs():
+    for side, s in _every_lib():
         if s.flag in sys.argv:
             print(build_side(side, force="--force" in sys.argv))
             sys.exit(0)
     if "--resources" in sys.argv:                   # the denoiser's kernels, then those of each side, loop and step library
-        for sources in [SOURCES] + [s.sources for _, s in _all_libs()]:
+        for sources in [SOURCES] + [s.sources for _, s in _every_lib()]:
             for name, u in sorted(resource_usage(verbose=True, sources=sources).items()):
                 print(f"{u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}")
         sys.exit(0)

@@ -740,7 +740,41 @@ def _handedness_report(spec, data, pos, first_batch, na, nr):
     return out
 
 
-def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffold=None, sequences=None, guided=None, handed=None):
+def _build_backbone(spec, pos, first_batch, na, nr):
+    """Stage (d'), ``backbone=``: N, C, O and CB of every residue of every sample from the C-alpha trace (``backbone.build``: one launch),
+    on the samples in their final frame and on their final hand -- after the handedness fix and after ``align_to``.  Returns the dict of
+    numpy values: the residue rows of the launch's outputs, then the spec's table and geometry."""
+    from . import backbone as BB
+    from . import chirality as CH
+    n = pos.shape[1]
+    one = {k: (v[:1] if torch.is_tensor(v) else v) for k, v in first_batch.items()}     # every sample is the same complex
+    mask, link = (t[:n].contiguous() for t in CH.trace_links(one, 0, na, nr))
+    got = BB.build(pos.float(), mask, link, BB.upload(spec, pos.device))
+    flags = got.flags[:, na: na + nr]
+    out = {"atoms": got.atoms[:, na: na + nr], "built": flags,
+           "unbuilt_residues": (~(flags[:, :, 0] & flags[:, :, 2] & flags[:, :, 4])).sum(1)}    # a residue without its N, its C or its O
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    out.update(spec.describe())
+    return out
+
+
+def _with_backbone(proteins, built):
+    """the proteins with the built atoms in ``atom_pos`` / ``atom_mask`` (atom37 indices 0 .. 4: N, CA, C, CB, O); CA stays what
+    ``update_pos`` made it, and CB is left out of a residue decoded as G or left undetermined"""
+    no_cb = {RESIDUE_TYPES.index("G"), -1}
+    out = []
+    for k, prot in enumerate(proteins):
+        atom_pos, atom_mask = prot.atom_pos.copy(), prot.atom_mask.copy()
+        have = built["built"][k].copy()
+        have[:, 3] &= ~np.isin(prot.aatype, list(no_cb))
+        for a in (0, 2, 3, 4):
+            atom_pos[:, a] = np.where(have[:, a, None], built["atoms"][k][:, a], 0.0)
+            atom_mask[:, a] = have[:, a]
+        out.append(dataclasses.replace(prot, atom_pos=atom_pos, atom_mask=atom_mask))
+    return out
+
+
+def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffold=None, sequences=None, guided=None, handed=None, built=None):
     """Stage (f): the files of ``output_dir``"""
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
@@ -773,6 +807,8 @@ def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffol
             f.write("# " + " ".join(TEXT_COLUMNS) + "\n")
             for k in range(len(proteins)):
                 f.write(" ".join(str(int(handed[RESULT_NAMES.get(c, c)][k])) for c in TEXT_COLUMNS) + "\n")
+    if built is not None:
+        np.savez(out / "sample_backbone.npz", **built)
     if sequences is not None:
         np.savez(out / "sample_sequences.npz", **{k: (np.array(v) if k == "sequences" else v) for k, v in sequences.items()})
         with open(out / "sample_sequences.fasta", "w") as f:
@@ -785,7 +821,7 @@ def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffol
 def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_size: int = 1, seed: int = 0,
                      output_dir: Optional[Union[str, Path]] = None, redesign=None, align_to=None, mirror: bool = True,
                      correspondence: str = "index", assess=None, scaffold=None, sequence_rules=None, decode=None, solver=None,
-                     guidance=None, handedness=None):
+                     guidance=None, backbone=None, handedness=None):
     """Draw ``num_samples`` samples of one featurised complex ``data`` (the dict of ligand_to_data ∪ protein_to_data).
 
     Returns (positions [S,N,3] in Angstrom, logits [S,N,21], proteins, ligand_positions).  With ``output_dir`` the CA
@@ -900,7 +936,22 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     ``input_counts`` [8] of the input structure.  The census values describe the samples AS DRAWN; ``flipped`` says which were
     reflected, and by the exact symmetry a flipped sample's counts are the swapped ones.  ``output_dir`` also receives
     ``sample_handedness.npz`` (the dict) and ``sample_handedness.txt``: a ``#`` line naming the columns, then one line per sample holding
-    verdict, basis, flipped and the eight counts.  Nothing is claimed about how often a real sample is decided."""
+    verdict, basis, flipped and the eight counts.  Nothing is claimed about how often a real sample is decided.
+
+    ``backbone`` (``"build"`` or a backbone.Backbone, keyword only, default None: nothing below happens, every launch, draw, return
+    value and file is what it was): build N, C, O and CB of every residue from the C-alpha trace, with ``protein_redesign_amd.backbone``
+    on the device -- a rigid planar trans peptide between consecutive C-alphas, turned about the CA-CA axis by an angle read off a table
+    of the C-alpha virtual dihedral (include/prd_backbone.h).  It is the LAST stage on the device: after the handedness fix, ``assess``,
+    the guidance report and ``align_to``, which may have reflected the sample, so the atoms come back in the final frame and on the
+    final hand.  The residues are L-residues whatever the trace: without ``handedness`` a ``UserWarning`` says that mirrored samples get
+    L-residues on a D-trace (a ``scaffold`` pins the hand, and nothing is refused with one).  The proteins' ``atom_pos`` / ``atom_mask``
+    then carry N, CA, C, O and CB (no CB on a residue decoded as G or left undetermined), and ``sample_protein.pdb`` holds them.  Only
+    chain stretches of at least 4 residues with virtual bonds inside the spec's window are built; elsewhere a residue keeps its CA alone.
+    Refused, before the model is touched: any other value.  The return value gains one more trailing ``dict`` of numpy values, after all
+    of the above: ``atoms`` [S,nr,5,3] (N, CA, C, CB, O; zeros where not built), ``built`` [S,nr,5] (bool, as the launch decided: CB is
+    marked on G too), ``unbuilt_residues`` [S] (residues without their N, C or O), ``table`` [73] (radians) and the geometry (``L0``,
+    ``plane_C``, ``plane_O``, ``plane_N``, ``cb``, ``bond``, ``min_angle``).  ``output_dir`` also receives ``sample_backbone.npz`` (the
+    dict).  Nothing is claimed about accuracy on real proteins."""
     if guidance is not None:
         from .guidance import check_guidance
         check_guidance(guidance)
@@ -909,6 +960,9 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         from .solver import Solver
         if not isinstance(solver, Solver):
             raise TypeError(f"solver must be a solver.Solver, got {type(solver).__name__}")
+    if backbone is not None:
+        from .backbone import Backbone
+        backbone = Backbone.of(backbone)
     struct_ref, align_ref, quality_ref, spec = _references(model, data, redesign, align_to, correspondence, assess, scaffold,
                                                            sequence_rules, decode, handedness)
     device = model.device
@@ -922,7 +976,7 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     if spec is not None:
         spec = spec.to(device)                  # a positions mask is uploaded once, not per batch
     na, nr = int(data["num_atoms"]), int(data["num_residues"])
-    scored = align_to is not None or assess is not None or guidance is not None or handedness is not None     # then the samples stay on the device until they are scored
+    scored = align_to is not None or assess is not None or guidance is not None or handedness is not None or backbone is not None     # then the samples stay on the device until they are scored
     drawn, logits, first_batch, sources = _draw(model, data, num_samples, batch_size, seed, spec, device, keep_on_device=scored,
                                                 scaffold=scaffold, sequence_rules=sequence_rules, keep_logits=decode is not None,
                                                 solver=solver, guidance=guidance)
@@ -941,6 +995,12 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     quality = _assess(pos, first_batch, quality_ref, na, nr) if assess is not None else None
     guided = _guidance_report(guidance, data, pos, first_batch, na, nr) if guidance is not None else None
     pos, alignment = _superpose(pos, data, struct_ref, align_ref, mirror, na, nr) if align_to is not None else (pos, None)
+    built = None
+    if backbone is not None:
+        if handedness is None and scaffold is None:
+            warnings.warn("backbone= without handedness=: the builder places L-residues whatever the trace, so a mirror-image sample gets "
+                          "L-residues on a D-trace; use handedness='fix'", UserWarning)
+        built = _build_backbone(backbone, pos, first_batch, na, nr)
     sequences = None
     if decode is not None:
         design = first_batch.get("residue_inv_extra_mask") if first_batch is not None else None      # the prepared batch carries it
@@ -952,9 +1012,12 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     if alignment is not None:
         alignment = {k: float(v.cpu()) if k == "diversity" else v.cpu().numpy() for k, v in alignment.items()}
     proteins, ligands = _decode(data, positions, logits, na, nr, sequences["tokens"] if sequences is not None else None)
+    if built is not None:
+        proteins = _with_backbone(proteins, built)
     if output_dir is not None:
-        _write(output_dir, proteins, ligands, used_mask, alignment, quality, kept, sequences, guided, handed)
+        _write(output_dir, proteins, ligands, used_mask, alignment, quality, kept, sequences, guided, handed, built)
     result = (positions, logits, proteins, ligands) + ((used_mask,) if spec is not None else ())
     result = result + ((alignment,) if alignment is not None else ()) + ((quality,) if quality is not None else ())
     result = result + ((kept,) if kept is not None else ()) + ((sequences,) if sequences is not None else ())
-    return result + ((guided,) if guided is not None else ()) + ((handed,) if handed is not None else ())
+    result = result + ((guided,) if guided is not None else ()) + ((handed,) if handed is not None else ())
+    return result + ((built,) if built is not None else ())
