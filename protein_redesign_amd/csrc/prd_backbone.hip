@@ -12,8 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include "../../../include/prd_backbone.h"
-#include "../prd_launch.h"
+#include "../../include/prd_backbone.h"
+#include "prd_launch.h"
 
 namespace {
 

@@ -14,8 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include "../../../include/prd_chirality.h"
-#include "../prd_launch.h"
+#include "../../include/prd_chirality.h"
+#include "prd_launch.h"
 
 namespace {
 

@@ -13,8 +13,8 @@
 // A sample whose counter is outside [0, rows) is left alone by every workgroup of it: no table row is read, nothing is written.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../../include/prd_guide.h"
-#include "../prd_launch.h"
+#include "../../include/prd_guide.h"
+#include "prd_launch.h"
 
 namespace {
 

@@ -8,8 +8,8 @@
 // Launch latency, not bandwidth, is what it costs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../../include/prd_multistep.h"
-#include "../prd_launch.h"
+#include "../../include/prd_multistep.h"
+#include "prd_launch.h"
 
 namespace {
 

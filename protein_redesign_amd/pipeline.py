@@ -740,7 +740,7 @@ def _handedness_report(spec, data, pos, first_batch, na, nr):
     return out
 
 
-def _build_backbone(spec, pos, first_batch, na, nr):
+def _backbone_atoms(spec, pos, first_batch, na, nr):
     """Stage (d'), ``backbone=``: N, C, O and CB of every residue of every sample from the C-alpha trace (``backbone.build``: one launch),
     on the samples in their final frame and on their final hand -- after the handedness fix and after ``align_to``.  Returns the dict of
     numpy values: the residue rows of the launch's outputs, then the spec's table and geometry."""
@@ -1000,7 +1000,7 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         if handedness is None and scaffold is None:
             warnings.warn("backbone= without handedness=: the builder places L-residues whatever the trace, so a mirror-image sample gets "
                           "L-residues on a D-trace; use handedness='fix'", UserWarning)
-        built = _build_backbone(backbone, pos, first_batch, na, nr)
+        built = _backbone_atoms(backbone, pos, first_batch, na, nr)
     sequences = None
     if decode is not None:
         design = first_batch.get("residue_inv_extra_mask") if first_batch is not None else None      # the prepared batch carries it

@@ -21,7 +21,7 @@ BAND, CAP = 1e-4, 0.005
 # and for the perturbed family -- measured 1.19e-5 and 1.23e-5 (``measured_E``; tests/test_backbone_cpu.py holds the measurement to
 # [E / 2, E]), about one and a half ulps of a coordinate of 100 Angstrom.  The device is allowed 4 E.
 E = (1.5e-5, 1.5e-5)
-TILE, HALO = 256, 3                     # the kernel's row tile and its halo (csrc/backbone/prd_backbone.hip)
+TILE, HALO = 256, 3                     # the kernel's row tile and its halo (csrc/prd_backbone.hip)
 N_, CA_, C_, CB_, O_ = range(5)
 
 

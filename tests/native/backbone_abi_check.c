@@ -1,7 +1,7 @@
 /* Host-side check of the argument validation of libprd_backbone.so (include/prd_backbone.h), meant to run under AddressSanitizer on a
  * machine WITHOUT a GPU: every call below must be refused (a negative PRD_BACKBONE_ERR_* code) before any HIP API is touched, with no
  * out-of-bounds access on the host side.
- * Build + run: protein_redesign_amd.build.build_backbone_check()   (tests/test_backbone_cpu.py) */
+ * Build + run: protein_redesign_amd.build.build_side_check("backbone")   (tests/test_backbone_cpu.py) */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>

@@ -1,7 +1,7 @@
 /* Host-side check of the argument validation of libprd_chirality.so (include/prd_chirality.h), meant to run under AddressSanitizer on a
  * machine WITHOUT a GPU: every call below must be refused (a negative PRD_CHIRALITY_ERR_* code) before any HIP API is touched, with no
  * out-of-bounds access on the host side -- the walk over the caller's host copy of the centre list is the one loop over caller memory.
- * Build + run: protein_redesign_amd.build.build_chirality_check()   (tests/test_chirality_cpu.py) */
+ * Build + run: protein_redesign_amd.build.build_side_check("chirality")   (tests/test_chirality_cpu.py) */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>

@@ -1,19 +1,16 @@
 """CPU: the yardstick of the alignment tests (tests/align_ref.py) on planted cases, the header / build / export list of
 libprd_align.so, and the ``align_to`` argument of pipeline.generate_samples as far as it goes without a GPU."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import align_ref as AR
-from conftest import ROOT
 from protein_redesign_amd import _lib, build
 from protein_redesign_amd import pipeline as PL
 from protein_redesign_amd.synthetic import synthetic_sample
 from sample_stubs import _NoDevice, _Stub, header_entries
-from test_binding_cpu import Recorder, exported
 
 LENGTHS = [3, 4, 5, 21, 22, 63, 64, 65, 130, 257, 1025]
 HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
@@ -97,42 +94,11 @@ def test_header_parses_with_the_derived_binding():
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-def test_build_align_compiles_exports_the_header_and_is_incremental(monkeypatch):
-    lib = build.build_align(verbose=False)
-    assert lib == build.LIB_ALIGN == os.path.join(ROOT, "protein_redesign_amd", "libprd_align.so") and os.path.exists(lib)
-    assert exported(lib) == set(header_entries("align"))
-    rec = Recorder(execute=True)
-    rec.install(monkeypatch)
-    assert build.build_align(verbose=False) == lib
-    assert rec.cmds == []                                       # a second build starts no compiler
-
-
-def test_build_issues_the_commands_it_issued_before(monkeypatch):
-    """build() knows nothing of the new library; build_align() is the same routine on the one source with the committed flags"""
-    monkeypatch.delenv("HIPCC", raising=False)
-    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
-    rec = Recorder(execute=False)
-    rec.install(monkeypatch)
-    build.build(verbose=False)
-    assert len(rec.cmds) == len(build.SOURCES) + 1 and not any("align" in t for c in rec.cmds for t in c)
-    assert [c[-3] for c in rec.cmds[:-1]] == ["{ROOT}/protein_redesign_amd/csrc/" + s for s in build.SOURCES]
-    shipped = rec.cmds[0]
-    rec.cmds = []
-    build.build_align(verbose=False)
-    src, obj = "{ROOT}/protein_redesign_amd/csrc/prd_align.hip", "{ROOT}/protein_redesign_amd/csrc/prd_align.o"
-    assert rec.cmds == [shipped[:-3] + [src, "-o", obj],
-                        shipped[:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_align.so", obj]]
-    assert build.SOURCES == ["prd_gemm.hip", "prd_pair.hip", "prd_tri.hip", "prd_tri2.hip", "prd_bwd.hip", "prd_spa.hip", "prd_tri_heads.hip",
-                             "prd_tri_heads_bwd.hip", "prd_mask.hip"] and sorted(build.VARIANTS) == ["ab", "asan", "shipped", "timing", "trace"]
-
-
-@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_resources_of_the_new_kernels_are_reported_apart():
-    mine = build.resource_usage(sources=build.ALIGN_SOURCES)
+    mine = build.resource_usage(sources=build.SIDE_LIBS["align"].sources)
     assert sorted(mine) == ["align_apply_kernel", "align_compact_kernel", "align_finalize_kernel", "align_search_kernel"]
     assert all(u["scratch"] == 0 for u in mine.values())
     assert mine["align_search_kernel"]["occupancy"] >= 2        # 8 waves per workgroup, one workgroup per CU at the least
-    assert not set(mine) & set(build.resource_usage())          # the denoiser library's table is what it was
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
@@ -140,7 +106,7 @@ def test_workspace_bytes_refusals_growth_and_lower_bound():
     """prd_align_workspace_bytes is host code: 0 for what prd_align_superimpose refuses, never smaller for a longer row, and in the cross
     mode at least the header and the (S + R) x 3 planes of N floats that the kernels index."""
     from protein_redesign_amd import align
-    build.build_align(verbose=False)
+    build.build_side("align", verbose=False)
     ws = align.lib().prd_align_workspace_bytes
     TM, RMSD, CROSS, SELF = align.MODES["tm"], align.MODES["rmsd"], align.PAIRS_CROSS, align.PAIRS_SELF
     assert ws(2, 3, 4096, CROSS, TM, 1) > 0 and ws(2, 3, 4097, CROSS, TM, 1) == 0

@@ -21,12 +21,11 @@ from protein_redesign_amd import chirality as CH
 from protein_redesign_amd import pipeline as PL
 from protein_redesign_amd.conditioning import Scaffold
 from sample_stubs import _NoDevice, header_entries
-from test_binding_cpu import Recorder, exported
 from test_chirality_cpu import _host_reflect, _yardstick_census
 from test_generate_samples_combinations_cpu import fakes
 
 HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
-SOURCE = os.path.join(ROOT, "protein_redesign_amd", "csrc", "backbone", "prd_backbone.hip")
+SOURCE = os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_backbone.hip")
 ONES = lambda n: np.ones(n)         # noqa: E731
 
 
@@ -43,7 +42,7 @@ def test_header_parses_with_the_derived_binding():
     assert BB.ABI_VERSION == 100 and (BB.MAX_N, BB.MAX_S, BB.TABLE) == (32768, 65535, 73)
     with open(SOURCE) as f:
         text = f.read()
-    assert '#include "../prd_launch.h"' in text and "hipLaunchKernelGGL" not in text and "<<<" not in text and "asm" not in text
+    assert '#include "prd_launch.h"' in text and "hipLaunchKernelGGL" not in text and "<<<" not in text and "asm" not in text
     assert "atomic" not in text and "getenv" not in text and "hipMalloc" not in text and "Synchronize" not in text
     assert text.count("prd_launch<") == 1                       # one launch
     with open(os.path.join(ROOT, "include", "prd_backbone.h")) as f:
@@ -52,59 +51,15 @@ def test_header_parses_with_the_derived_binding():
     assert (BR.TILE, BR.HALO) == (256, 3) and "BB_TILE = BB_THREADS" in text and "BB_THREADS = 256" in text and "BB_HALO = 3" in text
 
 
-def test_one_compile_one_link_in_a_map_of_its_own(monkeypatch):
-    assert list(build.OUTPUT_LIBS) == ["backbone"]
-    # the seven pinned values are what they were
-    assert list(build.SIDE_LIBS) == ["align", "tmalign", "quality", "condition", "sequence"] and list(build.LOOP_LIBS) == ["solver"]
-    assert list(build.STEP_LIBS) == ["guide"] and list(build.SAMPLE_LIBS) == ["chirality"] and list(build.HISTORY_LIBS) == ["multistep"]
-    assert [n for n, _ in build._own_libs()] == list(build.SIDE_LIBS) + ["solver", "guide", "chirality"]
-    assert [n for n, _ in build._all_libs()] == [n for n, _ in build._own_libs()] + ["multistep"]
-    assert [n for n, _ in build._every_lib()] == [n for n, _ in build._all_libs()] + ["backbone"]
-    s = build.OUTPUT_LIBS["backbone"]
-    assert s.sources == [os.path.join("backbone", "prd_backbone.hip")] == build.BACKBONE_SOURCES and s.flag == "--backbone"
-    assert s.lib == build.LIB_BACKBONE == os.path.join(ROOT, "protein_redesign_amd", "libprd_backbone.so")
-    assert s.headers == [os.path.join(ROOT, "include", "prd_backbone.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
-    assert build._headers(s.sources[0]) == s.headers
-    monkeypatch.delenv("HIPCC", raising=False)
-    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
-    rec = Recorder(execute=False)
-    rec.install(monkeypatch)
-    build.build_chirality(verbose=False)
-    chirality_cmds, rec.cmds = rec.cmds, []
-    build.build_backbone(verbose=False)
-    src, obj = "{ROOT}/protein_redesign_amd/csrc/backbone/prd_backbone.hip", "{ROOT}/protein_redesign_amd/csrc/backbone/prd_backbone.o"
-    assert len(rec.cmds) == 2 and rec.cmds[0][-4:] == ["-c", src, "-o", obj] and "-ffp-contract=off" in rec.cmds[0]
-    assert rec.cmds[1] == rec.cmds[0][:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_backbone.so", obj]
-    assert rec.cmds == [[t.replace("chirality", "backbone") for t in c] for c in chirality_cmds]       # the same flags and routine
-    # the other builds compile none of it
-    rec.cmds = []
-    build.build(verbose=False)
-    for name, _ in build._all_libs():
-        build.build_side(name, verbose=False)
-    assert rec.cmds and not any("backbone" in t for c in rec.cmds for t in c)
-
-
-@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-def test_forced_cross_compile_exports_the_header_and_a_second_build_is_incremental(monkeypatch):
-    lib = build.build_backbone(force=True, verbose=False)
-    assert lib == build.LIB_BACKBONE and os.path.exists(lib)
-    assert exported(lib) == set(header_entries("backbone"))
-    rec = Recorder(execute=True)
-    rec.install(monkeypatch)
-    assert build.build_backbone(verbose=False) == lib
-    assert rec.cmds == []
-
-
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_resources_of_the_kernel():
     import re
-    mine = build.resource_usage(sources=build.BACKBONE_SOURCES)
+    mine = build.resource_usage(sources=build.SIDE_LIBS["backbone"].sources)
     assert sorted(mine) == ["backbone_build_kernel"]
     u = mine["backbone_build_kernel"]
     with open(SOURCE) as f:
         stated = int(re.search(r"constexpr int BB_LDS_BYTES = (\d+);", f.read()).group(1))
     assert u["lds"] == stated == (256 + 6) * 16 + (256 + 8) * 4 and u["scratch"] == 0 and u["agprs"] == 0 and u["vgprs"] <= 64
-    assert not set(mine) & set(build.resource_usage())
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
@@ -112,7 +67,7 @@ def test_the_library_refuses_on_the_host_before_any_device_call():
     """every refusal of prd_backbone.h is host code that runs before the first HIP call: reachable without a GPU, with device pointers
     that are never followed"""
     import ctypes
-    build.build_backbone(verbose=False)
+    build.build_side("backbone", verbose=False)
     L, D = BB.lib(), BB._DEFINES
     assert L.prd_backbone_version() == 100
     p = ctypes.c_void_p(4096)
@@ -140,11 +95,11 @@ def test_the_library_refuses_on_the_host_before_any_device_call():
 def test_the_host_side_of_the_library_under_address_sanitizer():
     """the same refusals from a stand-alone C program (tests/native/backbone_abi_check.c) against the library's host code built with
     AddressSanitizer.  Needs hipcc only (no GPU)."""
-    exe = build.build_backbone_check(verbose=False)
+    exe = build.build_side_check("backbone", verbose=False)
     out = subprocess.run([exe], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     text = out.stdout.decode(errors="replace")
     assert out.returncode == 0 and "backbone_abi_check OK" in text and "AddressSanitizer" not in text and "FAIL" not in text, text[-2000:]
-    assert os.path.dirname(exe) == build.VARIANTS["asan"].objdir and os.path.exists(build.LIB_BACKBONE.replace(".so", "_asan.so"))
+    assert os.path.dirname(exe) == build.VARIANTS["asan"].objdir and os.path.exists(build.SIDE_LIBS["backbone"].lib.replace(".so", "_asan.so"))
 
 
 # ---- the host specs -------------------------------------------------------------------------------------------------------------------------

@@ -19,10 +19,9 @@ from protein_redesign_amd import pipeline as PL
 from protein_redesign_amd.conditioning import Scaffold
 from protein_redesign_amd.synthetic import synthetic_batch, synthetic_sample
 from sample_stubs import _NoDevice, header_entries
-from test_binding_cpu import Recorder, exported
 
 HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
-SOURCE = os.path.join(ROOT, "protein_redesign_amd", "csrc", "chirality", "prd_chirality.hip")
+SOURCE = os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_chirality.hip")
 
 
 # ---- the yardstick ----------------------------------------------------------------------------------------------------------------------
@@ -133,7 +132,7 @@ def test_header_parses_with_the_derived_binding():
     assert CH.ABI_VERSION == 100 and (CH.MAX_N, CH.MAX_S, CH.MAX_C) == (32768, 65535, 1024)
     with open(SOURCE) as f:
         text = f.read()
-    assert '#include "../prd_launch.h"' in text and "hipLaunchKernelGGL" not in text and "<<<" not in text and "asm" not in text
+    assert '#include "prd_launch.h"' in text and "hipLaunchKernelGGL" not in text and "<<<" not in text and "asm" not in text
     assert "atomic" not in text and "getenv" not in text and "hipMalloc" not in text and "Synchronize" not in text
     assert text.count("prd_launch<") == 2                       # one kernel per entry point
     with open(os.path.join(ROOT, "include", "prd_chirality.h")) as f:
@@ -141,65 +140,23 @@ def test_header_parses_with_the_derived_binding():
     assert head.lstrip().startswith("/* libprd_chirality.so") and "Verdict" in head and "WHO VALIDATES THE ROWS" in head
 
 
-def test_one_compile_one_link_in_a_map_of_its_own(monkeypatch):
-    assert list(build.SAMPLE_LIBS) == ["chirality"] and list(build.LOOP_LIBS) == ["solver"] and list(build.STEP_LIBS) == ["guide"]
-    assert not any("chirality" in m for m in (build.SIDE_LIBS, build.LOOP_LIBS, build.STEP_LIBS))
-    assert [n for n, _ in build._own_libs()] == list(build.SIDE_LIBS) + ["solver", "guide", "chirality"]
-    s = build.SAMPLE_LIBS["chirality"]
-    assert s.sources == [os.path.join("chirality", "prd_chirality.hip")] == build.CHIRALITY_SOURCES and s.flag == "--chirality"
-    assert s.lib == build.LIB_CHIRALITY == os.path.join(ROOT, "protein_redesign_amd", "libprd_chirality.so")
-    assert s.headers == [os.path.join(ROOT, "include", "prd_chirality.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
-    assert build._headers(s.sources[0]) == s.headers
-    monkeypatch.delenv("HIPCC", raising=False)
-    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
-    rec = Recorder(execute=False)
-    rec.install(monkeypatch)
-    build.build_quality(verbose=False)
-    quality_cmds, rec.cmds = rec.cmds, []
-    build.build_chirality(verbose=False)
-    src, obj = "{ROOT}/protein_redesign_amd/csrc/chirality/prd_chirality.hip", "{ROOT}/protein_redesign_amd/csrc/chirality/prd_chirality.o"
-    assert len(rec.cmds) == 2 and rec.cmds[0][-4:] == ["-c", src, "-o", obj] and "-ffp-contract=off" in rec.cmds[0]
-    assert rec.cmds[1] == rec.cmds[0][:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_chirality.so", obj]
-    # the same flags and routine as a side library's: only source, object and library differ
-    swap = lambda t: t.replace("csrc/prd_quality", "csrc/chirality/prd_chirality").replace("quality", "chirality")      # noqa: E731
-    assert rec.cmds == [[swap(t) for t in c] for c in quality_cmds]
-    # the other builds compile none of it
-    rec.cmds = []
-    build.build(verbose=False)
-    for name in list(build.SIDE_LIBS) + list(build.LOOP_LIBS) + list(build.STEP_LIBS):
-        build.build_side(name, verbose=False)
-    assert rec.cmds and not any("chirality" in t for c in rec.cmds for t in c)
-
-
-@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-def test_forced_cross_compile_exports_the_header_and_a_second_build_is_incremental(monkeypatch):
-    lib = build.build_chirality(force=True, verbose=False)
-    assert lib == build.LIB_CHIRALITY and os.path.exists(lib)
-    assert exported(lib) == set(header_entries("chirality"))
-    rec = Recorder(execute=True)
-    rec.install(monkeypatch)
-    assert build.build_chirality(verbose=False) == lib
-    assert rec.cmds == []
-
-
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_resources_of_the_two_kernels():
     import re
-    mine = build.resource_usage(sources=build.CHIRALITY_SOURCES)
+    mine = build.resource_usage(sources=build.SIDE_LIBS["chirality"].sources)
     assert sorted(mine) == ["chirality_census_kernel", "chirality_reflect_kernel"]
     assert all(u["scratch"] == 0 and u["agprs"] == 0 for u in mine.values())
     with open(SOURCE) as f:
         stated = int(re.search(r"constexpr int CH_LDS_BYTES = (\d+);", f.read()).group(1))
     assert mine["chirality_census_kernel"]["lds"] == stated == (256 + 3) * 16 + (256 + 4) * 4 + 4 * 8 * 4 and mine["chirality_reflect_kernel"]["lds"] == 0
     assert mine["chirality_census_kernel"]["vgprs"] <= 64
-    assert not set(mine) & set(build.resource_usage())
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_the_library_refuses_on_the_host_before_any_device_call():
     """every refusal of prd_chirality.h is host code that runs before the first HIP call: reachable without a GPU, with device pointers that
     are never followed.  The centre rows are validated by the LIBRARY, on the host copy the caller passes beside the device list."""
-    build.build_chirality(verbose=False)
+    build.build_side("chirality", verbose=False)
     L, D = CH.lib(), CH._DEFINES
     assert L.prd_chirality_version() == 100
     p = ctypes.c_void_p(4096)
@@ -241,11 +198,11 @@ def test_the_host_side_of_the_library_under_address_sanitizer():
     """the same refusals from a stand-alone C program (tests/native/chirality_abi_check.c) against the library's host code built with
     AddressSanitizer: the walk over the caller's host copy of the centre list stays inside its 4 * C ints.  Needs hipcc only (no GPU)."""
     import subprocess
-    exe = build.build_chirality_check(verbose=False)
+    exe = build.build_side_check("chirality", verbose=False)
     out = subprocess.run([exe], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     text = out.stdout.decode(errors="replace")
     assert out.returncode == 0 and "chirality_abi_check OK" in text and "AddressSanitizer" not in text and "FAIL" not in text, text[-2000:]
-    assert os.path.dirname(exe) == build.VARIANTS["asan"].objdir and os.path.exists(build.LIB_CHIRALITY.replace(".so", "_asan.so"))
+    assert os.path.dirname(exe) == build.VARIANTS["asan"].objdir and os.path.exists(build.SIDE_LIBS["chirality"].lib.replace(".so", "_asan.so"))
 
 
 # ---- the specs and the python-side checks-------------------------------------------------------------------------------------------------

@@ -21,7 +21,6 @@ from protein_redesign_amd.constants import make_args
 from protein_redesign_amd.masking import Redesign
 from protein_redesign_amd.synthetic import NoiseSource, synthetic_sample
 from sample_stubs import _NoDevice, _Stub, header_entries
-from test_binding_cpu import Recorder, exported
 from test_generate_samples_combinations_cpu import NA, NR, complex_data, fakes, redesign_spec
 
 HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
@@ -176,56 +175,19 @@ def test_header_parses_with_the_derived_binding():
         assert '#include "prd_launch.h"' in f.read()         # the host half of its launch is the project's one
 
 
-def test_side_libs_has_the_entry_and_the_other_builds_issue_what_they_issued(monkeypatch):
-    s, q = build.SIDE_LIBS["condition"], build.SIDE_LIBS["quality"]
-    assert s.sources == ["prd_condition.hip"] == build.CONDITION_SOURCES and s.flag == "--condition"
-    assert s.lib == build.LIB_CONDITION == os.path.join(ROOT, "protein_redesign_amd", "libprd_condition.so")
-    assert s.headers == [os.path.join(ROOT, "include", "prd_condition.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
-    assert [x.replace("condition", "quality") for x in (s.sources[0], s.headers[0], s.lib, s.flag)] == [q.sources[0], q.headers[0], q.lib, q.flag]
-    monkeypatch.delenv("HIPCC", raising=False)
-    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
-    rec = Recorder(execute=False)
-    rec.install(monkeypatch)
-    build.build(verbose=False)
-    build.build_align(verbose=False)
-    build.build_tmalign(verbose=False)
-    build.build_quality(verbose=False)
-    assert len(rec.cmds) == len(build.SOURCES) + 1 + 6 and not any("condition" in t for c in rec.cmds for t in c)
-    shipped, quality_cmds = rec.cmds[0], rec.cmds[-2:]
-    rec.cmds = []
-    build.build_condition(verbose=False)
-    src, obj = "{ROOT}/protein_redesign_amd/csrc/prd_condition.hip", "{ROOT}/protein_redesign_amd/csrc/prd_condition.o"
-    assert rec.cmds == [shipped[:-3] + [src, "-o", obj],
-                        shipped[:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_condition.so", obj]]
-    assert rec.cmds == [[t.replace("quality", "condition") for t in c] for c in quality_cmds]      # only source, object and library swapped
-    assert "-ffp-contract=off" in rec.cmds[0]
-
-
-@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-def test_forced_cross_compile_exports_the_header_and_a_second_build_is_incremental(monkeypatch):
-    lib = build.build_condition(force=True, verbose=False)
-    assert lib == build.LIB_CONDITION and os.path.exists(lib)
-    assert exported(lib) == set(header_entries("condition"))
-    rec = Recorder(execute=True)
-    rec.install(monkeypatch)
-    assert build.build_condition(verbose=False) == lib
-    assert rec.cmds == []
-
-
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_resources_of_the_new_kernel():
-    mine = build.resource_usage(sources=build.CONDITION_SOURCES)
+    mine = build.resource_usage(sources=build.SIDE_LIBS["condition"].sources)
     assert sorted(mine) == ["condition_rows_kernel"]
     u = mine["condition_rows_kernel"]
     assert u["scratch"] == 0 and u["agprs"] == 0 and u["lds"] == 0 and u["occupancy"] == 8
-    assert not set(mine) & set(build.resource_usage())
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_the_library_refuses_on_the_host_before_any_device_call():
     """the refusals of prd_condition.h are host code that runs before the first HIP call: every one of them is reachable without a GPU,
     with pointers that are never followed"""
-    build.build_condition(verbose=False)
+    build.build_side("condition", verbose=False)
     L, D = conditioning.lib(), conditioning._DEFINES
     assert L.prd_condition_version() == 100
     p = ctypes.c_void_p(4096)

@@ -21,12 +21,11 @@ from protein_redesign_amd.guidance import Guidance, Restraint
 from protein_redesign_amd.solver import Solver
 from protein_redesign_amd.synthetic import NoiseSource, synthetic_batch
 from sample_stubs import _NoDevice, _Stub, header_entries
-from test_binding_cpu import Recorder, exported
 from test_conditioning_cpu import _generate
 from test_generate_samples_combinations_cpu import NA, NR
 
 HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
-SOURCE = os.path.join(ROOT, "protein_redesign_amd", "csrc", "guide", "prd_guide.hip")
+SOURCE = os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_guide.hip")
 
 
 # ---- header, build, host refusals of the library ----------------------------------------------------------------------------------------
@@ -42,64 +41,24 @@ def test_header_parses_with_the_derived_binding():
     assert D["MAX_B"] == 4096 and D["MAX_N"] == GD.MAX_N == 8192 and D["MAX_R"] == GD.MAX_R >= 2 * 8192 and D["TABLE_STRIDE"] == 4
     with open(SOURCE) as f:
         text = f.read()
-    assert '#include "../prd_launch.h"' in text and "hipLaunchKernelGGL" not in text and "<<<" not in text and "asm" not in text
+    assert '#include "prd_launch.h"' in text and "hipLaunchKernelGGL" not in text and "<<<" not in text and "asm" not in text
     assert "atomic" not in text and "getenv" not in text and "hipMalloc" not in text
     assert text.count("prd_launch<") == 1                       # one kernel per call
 
 
-def test_one_compile_one_link_and_neither_a_side_nor_a_loop_library(monkeypatch):
-    assert "guide" not in build.SIDE_LIBS and "guide" not in build.LOOP_LIBS and list(build.STEP_LIBS) == ["guide"]
-    s = build.STEP_LIBS["guide"]
-    assert s.sources == [os.path.join("guide", "prd_guide.hip")] == build.GUIDE_SOURCES and s.flag == "--guide"
-    assert s.lib == build.LIB_GUIDE == os.path.join(ROOT, "protein_redesign_amd", "libprd_guide.so")
-    assert s.headers == [os.path.join(ROOT, "include", "prd_guide.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
-    assert build._headers(s.sources[0]) == s.headers
-    monkeypatch.delenv("HIPCC", raising=False)
-    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
-    rec = Recorder(execute=False)
-    rec.install(monkeypatch)
-    build.build_condition(verbose=False)
-    condition_cmds, rec.cmds = rec.cmds, []
-    build.build_guide(verbose=False)
-    src, obj = "{ROOT}/protein_redesign_amd/csrc/guide/prd_guide.hip", "{ROOT}/protein_redesign_amd/csrc/guide/prd_guide.o"
-    assert len(rec.cmds) == 2 and rec.cmds[0][-4:] == ["-c", src, "-o", obj] and "-ffp-contract=off" in rec.cmds[0]
-    assert rec.cmds[1] == rec.cmds[0][:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_guide.so", obj]
-    # the same flags and routine as a side library's: only source, object and library differ
-    swap = lambda t: t.replace("csrc/prd_condition", "csrc/guide/prd_guide").replace("condition", "guide")      # noqa: E731
-    assert rec.cmds == [[swap(t) for t in c] for c in condition_cmds]
-    # the other builds compile none of it
-    rec.cmds = []
-    build.build(verbose=False)
-    for name in list(build.SIDE_LIBS) + list(build.LOOP_LIBS):
-        build.build_side(name, verbose=False)
-    assert rec.cmds and not any("guide" in t for c in rec.cmds for t in c)
-
-
-@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-def test_forced_cross_compile_exports_the_header_and_a_second_build_is_incremental(monkeypatch):
-    lib = build.build_guide(force=True, verbose=False)
-    assert lib == build.LIB_GUIDE and os.path.exists(lib)
-    assert exported(lib) == set(header_entries("guide"))
-    rec = Recorder(execute=True)
-    rec.install(monkeypatch)
-    assert build.build_guide(verbose=False) == lib
-    assert rec.cmds == []
-
-
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_resources_of_the_one_kernel():
-    mine = build.resource_usage(sources=build.GUIDE_SOURCES)
+    mine = build.resource_usage(sources=build.SIDE_LIBS["guide"].sources)
     assert sorted(mine) == ["guide_eps_kernel"]
     u = mine["guide_eps_kernel"]
     assert u["scratch"] == 0 and u["agprs"] == 0 and u["vgprs"] <= 64 and 4096 <= u["lds"] <= 4096 + 256     # the tile and two small arrays
-    assert not set(mine) & set(build.resource_usage())
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_the_library_refuses_on_the_host_before_any_device_call():
     """every refusal of prd_guide.h is host code that runs before the first HIP call: reachable without a GPU, with pointers that are
     never followed"""
-    build.build_guide(verbose=False)
+    build.build_side("guide", verbose=False)
     L, D = GD.lib(), GD._DEFINES
     assert L.prd_guide_version() == 100
     p, far = ctypes.c_void_p(1 << 20), ctypes.c_void_p(1 << 30)

@@ -16,11 +16,10 @@ from protein_redesign_amd import _lib, build, diffusion_model, solver
 from protein_redesign_amd.solver import Solver
 from protein_redesign_amd.synthetic import NoiseSource
 from sample_stubs import header_entries
-from test_binding_cpu import Recorder, exported
 from test_solver_cpu import _drawn
 
 HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
-SOURCE = os.path.join(ROOT, "protein_redesign_amd", "csrc", "multistep", "prd_multistep.hip")
+SOURCE = os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_multistep.hip")
 
 
 # ---- levels ---------------------------------------------------------------------------------------------------------------------------
@@ -269,68 +268,24 @@ def test_header_parses_with_the_derived_binding():
     assert solver.MULTISTEP_ABI_VERSION == 100 and solver.GAIN_STRIDE == 4
     with open(SOURCE) as f:
         text = f.read()
-    assert '#include "../prd_launch.h"' in text and "hipLaunchKernelGGL" not in text and "<<<" not in text and "asm" not in text
+    assert '#include "prd_launch.h"' in text and "hipLaunchKernelGGL" not in text and "<<<" not in text and "asm" not in text
     assert "atomic" not in text and "getenv" not in text and "hipMalloc" not in text and "Synchronize" not in text
     assert text.count("prd_launch<") == 1
 
 
-def test_one_compile_one_link_in_a_fifth_map(monkeypatch):
-    assert list(build.HISTORY_LIBS) == ["multistep"]
-    assert list(build.SIDE_LIBS) == ["align", "tmalign", "quality", "condition", "sequence"] and list(build.LOOP_LIBS) == ["solver"]
-    assert list(build.STEP_LIBS) == ["guide"] and list(build.SAMPLE_LIBS) == ["chirality"]
-    assert not any("multistep" in m for m in (build.SIDE_LIBS, build.LOOP_LIBS, build.STEP_LIBS, build.SAMPLE_LIBS))
-    assert [n for n, _ in build._all_libs()] == [n for n, _ in build._own_libs()] + ["multistep"]
-    s = build.HISTORY_LIBS["multistep"]
-    assert s.sources == [os.path.join("multistep", "prd_multistep.hip")] == build.MULTISTEP_SOURCES and s.flag == "--multistep"
-    assert s.lib == build.LIB_MULTISTEP == os.path.join(ROOT, "protein_redesign_amd", "libprd_multistep.so")
-    assert s.headers == [os.path.join(ROOT, "include", "prd_multistep.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
-    assert build._headers(s.sources[0]) == s.headers
-    monkeypatch.delenv("HIPCC", raising=False)
-    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
-    rec = Recorder(execute=False)
-    rec.install(monkeypatch)
-    build.build_condition(verbose=False)
-    condition_cmds, rec.cmds = rec.cmds, []
-    build.build_multistep(verbose=False)
-    src, obj = "{ROOT}/protein_redesign_amd/csrc/multistep/prd_multistep.hip", "{ROOT}/protein_redesign_amd/csrc/multistep/prd_multistep.o"
-    assert len(rec.cmds) == 2 and rec.cmds[0][-4:] == ["-c", src, "-o", obj] and "-ffp-contract=off" in rec.cmds[0]
-    assert rec.cmds[1] == rec.cmds[0][:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_multistep.so", obj]
-    # the same flags and routine as a side library's: only source, object and library differ
-    swap = lambda t: t.replace("csrc/prd_condition", "csrc/multistep/prd_multistep").replace("condition", "multistep")      # noqa: E731
-    assert rec.cmds == [[swap(t) for t in c] for c in condition_cmds]
-    # the other builds compile none of it
-    rec.cmds = []
-    build.build(verbose=False)
-    for name, _ in build._own_libs():
-        build.build_side(name, verbose=False)
-    assert rec.cmds and not any("multistep" in t for c in rec.cmds for t in c)
-
-
-@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-def test_forced_cross_compile_exports_the_header_and_a_second_build_is_incremental(monkeypatch):
-    lib = build.build_multistep(force=True, verbose=False)
-    assert lib == build.LIB_MULTISTEP and os.path.exists(lib)
-    assert exported(lib) == set(header_entries("multistep"))
-    rec = Recorder(execute=True)
-    rec.install(monkeypatch)
-    assert build.build_multistep(verbose=False) == lib
-    assert rec.cmds == []
-
-
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_resources_of_the_one_kernel():
-    mine = build.resource_usage(sources=build.MULTISTEP_SOURCES)
+    mine = build.resource_usage(sources=build.SIDE_LIBS["multistep"].sources)
     assert sorted(mine) == ["multistep_correct_kernel"]
     u = mine["multistep_correct_kernel"]
     assert u["scratch"] == 0 and u["agprs"] == 0 and u["lds"] == 0 and u["vgprs"] <= 32
-    assert not set(mine) & set(build.resource_usage()) and not set(mine) & set(build.resource_usage(sources=build.SOLVER_SOURCES))
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_the_library_refuses_on_the_host_before_any_device_call():
     """every refusal of prd_multistep.h is host code that runs before the first HIP call: reachable without a GPU, with pointers that
     are never followed"""
-    build.build_multistep(verbose=False)
+    build.build_side("multistep", verbose=False)
     L, D = solver.multistep_lib(), solver._MULTISTEP_DEFINES
     assert L.prd_multistep_version() == 100
     p = ctypes.c_void_p(4096)

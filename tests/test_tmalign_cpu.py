@@ -16,7 +16,7 @@ from protein_redesign_amd import _lib, build
 from protein_redesign_amd import pipeline as PL
 from protein_redesign_amd.synthetic import synthetic_sample
 from sample_stubs import _NoDevice, _Stub, header_entries
-from test_binding_cpu import Recorder, exported
+from test_binding_cpu import Recorder
 
 HAVE_HIPCC = os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
 
@@ -91,45 +91,15 @@ def test_header_parses_with_the_derived_binding():
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
-def test_build_tmalign_compiles_exports_the_header_and_is_incremental(monkeypatch):
-    lib = build.build_tmalign(verbose=False)
-    assert lib == build.LIB_TMALIGN == os.path.join(ROOT, "protein_redesign_amd", "libprd_tmalign.so") and os.path.exists(lib)
-    assert exported(lib) == set(header_entries("tmalign"))
-    rec = Recorder(execute=True)
-    rec.install(monkeypatch)
-    assert build.build_tmalign(verbose=False) == lib
-    assert rec.cmds == []                                       # a second build starts no compiler
-
-
-def test_the_other_builds_issue_the_commands_they_issued_before(monkeypatch):
-    monkeypatch.delenv("HIPCC", raising=False)
-    monkeypatch.setattr(build, "_stale", lambda out, deps: True)
-    rec = Recorder(execute=False)
-    rec.install(monkeypatch)
-    build.build(verbose=False)
-    assert len(rec.cmds) == len(build.SOURCES) + 1 and not any("align" in t for c in rec.cmds for t in c)
-    shipped = rec.cmds[0]
-    rec.cmds = []
-    build.build_align(verbose=False)
-    assert len(rec.cmds) == 2 and not any("tmalign" in t for c in rec.cmds for t in c)
-    rec.cmds = []
-    build.build_tmalign(verbose=False)
-    src, obj = "{ROOT}/protein_redesign_amd/csrc/prd_tmalign.hip", "{ROOT}/protein_redesign_amd/csrc/prd_tmalign.o"
-    assert rec.cmds == [shipped[:-3] + [src, "-o", obj],
-                        shipped[:1] + ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", "{ROOT}/protein_redesign_amd/libprd_tmalign.so", obj]]
-    assert build.ALIGN_SOURCES == ["prd_align.hip"] and build.TMALIGN_SOURCES == ["prd_tmalign.hip"]
-
-
-@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_the_shared_fit_header_makes_both_side_libraries_stale_and_not_the_denoiser(monkeypatch):
     """``_stale`` is the real one and no compiler runs: the header of the fit (csrc/prd_superpose.h) is given the newest time stamp, and
     a command that is recorded makes its output newer still, as the compiler would have."""
     build.build(verbose=False)
-    build.build_align(verbose=False)
-    build.build_tmalign(verbose=False)
+    build.build_side("align", verbose=False)
+    build.build_side("tmalign", verbose=False)
     header, real, written = os.path.join(ROOT, "protein_redesign_amd", "csrc", "prd_superpose.h"), os.path.getmtime, []
     assert os.path.exists(header)
-    newest = max(real(p) for p in (build.LIB, build.LIB_ALIGN, build.LIB_TMALIGN)) + 10.0
+    newest = max(real(p) for p in (build.LIB, build.SIDE_LIBS["align"].lib, build.SIDE_LIBS["tmalign"].lib)) + 10.0
     monkeypatch.setattr(os.path, "getmtime", lambda p: newest + 10.0 * (1 + written.index(p)) if p in written else newest if p == header else real(p))
 
     class Touching(Recorder):
@@ -140,8 +110,8 @@ def test_the_shared_fit_header_makes_both_side_libraries_stale_and_not_the_denoi
     rec.install(monkeypatch)
     build.build(verbose=False)
     assert rec.cmds == []
-    for fn, name in ((build.build_align, "align"), (build.build_tmalign, "tmalign")):
-        fn(verbose=False)
+    for name in ("align", "tmalign"):
+        build.build_side(name, verbose=False)
         obj = "{ROOT}/protein_redesign_amd/csrc/prd_%s.o" % name
         assert [c[-3:] for c in rec.cmds] == [["{ROOT}/protein_redesign_amd/csrc/prd_%s.hip" % name, "-o", obj],
                                               ["-o", "{ROOT}/protein_redesign_amd/libprd_%s.so" % name, obj]]
@@ -161,16 +131,15 @@ def test_the_fit_is_defined_in_one_file():
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_resources_of_the_new_kernels():
-    mine = build.resource_usage(sources=build.TMALIGN_SOURCES)
+    mine = build.resource_usage(sources=build.SIDE_LIBS["tmalign"].sources)
     assert sorted(mine) == ["tmalign_compact_kernel", "tmalign_finalize_kernel", "tmalign_refine_kernel", "tmalign_search_kernel"]
     assert all(u["scratch"] == 0 for u in mine.values())
-    assert not set(mine) & set(build.resource_usage()) and not set(mine) & set(build.resource_usage(sources=build.ALIGN_SOURCES))
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
 def test_workspace_bytes_refusals_growth_and_lower_bound():
     from protein_redesign_amd import tmalign
-    build.build_tmalign(verbose=False)
+    build.build_side("tmalign", verbose=False)
     ws = tmalign.lib().prd_tmalign_workspace_bytes
     assert ws(2, 3, 2048, 2048, 1) > 0 and ws(2, 3, 2049, 64, 1) == 0 and ws(2, 3, 64, 2049, 1) == 0
     assert ws(0, 3, 64, 64, 1) == 0 and ws(2, 0, 64, 64, 1) == 0 and ws(2, 3, 0, 64, 1) == 0 and ws(2, 3, 64, 0, 1) == 0 and ws(-1, 3, 64, 64, 0) == 0

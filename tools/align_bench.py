@@ -88,7 +88,7 @@ def main():
     gpu_pw = align.pairwise_tm(x, m).cpu().numpy()
     npairs = S * (S - 1) // 2
     seeds = len(AR.seeds(L))
-    res = build.resource_usage(sources=build.ALIGN_SOURCES)
+    res = build.resource_usage(sources=build.SIDE_LIBS["align"].sources)
     lines = [
         f"align_bench: {S} samples, L = {L} masked positions (N = {L}), mirror on, {seeds} seeds per (pair, mirror)",
         f"box: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; host {platform.processor() or platform.machine()}, {a.cpu_procs} processes for the yardstick",

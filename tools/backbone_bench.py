@@ -80,7 +80,7 @@ def main():
     read, written = N * 20 * S, N * 64 * S
     lines.append(f"the launch reads {read} bytes and writes {written} ({(read + written) / 1e6:.2f} MB in all): it is bound by launch and binding "
                  "overhead at this size, not by memory")
-    res = build.resource_usage(sources=build.BACKBONE_SOURCES)
+    res = build.resource_usage(sources=build.SIDE_LIBS["backbone"].sources)
     lines.append("resources (hipcc -Rpass-analysis=kernel-resource-usage, committed flags):")
     lines += [f"  {u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}" for name, u in sorted(res.items())]
     text = "\n".join(lines) + "\n"

@@ -81,7 +81,7 @@ def main():
     moved = N * 28 * S + N * 8 * S
     lines.append(f"the census reads {N * 28 * S} bytes and writes {N * 8 * S + S * 40 + S * C * 4} ({moved / 1e6:.2f} MB in all): it is bound by launch and "
                  "binding overhead at this size, not by memory")
-    res = build.resource_usage(sources=build.CHIRALITY_SOURCES)
+    res = build.resource_usage(sources=build.SIDE_LIBS["chirality"].sources)
     lines.append("resources (hipcc -Rpass-analysis=kernel-resource-usage, committed flags):")
     lines += [f"  {u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}" for name, u in sorted(res.items())]
     text = "\n".join(lines) + "\n"

@@ -72,7 +72,7 @@ def main():
             med = float(np.median(ms[name]))
             lines.append(f"{atoms + residues:5d} {name:<36} | {med:9.4f} {min(ms[name]):8.4f} {max(ms[name]):8.4f} | {med - base:+13.4f} ms")
         del loops
-    res = build.resource_usage(sources=build.CONDITION_SOURCES)
+    res = build.resource_usage(sources=build.SIDE_LIBS["condition"].sources)
     lines.append("resources (hipcc -Rpass-analysis=kernel-resource-usage, committed flags):")
     lines += [f"  {u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}" for name, u in sorted(res.items())]
     text = "\n".join(lines) + "\n"

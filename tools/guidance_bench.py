@@ -121,7 +121,7 @@ def main():
         lines.append(f"      ({len(guided.guidance.restraints)} restraints; clash / restraint energy at the last estimate: "
                      + " / ".join(f"{v:.3f}" for v in guided.guidance_energy.double().sum(dim=(0, 1)).tolist()) + ")")
         del loops
-    res = build.resource_usage(sources=build.GUIDE_SOURCES)
+    res = build.resource_usage(sources=build.SIDE_LIBS["guide"].sources)
     lines.append("resources (hipcc -Rpass-analysis=kernel-resource-usage, committed flags):")
     lines += [f"  {u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}" for name, u in sorted(res.items())]
     text = "\n".join(lines) + "\n"

@@ -84,7 +84,7 @@ def main():
             lines.append(f"{atoms + residues:5d} {name:<30} | {med:9.4f} {min(ms[name]):8.4f} {max(ms[name]):8.4f} | "
                          f"{med - float(np.median(base)):+9.4f} ms | {overlap}")
         del loops
-    res = build.resource_usage(sources=build.MULTISTEP_SOURCES)
+    res = build.resource_usage(sources=build.SIDE_LIBS["multistep"].sources)
     lines.append("resources (hipcc -Rpass-analysis=kernel-resource-usage, committed flags):")
     lines += [f"  {u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}" for name, u in sorted(res.items())]
     text = "\n".join(lines) + "\n"

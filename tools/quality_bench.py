@@ -91,7 +91,7 @@ def main():
         diff = float((fused() - plain()).abs().max())
         lines.append(f"{S:4d} {N:5d} | {tf[0]:9.3f} {tf[1]:8.3f} {tf[2]:8.3f} {mf / 2 ** 20:9.2f} | {tp[0]:9.3f} {tp[1]:8.3f} {tp[2]:8.3f} {mp / 2 ** 20:9.2f} | "
                      f"{tp[0] / tf[0]:11.2f} {diff:17.2e}")
-    res = build.resource_usage(sources=build.QUALITY_SOURCES)
+    res = build.resource_usage(sources=build.SIDE_LIBS["quality"].sources)
     lines.append("resources (hipcc -Rpass-analysis=kernel-resource-usage, committed flags):")
     lines += [f"  {u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}" for name, u in sorted(res.items())]
     text = "\n".join(lines) + "\n"

@@ -104,7 +104,7 @@ def main():
             med = float(np.median(sec))
             base = med if base is None else base
             lines.append(f"{atoms + residues:5d} {name:<26} | {med:9.4f} {min(sec):8.4f} {max(sec):8.4f} | {base / med:8.1f}x")
-    res = build.resource_usage(sources=build.SOLVER_SOURCES)
+    res = build.resource_usage(sources=build.SIDE_LIBS["solver"].sources)
     lines.append("resources (hipcc -Rpass-analysis=kernel-resource-usage, committed flags):")
     lines += [f"  {u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}" for name, u in sorted(res.items())]
     text = "\n".join(lines) + "\n"

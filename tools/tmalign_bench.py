@@ -61,7 +61,7 @@ def main():
     t = device_time(lambda: tmalign.align(x, y, mx, my), a.iters, 3)
     out = tmalign.align(x, y, mx, my)
     gpu_tm = out.tm.cpu().numpy()
-    res = build.resource_usage(sources=build.TMALIGN_SOURCES)
+    res = build.resource_usage(sources=build.SIDE_LIBS["tmalign"].sources)
     lines = [
         f"tmalign_bench: {S} samples of L = {L} against one reference of {Lr} residues, mirror on: {S * 2 * 3} refine workgroups",
         f"box: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; host {platform.processor() or platform.machine()}",
