@@ -306,7 +306,7 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-# ---- the side libraries (the rows of build.SIDE_LIBS): one binding, one statement of their argument checks ----------------------------
+# ---- the side libraries (the rows of build.SIDE_LIBS and build.MORE_SIDE_LIBS): one binding, one statement of their argument checks ----
 class SideLibrary:
     """The binding of ``libprd_<name>.so`` beside the package, derived from the name: ``include/prd_<name>.h`` is read and parsed here
     (``entries``, and ``defines`` without their ``PRD_<NAME>_`` prefix), the library itself is loaded on the first ``lib()``.  ``version``:

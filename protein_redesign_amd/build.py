@@ -31,6 +31,7 @@ HEADERS = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_launch.h"
 #   chirality  the handedness census of samples, a verdict each, the reflection of mirrored ones (chirality.py); after the loop
 #   multistep  the order-2 and order-3 correction of multistep sampling and its history (solver.py); after the boundary, at those orders
 #   backbone   N, C, O and CB of every residue from the C-alpha trace (backbone.py); the last device stage, generate_samples(backbone=...)
+#   dssp       hydrogen bonds and the eight DSSP classes of the built atoms (dssp.py); after backbone, generate_samples(secondary=...)
 # csrc/prd_superpose.h is the fit that align and tmalign share: touching it makes both stale and no object of the denoiser.
 # csrc/prd_launch.h is the host half of every launch, theirs as the denoiser's: touching it makes every object stale.  Each has a
 # trace form as well (build_side(name, variant="trace"): objects under csrc/trace, libprd_<name>_trace.so); build_trace_side links
@@ -47,6 +48,23 @@ SIDE_LIBS = {"align": _side("align", PRD_SUPERPOSE_H, traced=True), "tmalign": _
              "quality": _side("quality", traced=True), "condition": _side("condition", traced=True), "sequence": _side("sequence", traced=True),
              "solver": _side("solver"), "guide": _side("guide"), "chirality": _side("chirality"), "multistep": _side("multistep"),
              "backbone": _side("backbone")}
+# The second table: side libraries added after the first one was closed.  SIDE_LIBS, the top level of csrc/ and the command lines of its
+# ten rows are pinned as they stand by the tests that were written with them, so a later library is a row HERE -- the same row type, the
+# same flags, the same compile routine -- with its source and its private headers under csrc/side/ and its objects beside them
+# (csrc/side/prd_<name>.o; <variant objdir>/side/ for a variant).  csrc/side/prd_dssp_energy.h is the one statement of the hydrogen-bond
+# energy, shared by both roles of the sweep.  ``side_lib(name)`` finds a row in either table.
+MORE_SIDE_LIBS = {"dssp": SideLib(["side/prd_dssp.hip"], [os.path.join(_INCLUDE, "prd_dssp.h"), PRD_LAUNCH_H, os.path.join(CSRC, "side", "prd_dssp_energy.h")],
+                                  os.path.join(HERE, "libprd_dssp.so"), "--dssp", False)}
+
+
+def side_lib(name):
+    """the row of the side library ``name``, from either table"""
+    return SIDE_LIBS[name] if name in SIDE_LIBS else MORE_SIDE_LIBS[name]
+
+
+def all_side_libs():
+    """{name: row} of both tables, the first table first"""
+    return {**SIDE_LIBS, **MORE_SIDE_LIBS}
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -111,7 +129,7 @@ def _hipcc():
 
 def _headers(src):
     """the headers an object of ``src`` depends on"""
-    return next((s.headers for s in SIDE_LIBS.values() if src in s.sources), HEADERS)
+    return next((s.headers for s in all_side_libs().values() if src in s.sources), HEADERS)
 
 
 def _stamp(src):
@@ -185,6 +203,7 @@ def _build(v: Variant, sources, force: bool = False, verbose: bool = True) -> st
                     continue
         obj = os.path.join(v.objdir, src.replace(".hip", ".o"))
         objs.append(obj)
+        os.makedirs(os.path.dirname(obj), exist_ok=True)          # a source of the second table lies in a subdirectory, and so does its object
         if not (force or _stale(obj, [spath] + _headers(src))):
             continue
         cmd = [_hipcc()] + FLAGS + EXTRA_FLAGS.get(src, []) + v.cflags + ["-c", spath, "-o", obj]
@@ -210,10 +229,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
 
 def build_side(name: str, force: bool = False, verbose: bool = True, variant: str = "shipped") -> str:
-    """The side library ``name`` of SIDE_LIBS: its source with the committed FLAGS and the shipped variant's extras, its object beside
+    """The side library ``name`` of SIDE_LIBS or MORE_SIDE_LIBS: its source with the committed FLAGS and the shipped variant's extras, its object beside
     the denoiser's.  Not a variant of libprd_hip.so: ``build()`` compiles none of it, and no side library compiles another.
     Another ``variant`` ("trace", "asan"): that variant's flags and object directory, the library libprd_<name>_<variant>.so."""
-    s, v = SIDE_LIBS[name], VARIANTS[variant]
+    s, v = side_lib(name), VARIANTS[variant]
     lib = s.lib if variant == "shipped" else s.lib.replace(".so", f"_{variant}.so")
     return _build(Variant(v.cflags, v.ldflags, v.objdir, lib, None), s.sources, force, verbose)
 
@@ -242,7 +261,7 @@ def build_side_check(name: str, verbose: bool = True) -> str:
     tests/native/<name>_abi_check.c linked against it.  Runs on a machine without a GPU: every call of the driver is refused before
     any HIP API is used.  Returns the path of the driver binary."""
     lib = build_side(name, verbose=verbose, variant="asan")
-    return _link_driver("asan", f"{name}_abi_check", [lib], SIDE_LIBS[name].headers[:1], ["-g"] + _ASAN, verbose)
+    return _link_driver("asan", f"{name}_abi_check", [lib], side_lib(name).headers[:1], ["-g"] + _ASAN, verbose)
 
 
 def build_trace(verbose: bool = True) -> str:
@@ -290,12 +309,12 @@ if __name__ == "__main__":
         sys.exit(subprocess.call([build_trace()]))
     if "--trace-side" in sys.argv:
         sys.exit(subprocess.call([build_trace_side()]))
-    for side, s in SIDE_LIBS.items():
+    for side, s in all_side_libs().items():
         if s.flag in sys.argv:
             print(build_side(side, force="--force" in sys.argv))
             sys.exit(0)
     if "--resources" in sys.argv:                   # the denoiser's kernels, then those of each side library
-        for sources in [SOURCES] + [s.sources for s in SIDE_LIBS.values()]:
+        for sources in [SOURCES] + [s.sources for s in all_side_libs().values()]:
             for name, u in sorted(resource_usage(verbose=True, sources=sources).items()):
                 print(f"{u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}")
         sys.exit(0)
