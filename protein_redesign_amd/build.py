@@ -273,6 +273,15 @@ def build_trace(verbose: bool = True) -> str:
     return _link_driver("trace", "launch_trace", [lib], [PRD_HIP_H], ["-O1", "-Wno-format-extra-args"], verbose)
 
 
+def build_gemm_dispatch(verbose: bool = True) -> str:
+    """The launch trace of single calls of the GEMM family: the same libprd_hip_trace.so and the driver tests/native/gemm_dispatch_trace.c
+    linked against it, which reads one case per line from stdin (tests/gemm_cases.py), calls prd_gemm / prd_ln_rows / prd_softmax_rows /
+    prd_single_fc1_folded or one of their host queries with dummy addresses and prints the library's launch lines and the return code.
+    Host code only; tests/test_gemm_dispatch_cpu.py reads its output.  Returns the path of the driver binary."""
+    lib = _build(VARIANTS["trace"], SOURCES, verbose=verbose)
+    return _link_driver("trace", "gemm_dispatch_trace", [lib], [PRD_HIP_H], ["-O1"], verbose)
+
+
 def build_trace_side(verbose: bool = True) -> str:
     """The launch trace of the side libraries: libprd_<name>_trace.so of the five ``traced`` rows and the driver
     tests/native/side_launch_trace.c linked against them, which walks every entry point of their headers over the shapes at which a
