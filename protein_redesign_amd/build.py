@@ -32,6 +32,7 @@ HEADERS = [os.path.join(CSRC, "prd_common.h"), os.path.join(CSRC, "prd_launch.h"
 #   multistep  the order-2 and order-3 correction of multistep sampling and its history (solver.py); after the boundary, at those orders
 #   backbone   N, C, O and CB of every residue from the C-alpha trace (backbone.py); the last device stage, generate_samples(backbone=...)
 #   dssp       hydrogen bonds and the eight DSSP classes of the built atoms (dssp.py); after backbone, generate_samples(secondary=...)
+#   sasa       Shrake-Rupley point counts of every atom: burial and the ligand interface (sasa.py); after backbone, generate_samples(accessibility=...)
 # csrc/prd_superpose.h is the fit that align and tmalign share: touching it makes both stale and no object of the denoiser.
 # csrc/prd_launch.h is the host half of every launch, theirs as the denoiser's: touching it makes every object stale.  Each has a
 # trace form as well (build_side(name, variant="trace"): objects under csrc/trace, libprd_<name>_trace.so); build_trace_side links
@@ -57,14 +58,34 @@ MORE_SIDE_LIBS = {"dssp": SideLib(["side/prd_dssp.hip"], [os.path.join(_INCLUDE,
                                   os.path.join(HERE, "libprd_dssp.so"), "--dssp", False)}
 
 
+# The third table, and the LAST one: the contents of the first two, the listing of csrc/side/ and what ``all_side_libs()`` returns are
+# pinned by the tests written with them, so neither can take a row.  A library added from now on is a row HERE -- the same row type, the
+# same flags, the same compile routine -- and a directory csrc/<name>/ of its own, its object beside its source (<variant objdir>/<name>/
+# for a variant).  No fourth table is needed for the next one: the tests of a row of this table speak of that row alone, never of the
+# table's whole contents or of a directory listing.
+
+
+def _later(name, *headers):
+    return SideLib([f"{name}/prd_{name}.hip"], [os.path.join(_INCLUDE, f"prd_{name}.h"), PRD_LAUNCH_H, *headers], os.path.join(HERE, f"libprd_{name}.so"),
+                   f"--{name}", False)
+
+
+LATER_SIDE_LIBS = {"sasa": _later("sasa")}
+
+
 def side_lib(name):
-    """the row of the side library ``name``, from either table"""
-    return SIDE_LIBS[name] if name in SIDE_LIBS else MORE_SIDE_LIBS[name]
+    """the row of the side library ``name``, from any of the three tables"""
+    return every_side_lib()[name]
 
 
 def all_side_libs():
-    """{name: row} of both tables, the first table first"""
+    """{name: row} of the first two tables, the first table first (what it returned when the second was closed)"""
     return {**SIDE_LIBS, **MORE_SIDE_LIBS}
+
+
+def every_side_lib():
+    """{name: row} of all three tables, in the order of the tables"""
+    return {**SIDE_LIBS, **MORE_SIDE_LIBS, **LATER_SIDE_LIBS}
 
 # A variant of the library: flags added to every compile, flags added to the link, object directory, library, and -- for a variant
 # that differs from the shipped one by a macro alone -- that macro: a source that never tests it shares the shipped object.
@@ -129,7 +150,7 @@ def _hipcc():
 
 def _headers(src):
     """the headers an object of ``src`` depends on"""
-    return next((s.headers for s in all_side_libs().values() if src in s.sources), HEADERS)
+    return next((s.headers for s in every_side_lib().values() if src in s.sources), HEADERS)
 
 
 def _stamp(src):
@@ -203,7 +224,7 @@ def _build(v: Variant, sources, force: bool = False, verbose: bool = True) -> st
                     continue
         obj = os.path.join(v.objdir, src.replace(".hip", ".o"))
         objs.append(obj)
-        os.makedirs(os.path.dirname(obj), exist_ok=True)          # a source of the second table lies in a subdirectory, and so does its object
+        os.makedirs(os.path.dirname(obj), exist_ok=True)          # a source of the later tables lies in a subdirectory, and so does its object
         if not (force or _stale(obj, [spath] + _headers(src))):
             continue
         cmd = [_hipcc()] + FLAGS + EXTRA_FLAGS.get(src, []) + v.cflags + ["-c", spath, "-o", obj]
@@ -229,7 +250,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
 
 def build_side(name: str, force: bool = False, verbose: bool = True, variant: str = "shipped") -> str:
-    """The side library ``name`` of SIDE_LIBS or MORE_SIDE_LIBS: its source with the committed FLAGS and the shipped variant's extras, its object beside
+    """The side library ``name`` of SIDE_LIBS, MORE_SIDE_LIBS or LATER_SIDE_LIBS: its source with the committed FLAGS and the shipped variant's extras, its object beside
     the denoiser's.  Not a variant of libprd_hip.so: ``build()`` compiles none of it, and no side library compiles another.
     Another ``variant`` ("trace", "asan"): that variant's flags and object directory, the library libprd_<name>_<variant>.so."""
     s, v = side_lib(name), VARIANTS[variant]
@@ -318,12 +339,12 @@ if __name__ == "__main__":
         sys.exit(subprocess.call([build_trace()]))
     if "--trace-side" in sys.argv:
         sys.exit(subprocess.call([build_trace_side()]))
-    for side, s in all_side_libs().items():
+    for side, s in every_side_lib().items():
         if s.flag in sys.argv:
             print(build_side(side, force="--force" in sys.argv))
             sys.exit(0)
     if "--resources" in sys.argv:                   # the denoiser's kernels, then those of each side library
-        for sources in [SOURCES] + [s.sources for s in all_side_libs().values()]:
+        for sources in [SOURCES] + [s.sources for s in every_side_lib().values()]:
             for name, u in sorted(resource_usage(verbose=True, sources=sources).items()):
                 print(f"{u['vgprs']:4d} VGPR {u['agprs']:3d} AGPR {u['scratch']:5d} B scratch  occ {u['occupancy']}  LDS {u['lds']:6d}  {name}")
         sys.exit(0)

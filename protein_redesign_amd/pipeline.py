@@ -791,6 +791,37 @@ def _secondary_structure(spec, data, on_device, na, nr):
     return out
 
 
+def _accessibility(spec, data, on_device, pos, first_batch, na, nr):
+    """Stage (d'''), ``accessibility=``: the Shrake-Rupley counts of the built atoms and the ligand rows of every sample
+    (``sasa.measure``: two launches) on the device tensors of ``backbone.build`` as the stage before left them and on ``pos[:, :na]``,
+    and -- when the input has N, CA, C and O -- the same call on the input's own atoms and the share of residues a sample calls
+    buried or exposed as the input does.  Returns the dict of numpy values."""
+    from . import sasa as SA
+    got, mask, _ = on_device
+    device = got.atoms.device
+    elements = first_batch["atom_feats"][0, :na, 0]
+    rows = mask[na: na + nr]
+    up = SA.upload(spec, device)
+    found = SA.measure(got.atoms[:, na: na + nr], got.built[:, na: na + nr], pos[:, :na].float(), elements, rows, up)
+    out = dict(found)
+    ram, rap = torch.as_tensor(data["residue_atom_mask"]), torch.as_tensor(data["residue_atom_pos"], dtype=torch.float32)
+    has = ram[:, :5] > 0.5
+    whole = has[:, 0] & has[:, 1] & has[:, 2] & has[:, 4]         # marked, and with coordinates (an input from its sequence alone has none)
+    if _ca_trace_problem(data) is None and bool(whole.any()) and bool((rap[whole][:, [0, 2, 4]] != 0).any()):
+        atoms = torch.where(has[:, :, None], rap[:, :5], torch.zeros(()))[None].contiguous()
+        built = (has.to(torch.int32) << torch.arange(5, dtype=torch.int32)).sum(1).to(torch.int32)[None]
+        has_ligand = na > 0 and "atom_pos" in data and bool((torch.as_tensor(data["atom_pos"]) != 0).any())
+        ligand = torch.as_tensor(data["atom_pos"], dtype=torch.float32)[None, :na] if has_ligand else torch.zeros(1, 0, 3)
+        own = SA.measure(atoms.to(device), built.to(device), ligand.to(device), elements[: ligand.shape[1]], rows, up)
+        both = found["complete"] & own["complete"]                # [S,nr]: the residues whole in both
+        total = both.sum(1).to(torch.float64)
+        agree = ((found["buried"] == own["buried"]) & both).sum(1) / total.clamp(min=1)
+        out.update(input_relative=own["relative"][0], burial_agreement=torch.where(total > 0, agree, torch.full_like(total, float("nan"))))
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    out.update(spec.describe())
+    return out
+
+
 def _with_backbone(proteins, built):
     """the proteins with the built atoms in ``atom_pos`` / ``atom_mask`` (atom37 indices 0 .. 4: N, CA, C, CB, O); CA stays what
     ``update_pos`` made it, and CB is left out of a residue decoded as G or left undetermined"""
@@ -808,7 +839,7 @@ def _with_backbone(proteins, built):
 
 
 def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffold=None, sequences=None, guided=None, handed=None, built=None,
-           secondary=None):
+           secondary=None, accessibility=None):
     """Stage (f): the files of ``output_dir``"""
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
@@ -849,6 +880,14 @@ def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffol
             f.write("# one line per sample, one letter per residue: - coil, H alpha helix, B bridge, E strand, G 3-10 helix, I pi helix, T turn, S bend\n")
             for line in secondary["strings"]:
                 f.write(line + "\n")
+    if accessibility is not None:
+        from .sasa import SCALAR_COLUMNS as AREA_COLUMNS
+        cols = [c for c in AREA_COLUMNS if c in accessibility]
+        np.savez(out / "sample_accessibility.npz", **accessibility)
+        with open(out / "sample_accessibility.txt", "w") as f:
+            f.write("# " + " ".join(cols) + "\n")
+            for k in range(len(proteins)):
+                f.write(" ".join(str(accessibility[c][k].item()) for c in cols) + "\n")
     if sequences is not None:
         np.savez(out / "sample_sequences.npz", **{k: (np.array(v) if k == "sequences" else v) for k, v in sequences.items()})
         with open(out / "sample_sequences.fasta", "w") as f:
@@ -861,7 +900,7 @@ def _write(output_dir, proteins, ligands, used_mask, alignment, quality, scaffol
 def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_size: int = 1, seed: int = 0,
                      output_dir: Optional[Union[str, Path]] = None, redesign=None, align_to=None, mirror: bool = True,
                      correspondence: str = "index", assess=None, scaffold=None, sequence_rules=None, decode=None, solver=None,
-                     guidance=None, backbone=None, secondary=None, handedness=None):
+                     guidance=None, backbone=None, secondary=None, accessibility=None, handedness=None):
     """Draw ``num_samples`` samples of one featurised complex ``data`` (the dict of ligand_to_data ∪ protein_to_data).
 
     Returns (positions [S,N,3] in Angstrom, logits [S,N,21], proteins, ligand_positions).  With ``output_dir`` the CA
@@ -1008,7 +1047,28 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     ``output_dir`` also receives ``sample_secondary.npz`` (the dict) and ``sample_secondary.txt``: a ``#`` line, then one class string
     per sample.  Every quantity is a function of distances, so a mirror image is classed like the original.  Nothing is claimed about
     accuracy on real proteins: off the builder's anchor conformations its oxygen is off by up to 1.2 Angstrom, and strand pairing from
-    BUILT atoms is expected to be fragile."""
+    BUILT atoms is expected to be fragile.
+
+    ``accessibility`` (``"measure"`` or a sasa.Accessibility, keyword only, default None: nothing below happens, every launch, draw,
+    return value and file is what it was): how buried every residue is, how much of the ligand's surface the protein covers and the area
+    of their interface, with ``protein_redesign_amd.sasa`` on the device -- Shrake and Rupley's point count (include/prd_sasa.h) on the
+    built atoms N, CA, C, CB and O of every residue and the ligand rows ``positions[:, :na]``, each with its van der Waals radius plus the
+    probe, the ligand's by the element of ``atom_feats[..., 0]``.  It needs the atoms: ``accessibility`` without ``backbone`` is refused
+    before the model is touched (use ``backbone="build"``), and so is any other value.  The stage runs after the backbone stage (and
+    after ``secondary``), on the device tensors ``backbone.build`` left; a residue that kept its C-alpha alone contributes that C-alpha,
+    and CB takes part on every built residue -- the decoded sequence is NOT consulted.  The return value gains one more trailing ``dict``
+    of numpy values, after the secondary-structure dict: ``atom_area`` [S,nr,5] (Angstrom^2), ``residue_area``, ``relative`` (the
+    residue's area over ``sasa.REFERENCE_AREA``, the same residue in an extended chain), ``buried`` (relative < buried_below) and
+    ``complete`` (N, CA, C and O present), each [S,nr]; ``ligand_area`` and ``ligand_area_free`` [S,na] (in the complex / the ligand
+    alone); ``ligand_buried_fraction`` [S]; ``interface_area`` [S] (what both partners lose on complexation); ``interface_residues``
+    [S,nr] (residues that lose area to the ligand); ``total_area`` and ``buried_residues`` [S]; and the spec (``probe``, ``points``,
+    ``buried_below``, ``backbone_radii``, ``ligand_radii`` [119], ``reference_area``).  When the input's ``residue_atom_mask`` has N, CA,
+    C and O, also ``input_relative`` [nr] -- the same call on the input's own atoms (with its ligand, when it has coordinates) -- and
+    ``burial_agreement`` [S], the share of residues called buried or exposed as in the input, over the residues whole in both.
+    ``output_dir`` also receives ``sample_accessibility.npz`` (the dict) and ``sample_accessibility.txt``: a ``#`` line naming the
+    columns, then one line per sample holding the scalar columns of ``sasa.SCALAR_COLUMNS`` (those present).  The counts are exact
+    integers; nothing is claimed about real proteins: without side chains beyond CB the areas are those of a poly-alanine-like model
+    and overestimate exposure.  The point lattice is not mirror-symmetric: a mirror image gets nearly, not exactly, the same areas."""
     if guidance is not None:
         from .guidance import check_guidance
         check_guidance(guidance)
@@ -1025,6 +1085,11 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         secondary = Dssp.of(secondary)
         if backbone is None:
             raise ValueError("secondary= assigns secondary structure from N, C and O, which the samples do not have: use it with backbone=\"build\"")
+    if accessibility is not None:
+        from .sasa import Accessibility
+        accessibility = Accessibility.of(accessibility)
+        if backbone is None:
+            raise ValueError("accessibility= measures the surface of N, CA, C, CB and O, which the samples do not have: use it with backbone=\"build\"")
     struct_ref, align_ref, quality_ref, spec = _references(model, data, redesign, align_to, correspondence, assess, scaffold,
                                                            sequence_rules, decode, handedness)
     device = model.device
@@ -1057,7 +1122,7 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     quality = _assess(pos, first_batch, quality_ref, na, nr) if assess is not None else None
     guided = _guidance_report(guidance, data, pos, first_batch, na, nr) if guidance is not None else None
     pos, alignment = _superpose(pos, data, struct_ref, align_ref, mirror, na, nr) if align_to is not None else (pos, None)
-    built = assigned = None
+    built = assigned = surface = None
     if backbone is not None:
         if handedness is None and scaffold is None:
             warnings.warn("backbone= without handedness=: the builder places L-residues whatever the trace, so a mirror-image sample gets "
@@ -1065,6 +1130,8 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
         built, on_device = _backbone_atoms(backbone, pos, first_batch, na, nr)
         if secondary is not None:
             assigned = _secondary_structure(secondary, data, on_device, na, nr)
+        if accessibility is not None:
+            surface = _accessibility(accessibility, data, on_device, pos, first_batch, na, nr)
     sequences = None
     if decode is not None:
         design = first_batch.get("residue_inv_extra_mask") if first_batch is not None else None      # the prepared batch carries it
@@ -1079,9 +1146,10 @@ def generate_samples(model, data: Mapping[str, Any], num_samples: int, batch_siz
     if built is not None:
         proteins = _with_backbone(proteins, built)
     if output_dir is not None:
-        _write(output_dir, proteins, ligands, used_mask, alignment, quality, kept, sequences, guided, handed, built, assigned)
+        _write(output_dir, proteins, ligands, used_mask, alignment, quality, kept, sequences, guided, handed, built, assigned, surface)
     result = (positions, logits, proteins, ligands) + ((used_mask,) if spec is not None else ())
     result = result + ((alignment,) if alignment is not None else ()) + ((quality,) if quality is not None else ())
     result = result + ((kept,) if kept is not None else ()) + ((sequences,) if sequences is not None else ())
     result = result + ((guided,) if guided is not None else ()) + ((handed,) if handed is not None else ())
-    return result + ((built,) if built is not None else ()) + ((assigned,) if assigned is not None else ())
+    result = result + ((built,) if built is not None else ()) + ((assigned,) if assigned is not None else ())
+    return result + ((surface,) if surface is not None else ())
